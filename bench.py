@@ -16,7 +16,12 @@ BEFORE anything touches a GPU (fresh child processes, never a re-exec) and fails
 `--exchange lib` takes the per-step all-reduce through the library's own RCCL communicator (dfdb_group_create_rank /
 dfdb_group_count, include/dfdb.h) instead of torch.distributed's.
 
-Beside `value` (config 2, never anything else) the same JSON line carries, as extra keys:
+A plain run sets up, warms up, times --steps steps and prints the line: `value`, `ms_per_step`, the run's `config` and `job_hbm_gbps`.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's row indices and the global count) as float64 .npy files after the timed
+steps: the whole index array when it holds at most 4 Mi rows, else a fixed seeded sample of 2 Mi of them beside their positions.  Everything below
+(the per-kernel roofline, which times the steps with HIP events on, the read probe, and the extra legs) runs only with --full.
+
+With --full, beside `value` (config 2, never anything else) the same JSON line carries, as extra keys:
   configs         BASELINE.json configs 3 / 4 / 5 at their stated per-GPU sizes, at EVERY N (every rank runs them on its own shard; times are the
                   MAX over ranks): "3" (a, b, x: conjunctive predicate + projection [b, x]), "4" (String equality + materialize, flat), "4_dictionary"
                   (the same with K9's 16-bit codes beside the column), "5_shard" (the mixed Int64 + Float64 + FlatStrings scan, count() + sum(x) in ONE
@@ -552,6 +557,26 @@ def finish_line(res, keep_what):
     return out
 
 
+# ------------------------------------------------------------------ --dump-outputs: what the timed path computed, for comparing two builds output for output
+DUMP_WHOLE_MAX = 1 << 22         # index arrays of up to 4 Mi rows are written whole (32 MB as float64)
+DUMP_SAMPLE = 1 << 21            # larger ones: 2 Mi entries at fixed seeded positions, beside those positions (16 + 16 MB)
+
+
+def dump_outputs(d, torch, idx, nsel, count):
+    """idx: the device tensor the last timed step wrote its nsel ascending 1-based row indices into; count: that step's global count.
+    float64 holds every row index exactly (< 2^53).  The sample's positions depend on nsel alone, so two builds that agree on the count sample alike."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if nsel <= DUMP_WHOLE_MAX:
+        np.save(os.path.join(d, "indices.npy"), idx[:nsel].cpu().numpy().astype(np.float64))
+    else:
+        pos = np.sort(np.random.default_rng(SEED & 0xFFFFFFFF).integers(0, nsel, DUMP_SAMPLE))      # in [0, nsel): inside what the step wrote
+        got = idx[torch.from_numpy(pos).to(idx.device)].cpu().numpy()
+        np.save(os.path.join(d, "indices_sample.npy"), got.astype(np.float64))
+        np.save(os.path.join(d, "indices_sample_positions.npy"), pos.astype(np.float64))
+    np.save(os.path.join(d, "count.npy"), np.array([count], dtype=np.float64))
+
+
 # ------------------------------------------------------------------ BASELINE.json configs 3 / 4 / 5 (extra keys, never part of `value`)
 def claim_stdout():
     """This script's stdout is ONE JSON line.  RCCL prints a version banner on stdout from C code the first time a communicator is used (sys.stdout
@@ -1055,7 +1080,8 @@ def main_threads(args, out_fd):
         gq.count_async()                                   # one grouped all-reduce of the count on the engine streams, no host wait
     for _ in range(args.warmup):
         step()
-    ctx0.profile(True)
+    if args.full:
+        ctx0.profile(True)
     grp.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1063,12 +1089,15 @@ def main_threads(args, out_fd):
     grp.synchronize()
     elapsed = time.perf_counter() - t0
     total_sel = gq.count()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, outs[0], cnts[0], total_sel)
     kernels = {}
-    for k in ("scan_cmp", "scan_counts", "compact_indices"):
-        nl, ms = ctx0.profile_get(k)
-        if nl:
-            kernels[k] = dict(launches=nl, avg_ms=ms / nl)
-    ctx0.profile(False)
+    if args.full:
+        for k in ("scan_cmp", "scan_counts", "compact_indices"):
+            nl, ms = ctx0.profile_get(k)
+            if nl:
+                kernels[k] = dict(launches=nl, avg_ms=ms / nl)
+        ctx0.profile(False)
     local_rows = gt.shard(0).view()._query().count()
     scan_row_bytes = 8 + 1 / 8 + 4 / 1024
     scan_ms = kernels.get("scan_cmp", {}).get("avg_ms")
@@ -1085,13 +1114,14 @@ def main_threads(args, out_fd):
                    "launcher": "one process, a host thread per GPU (--mode threads)", "device": info["name"], "global_selected": total_sel,
                    "options": "library defaults (no ctx option set; placement_calibrate = 0)", "placement_calibration": "off"},
         "job_hbm_gbps": total_rows * (8 + 8 * sigma) / (elapsed / args.steps) / 1e9,
-        "roofline": {"bound": "hbm", "kernel": "k_scan_cmp<int64,GT>", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": (achieved / peak) if achieved else None,
-                     "traffic": None, "traffic_source": None, "algorithmic_bytes_per_launch": local_rows * scan_row_bytes, "avg_launch_ms": scan_ms, "kernels": kernels,
-                     "what": "shard 0's kernel (every shard runs the same launch on its own GPU)"},
     }
+    if args.full:
+        res["roofline"] = {"bound": "hbm", "kernel": "k_scan_cmp<int64,GT>", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": (achieved / peak) if achieved else None,
+                           "traffic": None, "traffic_source": None, "algorithmic_bytes_per_launch": local_rows * scan_row_bytes, "avg_launch_ms": scan_ms, "kernels": kernels,
+                           "what": "shard 0's kernel (every shard runs the same launch on its own GPU)"}
     del outs
     gq.close(); gt.close()
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         try:
             L = Legs(torch, None, torch.device("cuda", devices[0]), ctx0, 1, 0, "none", args.config_steps or max(3, min(args.steps, 10)), peak, 0)
             L.shards = n; L.group = grp; L.devices = devices
@@ -1126,6 +1156,9 @@ def main():
                     "or the library's own RCCL communicator behind the C ABI (dfdb_group_create_rank + dfdb_group_count)")
     ap.add_argument("--mode", default="processes", choices=["processes", "threads"], help="processes: one process per GPU (torch.distributed.run or self-spawned ranks); "
                     "threads: ONE process driving --gpus GPUs through dfdb_group_create (a host thread per GPU, ncclCommInitAll) — what a Julia session gets")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the per-kernel roofline (HIP events on during the timed steps), "
+                    "the read probe, the config / interp / unique / groupreduce legs, decode_scan, cold and cpu_baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (row indices, global count) as float64 .npy files under DIR")
     ap.add_argument("--what", action="store_true", help="keep every leg's prose description (`what`) in the line (off: the line stays small enough for a record that keeps its tail)")
     ap.add_argument("--no-configs", action="store_true", help="skip the configs 3 / 4 / 5 legs (extra keys)")
     ap.add_argument("--config-scale", type=float, default=1.0, help="scale the rows of the config legs (functional runs; 1.0 = BASELINE.json's sizes)")
@@ -1236,17 +1269,19 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # what this box / this allocation gives K1's read stream with nothing written beside it (dfdb_table_read_probe: the scan's load shape, no stores): the
-    # ceiling K1's own rate is read against — a slow box or an unlucky placement shows here, a slower kernel does not
+    # --full: what this box / this allocation gives K1's read stream with nothing written beside it (dfdb_table_read_probe: the scan's load shape, no stores):
+    # the ceiling K1's own rate is read against — a slow box or an unlucky placement shows here, a slower kernel does not
     probe_best_ms = probe_avg_ms = None
-    try:
-        probe_best_ms, probe_avg_ms = t.read_probe("x", 10)
-    except Exception as e:
-        print(f"bench.py: read probe failed: {e}", file=sys.stderr)
+    if args.full:
+        try:
+            probe_best_ms, probe_avg_ms = t.read_probe("x", 10)
+        except Exception as e:
+            print(f"bench.py: read probe failed: {e}", file=sys.stderr)
     step()
-    # roofline leg: HIP event pairs around every launch, recorded on the launch stream DURING the timed steps and resolved
+    # --full, roofline leg: HIP event pairs around every launch, recorded on the launch stream DURING the timed steps and resolved
     # after them (no host synchronisation inside the region: dfdb_ctx_profile_get folds them)
-    ctx.profile(True)
+    if args.full:
+        ctx.profile(True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1262,13 +1297,16 @@ def main():
         all_reduce(el, dist.ReduceOp.MAX)
         elapsed = float(el.item())
     total_sel = gq.count() if lib else int(cnt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, out, nsel, total_sel)
 
     kernels = {}
-    for k in ("scan_cmp", "scan_counts", "compact_indices"):
-        n, ms = ctx.profile_get(k)
-        if n:
-            kernels[k] = dict(launches=n, avg_ms=ms / n)
-    ctx.profile(False)
+    if args.full:
+        for k in ("scan_cmp", "scan_counts", "compact_indices"):
+            n, ms = ctx.profile_get(k)
+            if n:
+                kernels[k] = dict(launches=n, avg_ms=ms / n)
+        ctx.profile(False)
 
     # ---- opt-in (--placement): the same step after the engine's one-time placement calibration (query.cpp: place_mask re-places the column and picks a
     # bitmap allocation).  An extra key; `value` above is what a caller gets who sets no option.
@@ -1314,24 +1352,7 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         value = total_rows * args.steps / elapsed
         sigma = nsel / local_rows
-        kname = "k_scan_cmp<int64,GT>"
-        scan_bytes = local_rows * scan_row_bytes
-        scan_ms = kernels.get("scan_cmp", {}).get("avg_ms")
-        achieved = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms else None
         job_bytes = total_rows * (8 + 8 * sigma)       # 8 + 8*sigma B/row for the whole job
-        # HBM traffic of that kernel from the PMC passes (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of this
-        # same command; FETCH_SIZE doubled per the gfx950 correction, calibrated on a known-byte read): profiles/
-        traffic, traffic_src = None, None
-        import glob
-        import re
-        pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_scan_cmp.json")), key=lambda f: -int(re.search(r"r(\d+)_pmc", f).group(1)))
-        for pmc in pmcs:                                   # the newest round's PMC passes first
-            with open(pmc) as f:
-                pj = json.load(f)
-            if pj.get("rows"):
-                traffic = pj["hbm_bytes_per_launch_corrected"] * local_rows / pj["rows"]
-                traffic_src = f"profiles/{os.path.basename(pmc)} (2*FETCH_SIZE + WRITE_SIZE, scaled to rows)"
-                break
         res = {
             "metric": "filtered-scan rows/sec + achieved HBM GB/s, 1e9-row Int64 col, 10% selectivity",
             "value": value, "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1352,10 +1373,28 @@ def main():
                                                           "9 bitmap allocations, the fastest kept (ctx option placement_calibrate, opt-in: --placement; `value` is measured before it)"}
                                                  if pl_n else "off")},
             "job_hbm_gbps": job_bytes / (elapsed / args.steps) / 1e9,
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": peak, "unit": "GB/s",
-                         "frac": (achieved / peak) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": scan_bytes, "avg_launch_ms": scan_ms, "kernels": kernels},
         }
+        if args.full:
+            kname = "k_scan_cmp<int64,GT>"
+            scan_bytes = local_rows * scan_row_bytes
+            scan_ms = kernels.get("scan_cmp", {}).get("avg_ms")
+            achieved = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms else None
+            # HBM traffic of that kernel from the PMC passes (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of this
+            # same command; FETCH_SIZE doubled per the gfx950 correction, calibrated on a known-byte read): profiles/
+            traffic, traffic_src = None, None
+            import glob
+            import re
+            pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_scan_cmp.json")), key=lambda f: -int(re.search(r"r(\d+)_pmc", f).group(1)))
+            for pmc in pmcs:                                   # the newest round's PMC passes first
+                with open(pmc) as f:
+                    pj = json.load(f)
+                if pj.get("rows"):
+                    traffic = pj["hbm_bytes_per_launch_corrected"] * local_rows / pj["rows"]
+                    traffic_src = f"profiles/{os.path.basename(pmc)} (2*FETCH_SIZE + WRITE_SIZE, scaled to rows)"
+                    break
+            res["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": peak, "unit": "GB/s",
+                               "frac": (achieved / peak) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": scan_bytes, "avg_launch_ms": scan_ms, "kernels": kernels}
         if probe_best_ms:
             ceil = local_rows * 8 / (probe_best_ms * 1e-3) / 1e9
             res["roofline"].update({"box_read_ceiling_GBps": ceil, "box_read_ceiling_avg_GBps": local_rows * 8 / (probe_avg_ms * 1e-3) / 1e9,
@@ -1364,7 +1403,7 @@ def main():
         res["config"]["options"] = "library defaults (no ctx option set; placement_calibrate = 0)" if not (lib and args.placement) else "placement_calibrate = 1"
         if calibrated_cfg is not None:
             res["calibrated_config"] = calibrated_cfg
-        if world == 1 and not lib and not args.no_decode_leg:
+        if args.full and world == 1 and not lib and not args.no_decode_leg:
             try:
                 res["decode_scan"] = decode_scan_leg(dfdb, ctx, t, rows, max(3, min(args.steps, 10)), out.data_ptr(), cap, cnt.data_ptr(), torch.cuda.synchronize)
             except Exception as e:      # an extra figure: never fail the bench line for it
@@ -1374,7 +1413,7 @@ def main():
         os.write(out_fd, (json.dumps(finish_line(line, args.what)) + "\n").encode())
 
     # ---- configs 3 / 4 / 5 on every rank (the column of config 2 goes first: the legs bring their own tables)
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         # The legs are extra keys; the headline must survive them.  They exchange between ranks (barriers, the library's group): should a rank
         # ever be left waiting in one (the N > 1 path has only run on one physical GPU so far), a deadline ends EVERY rank's process — rank 0 prints
         # the line first, with whatever legs had finished and a note — instead of the whole run dying in the driver's timeout with nothing printed.
@@ -1400,14 +1439,14 @@ def main():
         watchdog.cancel()
         if res is not None:
             res["configs"] = legs
-    if res is not None and world == 1 and not lib and not args.no_cold:
+    if args.full and res is not None and world == 1 and not lib and not args.no_cold:
         try:
             torch.cuda.empty_cache()
             res["cold"] = cold_leg(dfdb, ctx, torch, dev, args.cold_rows, peak, args.cold_chunk_blocks)
         except Exception as e:          # an extra figure: never fail the bench line for it
             res["cold"] = {"error": f"{type(e).__name__}: {e}"}
     if res is not None:
-        if not args.no_cpu and world == 1:      # the CPU baseline is an N=1, rank-0 figure
+        if args.full and not args.no_cpu and world == 1:      # the CPU baseline is an N=1, rank-0 figure
             res["cpu_baseline"] = cpu_baseline(args.cpu_rows, 3)
         emit(res)
     if world > 1:

@@ -111,7 +111,7 @@ def test_bench_over_real_devices_with_nccl(oracle, exchange):
     the library's own communicator: one line, N GPUs, the global count the oracle's, every config leg present"""
     n = min(_need_devices(2), 8)
     rows = 20_000_000
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--exchange", exchange, "--rows", str(rows), "--steps", "3", "--warmup", "1", "--no-cpu",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--exchange", exchange, "--rows", str(rows), "--steps", "3", "--warmup", "1", "--full", "--no-cpu",
                         "--config-scale", "0.004"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -136,7 +136,7 @@ def test_bench_threads_mode_over_real_devices(oracle):
     n = min(_need_devices(2), 8)
     rows = 20_000_000
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "threads", "--gpus", str(n), "--rows", str(rows), "--steps", "3", "--warmup", "1",
-                        "--config-scale", "0.004"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
+                        "--full", "--config-scale", "0.004"], env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     r = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])
     assert r["n_gpus"] == n and "RCCL" in r["config"]["sharding"]

@@ -49,7 +49,7 @@ def main():
         return sum(fv) / len(fv), sum(wv) / len(wv), [len(fv), len(wv)]
 
     fk, wk, n1 = per_launch("k_scan_cmp")
-    out = {"command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-configs --no-cold ; the same with "
+    out = {"command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-configs --no-cold ; the same with "
                       "--pmc WRITE_SIZE (separate passes: the TCC cannot hold both). Round 6; tools/r6_profiles.sh + tools/r6_collect.py.",
            "kernel": "dfdb::k_scan_cmp<long, GT, false, nt=true, false>", "rows": rows, "launches": n1,
            "FETCH_SIZE_KB_per_launch": fk, "WRITE_SIZE_KB_per_launch": wk,

@@ -2,7 +2,7 @@
 """print the interesting figures of one bench.py JSON line: python tools/r4_show_bench.py file.json"""
 import json, sys
 r = json.load(open(sys.argv[1]))
-print("value", r["value"], "ms/step", r["ms_per_step"], "K1 frac", r["roofline"]["frac"], "|", r["config"].get("options"))
+print("value", r["value"], "ms/step", r["ms_per_step"], "K1 frac", (r.get("roofline") or {}).get("frac"), "|", r["config"].get("options"))
 for k, v in r.get("configs", {}).items():
     if k == "interp":
         for e, x in v.items():
