@@ -198,6 +198,14 @@ void query_unique(dfdb_query* q, int32_t p);
 void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes);
 void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f);
 void query_return_mask(dfdb_query* q);            // give a borrowed calibrated bitmap back to its column
+// query.cpp helpers that unique.cpp builds on
+size_t padded_words(int64_t nrows);               // bitmap words for n rows, padded so that K2's 64-word (4096-row) reads stay in bounds
+uint64_t splitmix64_host(uint64_t x);
+const Column& need_resident(dfdb_table* t, int ordinal);
+void selection_changed(dfdb_query* q);            // the bitmap changed outside query_execute: drop what was derived from it
+void scan_prefix(dfdb_query* q);                  // tile counts -> prefix
+void ensure_executed_checked(dfdb_query* q);
+void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt);
 void set_string_tile_offsets(dfdb_ctx* ctx, Column& c);   // K4 over a resident string column
 bool read_file_range(const std::string& file, uint8_t* dst, int64_t lo, int64_t hi);   // table.cpp: parallel pread
 bool read_file_range_fd(int fd, uint8_t* dst, int64_t lo, int64_t hi);

@@ -15,10 +15,9 @@
 // 8 + 12 + 12 bytes per selected row, all streams.  The order of a partition's records depends on timing; the result (smallest row per key) does not.
 // A key that a large part of the rows hold (one partition = one workgroup's work) is kept out of the records: the partition pass gives it one of a workgroup's
 // 256 LDS slots (HOT KEYS, below) and the table pass gets one list entry per workgroup and key instead.
-// A partition that holds more distinct keys than its table takes raises a flag and the host runs the hash-table form instead (query.cpp: unique_hashed); keys
+// A partition that holds more distinct keys than its table takes raises a flag and the host runs the hash-table form instead (unique.cpp: unique_hashed); keys
 // are isequal images (one NaN, -0.0 apart from 0.0), a missing key and the one image that cannot be stored (all ones) are kept aside in aux[1] / aux[0]
 // exactly as k_unique_insert keeps them.  Measured history: profiles/r6_unique_radix.txt; what the instruction and store choices rest on: tools/ubench/.
-#include <cstdlib>
 #include "device_utils.hpp"
 #include "kernels.hpp"
 #include "../../include/dfdb_ir.h"
@@ -145,7 +144,7 @@ template <int KIND> __device__ __forceinline__ uint64_t keys_storable(uint64_t& 
   return __ballot(k != kREmpty);                                // (called with every lane active: the compare's result as it stands)
 }
 
-// ---- the SAMPLE: counts[p] = selected rows whose key falls into partition p among every `step`-th tile (query.cpp looks at the largest partition before anything
+// ---- the SAMPLE: counts[p] = selected rows whose key falls into partition p among every `step`-th tile (unique.cpp looks at the largest partition before anything
 // is written: a skewed column gets the partition kernels that look for hot keys).  The partition pass needs no counts: it takes pages from a pool as it goes.
 template <int KIND>
 __global__ __launch_bounds__(kRBlock) void k_radix_hist(const uint64_t* __restrict__ sel, const void* __restrict__ col, int dtype, const uint64_t* __restrict__ missing,
@@ -232,7 +231,7 @@ __device__ __forceinline__ void acc_value(uint64_t* slot, uint64_t v, int gop, i
 template <int KIND, int BLOCK, bool HASVAL, bool V8, bool HOT>
 __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __restrict__ sel, const void* __restrict__ col, int dtype, const uint64_t* __restrict__ missing,
                                                              int64_t nrows, int64_t rows_per_chunk, int kbits, RadixPool pool,
-                                                             uint32_t* __restrict__ recs_out, uint64_t* aux, RadixVals vals, int xp) {
+                                                             uint32_t* __restrict__ recs_out, uint64_t* aux, RadixVals vals) {
   __shared__ uint64_t spec_sh[4];                               // HASVAL: {rows, reduced value} of the rows whose key is the unstorable image, then of the rows whose key is missing: this workgroup's
   __shared__ uint64_t hc_key[HOT ? kHotSlots : 1], hc_val[HOT && HASVAL ? kHotSlots : 1];      // the hot keys' slots: key, (HASVAL) reduced value, ...
   __shared__ uint32_t hc_cnt[HOT ? kHotSlots : 1], hc_row[HOT ? kHotSlots : 1], hc_any;         // ... rows, smallest row; whether any slot is taken
@@ -336,7 +335,7 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
       else nmiss = tile_load<KIND, false>(nkey, nin, sel, col, dtype, missing, nb, nrows, wv, lane);
     }
     __syncthreads();
-    if (xp & 8) continue;                                       // (bit 3, timing only: loads and ranks only)
+    asm volatile("" ::: "memory");                              // (step 1 ends here for the compiler too: without this fence the register allocation of steps 2-4 spills more)
     // 2. exclusive scan of the tile's counts (thread p owns partition p; its count is cleared for the next tile as it is read)
     uint32_t h = 0;
     if (tid < P) { h = hist2[tid]; hist2[tid] = 0; }
@@ -354,7 +353,6 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
     uint32_t got = 0;
     if (tid < P) { lstart[tid] = ex; if (h) got = atomicAdd(&pool.front[fx], h); } // the tile's run of partition `tid`: reserved behind whatever the XCD's other workgroups reserved last
     __syncthreads();
-    if (xp & 4) continue;                                       // (bit 2, timing only: ranks and scan only)
     // 3. the tile's records into LDS, sorted by partition (the eight reads of lstart first, unconditionally: a branch per row made each wait for its own)
     uint32_t ls[8];
 #pragma unroll
@@ -373,7 +371,7 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         val[j] = 0;
-        if (vals.col && !(xp & 256) && pr[j] != ~0u)                                           // (bit 8, timing only: no values)
+        if (vals.col && pr[j] != ~0u)
           val[j] = rvalue_of<V8>(vals.col, vals.vdt, base + lo + (uint32_t)(j * 64));
       }
     }
@@ -411,7 +409,6 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
       place[tid] = pl;
     }
     __syncthreads();
-    if (xp & 2) continue;                                       // (bit 1, timing only: nothing after the sort)
     // 4. out: all the LDS reads, then the stores
     uint64_t ok[8]; uint32_t ow[8]; uint4 od[8];
 #pragma unroll
@@ -437,7 +434,6 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
       const uint32_t s = (uint32_t)(k * BLOCK + tid);
       if (s < total) {
         const uint32_t dst = s + (s < od[k].z ? od[k].x : od[k].y);
-        if (xp & 1) { if (ok[k] == 12345ull) recs_out[dst] = 1; continue; }              // (DFDB_RADIX_XP bit 0, timing only: no stores)
         // one 12-byte record {key image, row}: a partition's run of a tile is ONE piece of 192 bytes, not 128 + 64 in two arrays (the pass waits for its
         // stores, and what they cost goes by the number of pieces: tools/ubench/scatter_runs.hip; as nontemporal stores: 7.4 ms instead of 6.15)
         if (HASVAL) {
@@ -504,7 +500,7 @@ __device__ __forceinline__ void recs_load(uint64_t (&kk)[4], uint32_t (&rw)[4], 
   }
 }
 __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __restrict__ recs, RadixPool pool,
-                                                          int P, uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, uint64_t* aux, int kbits, int xp) {
+                                                          int P, uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, uint64_t* aux, int kbits) {
   extern __shared__ uint64_t tab_sh[];
   uint64_t* tkey = tab_sh;                                    // [kRSlots]
   uint32_t* trow = (uint32_t*)(tkey + kRSlots);               // [kRSlots]
@@ -557,7 +553,6 @@ __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __rest
       }
       next_block(cp, cc);
       if (cc) { if (cc == 4u * kRBlock) recs_load<true>(nk, nr, cp, cc, tid); else recs_load<false>(nk, nr, cp, cc, tid); }
-      if (xp & 32) { if ((kk[0] ^ kk[1] ^ kk[2] ^ kk[3]) == 12345ull && (rw[0] ^ rw[1] ^ rw[2] ^ rw[3]) == 77u) abort_sh = 1; continue; }   // (DFDB_RADIX_XP bit 5, timing only: the loads alone)
       uint32_t hb[4]; ulonglong2 tt[4]; uint2 qq[4];
 #pragma unroll
       for (int j = 0; j < 4; j++) hb[j] = table_home(kk[j]);
@@ -572,7 +567,6 @@ __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __rest
         bool pending = false;
         if (e0 | e1) { if ((e0 ? qq[j].x : qq[j].y) > rw[j]) atomicMin(&trow[hb[j] + (e0 ? 0u : 1u)], rw[j]); }
         else pending = kk[j] != kREmpty;                      // (an absent record compares equal to an empty slot — its row, all ones, changes nothing — or is skipped here)
-        if (xp & 64) pending = false;                         // (DFDB_RADIX_XP bit 6, timing only: nothing is claimed)
         const uint64_t pm = __ballot(pending);
         if (pm) {
           if (pending) { const uint32_t e = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u)); qk[e] = kk[j]; qr[e] = rw[j]; }
@@ -790,7 +784,6 @@ int64_t radix_rows_per_chunk(int64_t nrows, int chunks) {
   const int64_t per = (nrows + chunks - 1) / chunks;
   return (per + kRTile - 1) / kRTile * kRTile;              // whole tiles of the partition pass (and whole bitmap words)
 }
-static int radix_xp() { static const int v = [] { const char* e = getenv("DFDB_RADIX_XP"); return e ? atoi(e) : 0; }(); return v; }   // timing experiments only: results are WRONG with any bit set
 static size_t radix_partition_lds_bytes(int block) { return (size_t)part_lds_words(block) * 4 + (size_t)block * 8 * 8; }
 static int radix_kind(int dtype) { return dtype == DFDB_F64 ? kKindF64 : (dtype == DFDB_I64 || dtype == DFDB_U64 ? kKindRaw8 : kKindAny); }
 int radix_share() { return kRShare; }
@@ -817,11 +810,10 @@ bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const void* col, in
 template <int KIND, bool HASVAL, bool V8, bool HOT>
 static bool radix_partition_go(hipStream_t s, const uint64_t* sel, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int kbits, int chunks,
                                const RadixPool& pool, uint32_t* recs_out, uint64_t* aux, const RadixVals& vals) {
-  static const bool ok = hipFuncSetAttribute((const void*)k_radix_partition<KIND, kRBlock, HASVAL, V8, HOT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)radix_partition_lds_bytes(kRBlock)) == hipSuccess;      // (+ the static arrays: under 160 KB)
-  if (!ok) { (void)hipGetLastError(); return false; }
+  if (!allow_dynamic_lds((const void*)k_radix_partition<KIND, kRBlock, HASVAL, V8, HOT>, radix_partition_lds_bytes(kRBlock))) return false;      // (+ the static arrays: under 160 KB)
   hipLaunchKernelGGL((k_radix_partition<KIND, kRBlock, HASVAL, V8, HOT>), dim3(chunks), dim3(kRBlock), radix_partition_lds_bytes(kRBlock), s, sel, col, dtype, missing, nrows,
-                     radix_rows_per_chunk(nrows, chunks), kbits, pool, recs_out, aux, vals, radix_xp());
-  return true;
+                     radix_rows_per_chunk(nrows, chunks), kbits, pool, recs_out, aux, vals);
+  return hipGetLastError() == hipSuccess;
 }
 // (512-thread workgroups sorting 4096 rows, two per CU, instead of one of 1024 sorting 8192: 5.36-5.43 ms against 5.32-5.33 — the pass waits for its stores either way)
 // group = nullptr: 12-byte records for unique; otherwise 20-byte records {key, row, value} for groupreduce (group->valcol may be null: count only)
@@ -846,24 +838,22 @@ bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const void* col,
 bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux,
                         const RadixGroup& group, int cus) {
   const size_t lds = (size_t)kGSlots * 24 + (size_t)(kRBlock / 64) * kRQueue * 20;
-  static bool ok = [] { return hipFuncSetAttribute((const void*)k_radix_group, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess; }();
-  if (!ok) { (void)hipGetLastError(); return false; }
+  if (!allow_dynamic_lds((const void*)k_radix_group, 156 * 1024)) return false;
   const int P = 1 << kbits;
   hipLaunchKernelGGL(k_radix_group, dim3(P < cus ? P : cus), dim3(kRBlock), lds, s, recs, pool, P, mark ? 1 : 0, bitmap, tile_counts, aux, (uint4*)group.results, group.nres,
                      group.gop, group.vkind, kbits);
-  return true;
+  return hipGetLastError() == hipSuccess;
 }
 void launch_radix_group_finish(hipStream_t s, const RadixGroup& group, const uint64_t* ubits, const uint64_t* uprefix, const uint64_t* aux, uint64_t* cnt, uint64_t* val) {
   hipLaunchKernelGGL(k_radix_group_finish, dim3(1024), dim3(256), 0, s, (const uint4*)group.results, group.nres, ubits, uprefix, aux, group.gspec, cnt, val);
 }
 bool launch_radix_unique(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux, int cus) {
   const size_t lds = (size_t)kRSlots * 12 + (size_t)(kRBlock / 64) * kRQueue * 12;
-  static bool ok = [] { return hipFuncSetAttribute((const void*)k_radix_unique, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) == hipSuccess; }();
-  if (!ok) { (void)hipGetLastError(); return false; }
+  if (!allow_dynamic_lds((const void*)k_radix_unique, 156 * 1024)) return false;
   const int P = 1 << kbits;
   const int grid = P < cus ? P : cus;                       // one 96-KB table per CU at a time
-  hipLaunchKernelGGL(k_radix_unique, dim3(grid), dim3(kRBlock), lds, s, recs, pool, P, bitmap, tile_counts, aux, kbits, radix_xp());
-  return true;
+  hipLaunchKernelGGL(k_radix_unique, dim3(grid), dim3(kRBlock), lds, s, recs, pool, P, bitmap, tile_counts, aux, kbits);
+  return hipGetLastError() == hipSuccess;
 }
 
 }  // namespace dfdb

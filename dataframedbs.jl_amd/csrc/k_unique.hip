@@ -13,7 +13,7 @@
 // The table is sized by the DISTINCT values, which nobody knows beforehand (round 4; it used to be sized by the selected rows:
 // 34 GB of table for 1e9 rows of 1e6 values, every probe a miss in every cache — 86 ms, this form 20): the host feeds the
 // rows in three chunks (1 M rows, 16 M, the rest), reads the number of claimed slots after each, estimates the distinct count
-// of the whole selection from it (query.cpp: unique_capacity_wanted) and MIGRATES the entries to a larger table when needed; a
+// of the whole selection from it (unique.cpp: unique_capacity_wanted) and MIGRATES the entries to a larger table when needed; a
 // probe sequence of kMaxProbe slots raises an abort flag, the host grows the table and repeats that chunk (inserts are idempotent).
 // Fixed-width values are their own keys.  A String's key is a salted 64-bit hash of its bytes; the slot remembers where one
 // holder's bytes start, a verify pass compares every selected row with that representative and reports a true hash collision
@@ -21,7 +21,6 @@
 // Integer keys of a small range take the dense form at the end of this file instead (no hashing: a presence bit per value in LDS).
 #include "device_utils.hpp"
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 #include "kernels.hpp"
 #include "../../include/dfdb_ir.h"
@@ -965,15 +964,10 @@ static bool try_hash_lds(hipStream_t s, const AccArgs& A, const void* gkeys) {
   slots &= ~(size_t)3;
   if (slots < (size_t)A.ngroups + A.ngroups / 4 + 8) return false;             // (a load factor above 0.8: the probes get long)
   const size_t lds = acc + slots * 10;
-  static std::atomic<bool> raised[64] = {};
-  int dev = 0; (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire))) {
-    if (hipFuncSetAttribute((const void*)k_group_acc_hash_lds<OPK>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-  }
+  if (!allow_dynamic_lds((const void*)k_group_acc_hash_lds<OPK>, 156 * 1024)) return false;
   const unsigned g = (unsigned)std::min<int64_t>(256, std::max<int64_t>(1, (A.nrows + 1023) / 1024));
   hipLaunchKernelGGL((k_group_acc_hash_lds<OPK>), dim3(g), dim3(1024), lds, s, A, gkeys, (uint32_t)slots, ngp);
-  return true;
+  return hipGetLastError() == hipSuccess;
 }
 int launch_group_accumulate(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
                              int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* special, uint64_t* cnt, uint64_t* val,
@@ -1329,16 +1323,10 @@ static bool try_dense_lds(hipStream_t s, const AccArgs& A, uint32_t range) {
   const int ngp = (A.ngroups + 1) & ~1;
   const size_t lds = (size_t)ngp * 16 + ((size_t)range + 2) * 4;
   if (lds > 156 * 1024) return false;
-  // (the attribute belongs to the function ON A DEVICE: a process that drives several GPUs raises it on each)
-  static std::atomic<bool> raised[64] = {};
-  int dev = 0; (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire))) {
-    if (hipFuncSetAttribute((const void*)k_group_acc_dense_lds<OPK>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-  }
+  if (!allow_dynamic_lds((const void*)k_group_acc_dense_lds<OPK>, 156 * 1024)) return false;
   const unsigned g = (unsigned)std::min<int64_t>(256, std::max<int64_t>(1, (A.nrows + 1023) / 1024));
   hipLaunchKernelGGL((k_group_acc_dense_lds<OPK>), dim3(g), dim3(1024), lds, s, A, range, ngp);
-  return true;
+  return hipGetLastError() == hipSuccess;
 }
 int launch_group_accumulate_dense(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
                                    int64_t nrows, uint64_t lo, uint32_t range, uint64_t span_lo, uint64_t span_hi, const uint64_t* gids, const uint64_t* aux, uint64_t* cnt, uint64_t* val,

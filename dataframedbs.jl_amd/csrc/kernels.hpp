@@ -7,6 +7,16 @@
 
 namespace dfdb {
 
+// a kernel that may take more than 64 KB of dynamic LDS: its limit raised to `bytes` before EVERY launch (the attribute belongs to the function on the current
+// device, and one process may drive several).  An earlier call's error is cleared first, so that the launcher's hipGetLastError() after the launch is the
+// launch's own.  false, the error cleared: the launch must not be made
+inline bool allow_dynamic_lds(const void* kernel, size_t bytes) {
+  (void)hipGetLastError();
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
+}
+
 enum CmpOp : int { CMP_EQ = 0, CMP_NE = 1, CMP_LT = 2, CMP_LE = 3, CMP_GT = 4, CMP_GE = 5 };
 
 // one simple term `col OP const` of a conjunction/disjunction (K1 multi-column form).  op2 >= 0: the term is the INTERVAL
@@ -159,7 +169,7 @@ void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile
                        uint64_t* aux, uint64_t salt);
 // dense form.  aux words: 1 = smallest missing row, 5 = a key outside [lo, lo + range) was met, 6 = distinct keys, 7 = keys whose first row is known, 8 / 9 = min / max image
 // radix-partitioned form of the hash-table unique (k_radix.hip): partition into a pool of pages -> one LDS table per partition.  false: the launch is
-// not possible (LDS attribute refused, too many partition bits): the caller stays with the hash table.  The pool: `front` [2^kbits x radix_share()] running
+// not possible or refused (LDS attribute refused, too many partition bits, a launch error): the caller stays with the hash table.  The pool: `front` [2^kbits x radix_share()] running
 // positions of the streams (zero before the pass), `pt` [2^kbits x radix_share()][maxv] the streams' pages (all ones before the pass), `next_page` the pool's
 // counter (zero), `dump_page` the page nobody owns (radix_pool_pages() - 1); the records' buffer holds radix_pool_record_bytes().
 struct RadixPool { uint32_t* front; uint32_t* pt; uint32_t* next_page; uint32_t maxv; uint32_t dump_page;
@@ -195,6 +205,19 @@ void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, 
 void launch_dense_group_ids(hipStream_t s, uint64_t* first, uint32_t range, uint64_t* aux, const uint64_t* ubits, const uint64_t* uprefix);
 int launch_group_accumulate_dense(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
                                    int64_t nrows, uint64_t lo, uint32_t range, uint64_t span_lo, uint64_t span_hi, const uint64_t* gids, const uint64_t* aux, uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag = nullptr);
+// K9 (dictionary codes) and groupreduce's group numbers, accumulate passes and finish (k_unique.hip)
+void launch_dict_first_rows(hipStream_t s, const uint64_t* sel, const uint16_t* codes, int64_t nrows, uint64_t* first, int dict_n, int64_t tile0, int64_t tile1);
+void launch_set_rows(hipStream_t s, const uint64_t* rows, int n, uint64_t* bitmap, uint32_t* tile_counts);
+void launch_group_accumulate_codes(hipStream_t s, const uint64_t* sel, const uint16_t* codes, const uint32_t* rank_of_code, const void* valcol, int valdt, int op,
+                                   int64_t nrows, uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
+void launch_group_ids(hipStream_t s, UniqueEntry* ent, uint64_t cap, uint64_t* special, const uint64_t* ubits, const uint64_t* uprefix);
+int launch_group_accumulate(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
+                            int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* special, uint64_t* cnt, uint64_t* val,
+                            int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag = nullptr, const void* gkeys = nullptr);
+void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const void* valcol, int valdt,
+                                 int op, int64_t nrows, const UniqueEntry* ent, const uint64_t* rep_off, const uint32_t* rep_len, uint64_t mask, uint64_t* special, uint64_t salt,
+                                 uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
+void launch_group_finish(hipStream_t s, uint64_t* val, int64_t ng, int kind, int op);
 
 // ---- K7: LZ4 block decode, K8: missing bitmaps, block bodies ---------------------------------------
 // (dst: the decoders may READ up to 32 bytes past the end of the last block's output — far-match sources are fetched 24 bytes at a time — so the

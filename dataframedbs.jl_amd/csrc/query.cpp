@@ -81,7 +81,7 @@ void query_add_stage(dfdb_query* q, Stage&& ns) {
 }
 
 // ---------------------------------------------------------------- device state
-static size_t padded_words(int64_t nrows) { return (size_t)(round_up(nrows > 0 ? nrows : 1, kCTileRows) / 64 + 64); }
+size_t padded_words(int64_t nrows) { return (size_t)(round_up(nrows > 0 ? nrows : 1, kCTileRows) / 64 + 64); }
 
 static void ensure_state(dfdb_query* q) {
   dfdb_table* t = q->t;
@@ -229,11 +229,11 @@ static void place_mask(dfdb_query* q, int ordinal, Launch&& launch /* (uint64_t*
   }
 }
 
-static uint64_t splitmix64_host(uint64_t x) { x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); }
+uint64_t splitmix64_host(uint64_t x) { x += 0x9E3779B97F4A7C15ull; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); }
 
 // (a compressed-only column — keep_compressed = 2 — that reaches a consumer through here gets a whole-column decode for the ABI call in progress:
 //  table.cpp column_data; the paths that need none — K7's fused scan, the survivors' arena of the gathers — do not come through here)
-static const Column& need_resident(dfdb_table* t, int ordinal) {
+const Column& need_resident(dfdb_table* t, int ordinal) {
   Column& c = t->cols[(size_t)ordinal];
   if (!c.resident) fail(DFDB_ERR_ARGUMENT, "column %s is not resident on the device (dfdb_table_load it first)", c.name.c_str());
   if (c.comp_only) (void)column_data(t, c);
@@ -250,11 +250,11 @@ static void raise_reached_errors(dfdb_query* q, int nstages);
 // The bitmap was changed outside query_execute (unique narrowed it to the first occurrences, groupreduce put the full selection back): everything derived
 // from the PREVIOUS bitmap goes — the host count, and the survivors' arenas of compressed-only projection columns, which hold only the blocks that kept a
 // row under the selection they were decoded for (a fetch restored the full selection and a later materialize gathered through the narrowed arena).
-static void selection_changed(dfdb_query* q) {
+void selection_changed(dfdb_query* q) {
   q->count = -1;
   for (auto& a : q->arenas) a.second.valid = false;
 }
-static void scan_prefix(dfdb_query* q) {
+void scan_prefix(dfdb_query* q) {
   dfdb_ctx* ctx = q->t->ctx;
   LaunchTimer lt(ctx, "scan_counts");
   launch_scan_counts(ctx->stream, q->tile_counts.as<uint32_t>(), q->prefix.as<uint64_t>(), ceil_div(q->t->nrows, kTileRows), q->scan_scratch.as<uint64_t>());
@@ -770,7 +770,7 @@ int64_t query_count(dfdb_query* q, int nstages);
 // without the index — where query_count waits for the count (only dfdb_count did so).  Consumers that stay asynchronous on the device
 // (dfdb_select_indices / _bitmap into device memory without a count, the group layer's device aggregates) are covered by the caller's next dfdb_count or
 // dfdb_table_decode_status, as include/dfdb.h says.
-static void ensure_executed_checked(dfdb_query* q) {
+void ensure_executed_checked(dfdb_query* q) {
   ensure_executed(q);
   if (q->decoded_col >= 0 || !q->comp_scanned.empty()) (void)query_count(q, -1);
 }
@@ -964,7 +964,7 @@ int64_t query_string_bytes(dfdb_query* q, int i) {
 }
 
 // one output column of the projection (ProjectionExecutor.eval_on_range for column p: projection.jl:128-154)
-static void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
+void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const Node& e = *q->proj[(size_t)p].expr;
   o.dtype = e.dtype; o.count = cnt; o.nbytes = 0;
@@ -1138,725 +1138,6 @@ void table_add_from_query(dfdb_table* dst, const char* name, dfdb_query* q, int3
   if (dst->nrows < 0) dst->nrows = cnt;
   dst->cols.push_back(std::move(c));
 }
-
-// unique(col) (column.jl:102-126 driving Base.unique; docs/src/index.md:171-182,479-486): the current selection is narrowed to
-// the rows that hold the FIRST occurrence of their value in projection column p (isequal semantics), so count / materialize
-// afterwards return the distinct values in order of first appearance.  A later reset / execute restores the full selection.
-void launch_dict_first_rows(hipStream_t s, const uint64_t* sel, const uint16_t* codes, int64_t nrows, uint64_t* first, int dict_n, int64_t tile0, int64_t tile1);
-void launch_set_rows(hipStream_t s, const uint64_t* rows, int n, uint64_t* bitmap, uint32_t* tile_counts);
-void launch_group_accumulate_codes(hipStream_t s, const uint64_t* sel, const uint16_t* codes, const uint32_t* rank_of_code, const void* valcol, int valdt, int op,
-                                   int64_t nrows, uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
-constexpr int64_t kGroupsInLds = 9216;      // groups a workgroup's LDS accumulators hold (k_unique.hip kGroupLdsBig): above it groupreduce goes by radix
-// what unique leaves behind for groupreduce: the hash table {key, first row} (Strings: + where one holder's bytes are), or — integer keys of a small
-// range — the first row per value; groupreduce turns the rows into group numbers in place
-struct UniqueTables {
-  DevBuf ent, aux, rep_off, rep_len, first, present;
-  uint64_t cap = 0, salt = 0, lo = 0; uint32_t range = 0; bool is_str = false, dense = false;
-  uint64_t span_lo = ~0ull, span_hi = 0;   // dense form: the first / last value index that is present (the table is laid out for the widest span it can hold)
-  // in: the dense form may look at the HEAD of the column only (groupreduce over integer keys, round 5: its accumulate pass meets every row anyway and reports a key
-  // that has no group — one outside the span laid out, or one that first turns up behind the head —, in which case everything runs again over all rows); out: it did
-  bool allow_head = false, head_only = false;
-  bool defer_verify = false;     // in: the caller's own pass over the rows compares every String with its slot's representative (groupreduce's accumulate pass)
-  int salt_skip = 0;             // in: salts already found colliding
-  // in: String keys with defer_verify — if the second insert chunk (16 M rows) met no string the first (1 M rows) had not, the rest of the rows are NOT
-  // inserted: the caller's pass meets every row anyway and reports a string that is not in the table (`optimistic` comes back true; the caller then
-  // runs everything again with allow_optimistic = false).  Ten brands over 5e8 rows: the insert pass 2.2 -> 0.1 ms.
-  bool allow_optimistic = false, optimistic = false;
-  // in: the caller can reduce by radix (group_radix: more groups than LDS accumulators hold) and wants to know EARLY whether that is the case; out: the number of
-  // distinct keys the first chunk's rows promise when it is more than 9216 — and then nothing else was done: the selection is as it was, no table was finished
-  bool group_probe = false; int64_t group_estimate = 0;
-};
-// K9: unique over a String column that has a dictionary — the first selected row of every code, no hash table.  Leaves what unique_impl leaves (the
-// bitmap holds exactly the first occurrences, prefix scanned); rank_of_code (optional) maps a code to its group number in order of first appearance.
-static int64_t dict_unique(dfdb_query* q, const Column& col, DevBuf* rank_of_code) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  const int dn = col.dict_n;
-  DevBuf& first = q->du_first; first.ensure((size_t)dn * 8 + 64);      // (scratch kept on the query: every hipFree synchronises the device)
-  HIP_CHECK(hipMemsetAsync(first.p, 0xFF, (size_t)dn * 8, s));
-  // the first 4 M rows first: a code that has a first row there can only keep it, and a dictionary's codes have usually all turned up by then (ten brands over
-  // 5e8 rows: the pass over all the codes was 0.65 ms of the groupreduce's 2.8) — only if one is still without does the rest of the column get walked
-  const int64_t nt = ceil_div(t->nrows, kTileRows), head = 4096;
-  std::vector<uint64_t> fr((size_t)dn);
-  auto walk = [&](int64_t t0, int64_t t1) {
-    { LaunchTimer lt(ctx, "unique");
-      launch_dict_first_rows(s, q->bitmap.as<uint64_t>(), col.dict_codes.as<uint16_t>(), t->nrows, first.as<uint64_t>(), dn, t0, t1); }
-    HIP_CHECK(hipMemcpyAsync(fr.data(), first.p, (size_t)dn * 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-  };
-  if (nt > 4 * head) {
-    walk(0, head);
-    bool all = true;
-    for (int k = 0; k < dn; k++) all = all && fr[(size_t)k] != ~0ull;
-    if (!all) walk(head, nt);
-  } else walk(0, nt);
-  std::vector<std::pair<uint64_t, uint32_t>> present;
-  for (int k = 0; k < dn; k++) if (fr[(size_t)k] != ~0ull) present.emplace_back(fr[(size_t)k], (uint32_t)k);
-  std::sort(present.begin(), present.end());
-  const int64_t ng = (int64_t)present.size();
-  std::vector<uint64_t> rows((size_t)std::max<int64_t>(ng, 1));
-  std::vector<uint32_t> rank((size_t)dn, 0xffffffffu);
-  for (int64_t g = 0; g < ng; g++) { rows[(size_t)g] = present[(size_t)g].first; rank[present[(size_t)g].second] = (uint32_t)g; }
-  DevBuf& drows = q->du_rows; drows.ensure(rows.size() * 8 + 64);
-  HIP_CHECK(hipMemcpyAsync(drows.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, s));
-  if (rank_of_code) { rank_of_code->ensure(rank.size() * 4 + 64); HIP_CHECK(hipMemcpyAsync(rank_of_code->p, rank.data(), rank.size() * 4, hipMemcpyHostToDevice, s)); }
-  HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
-  HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
-  launch_set_rows(s, drows.as<uint64_t>(), (int)ng, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>());
-  scan_prefix(q);
-  selection_changed(q); q->cap_col = -1; q->cap_col2 = -1; q->cap_str_col = -1; q->agg_col = -1; q->const_str_col = -1;
-  stream_wait(ctx);                                        // rows / rank are pageable host memory
-  return ng;
-}
-constexpr size_t kUniqueAuxBytes = 128;      // k_unique.hip: 0 first row of the key that cannot be stored, 1 first missing row, 2 claimed slots, 3 abort, 4 collision, 5-10 the dense form's (10: found-before snapshot)
-static void unique_reset_aux(dfdb_ctx* ctx, DevBuf& aux) {
-  hipStream_t s = ctx->stream;
-  aux.ensure(kUniqueAuxBytes);
-  HIP_CHECK(hipMemsetAsync(aux.p, 0, kUniqueAuxBytes, s));
-  HIP_CHECK(hipMemsetAsync(aux.p, 0xFF, 16, s));                       // no such row yet
-  HIP_CHECK(hipMemsetAsync((char*)aux.p + 64, 0xFF, 8, s));            // the running minimum (k_dense_minmax)
-  HIP_CHECK(hipMemsetAsync((char*)aux.p + 88, 0xFF, 8, s));            // the smallest present value index (k_dense_count)
-}
-static uint64_t pow2_at_least(uint64_t n) { uint64_t c = 1024; while (c < n) c <<= 1; return c; }
-
-// How many slots the table should have before the next chunk: `d` distinct keys met in the first `r` selected rows, `remaining` rows to come.
-// If the rows so far were nearly all different nothing can be said (every remaining row may bring a key).  Otherwise the distinct count D of the whole
-// selection is estimated as if keys were drawn uniformly — d = D (1 - exp(-r / D)), solved for D — and doubled: skewed data has more rare keys than that,
-// and an estimate that turns out too small costs one more migration (or an aborted chunk), never a wrong result.
-static uint64_t unique_capacity_wanted(uint64_t d, uint64_t r, uint64_t remaining, uint64_t cap, uint64_t capmax) {
-  if (remaining == 0 || r == 0) return cap;
-  double need;
-  if ((double)d > 0.95 * (double)r) need = (double)d + (double)remaining;
-  else {
-    double lo = (double)(d ? d : 1), hi = 20.0 * (double)r;
-    for (int it = 0; it < 64; it++) { const double D = 0.5 * (lo + hi); if (D * (1.0 - std::exp(-(double)r / D)) < (double)d) lo = D; else hi = D; }
-    need = std::min((double)d + (double)remaining, 2.0 * hi + 1024.0);
-  }
-  const uint64_t want = pow2_at_least((uint64_t)(2.0 * need));
-  return std::min(std::max(want, cap), capmax);
-}
-
-// integer keys whose selected values span less than the dense form's range (k_unique.hip, last section).  false: the span is too wide
-static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  const int dt = dt_base(col.dtype);
-  const int64_t limit = std::min<int64_t>(unique_dense_max_range(), ctx_option(ctx, "unique_dense_range", unique_dense_max_range()));
-  const uint64_t* miss = dt_nullable(col.dtype) ? col.missing.as<uint64_t>() : nullptr;
-  const uint64_t flip = dt_issigned(dt) ? (1ull << 63) : 0ull;
-  uint64_t* aux = nullptr;
-  uint64_t distinct = 0;
-  const int64_t nt_all = ceil_div(t->nrows, kTileRows), head_tiles = std::max<int64_t>(1, ctx_option(ctx, "dense_head_tiles", 4096));
-  T.head_only = T.allow_head && nt_all >= 8 * head_tiles;               // (the sample below still looks at the whole column: the span is laid around what IT saw)
-  auto prows = [&]() -> int64_t { return T.head_only ? head_tiles * kTileRows : t->nrows; };      // the rows the presence pass and the first-row launches walk
-  auto minmax = [&](int64_t tile_step, uint64_t* mm) {                 // order-preserving images of the smallest / largest selected key (of every tile_step-th tile)
-    unique_reset_aux(ctx, T.aux);
-    { LaunchTimer lt(ctx, "unique_minmax"); launch_dense_minmax(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t->nrows, tile_step, T.aux.as<uint64_t>()); }
-    HIP_CHECK(hipMemcpyAsync(mm, (char*)T.aux.p + 64, 16, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-  };
-  auto presence = [&](uint64_t lo_im, uint64_t span) -> bool {         // false: a selected key lies outside [lo, lo + span]
-    T.lo = lo_im ^ flip; T.range = (uint32_t)(span + 1);
-    const size_t words = ((size_t)T.range + 31) / 32;
-    T.first.ensure((size_t)T.range * 8 + 64); T.present.ensure(words * 4 + 64);
-    HIP_CHECK(hipMemsetAsync(T.first.p, 0xFF, (size_t)T.range * 8, s));
-    HIP_CHECK(hipMemsetAsync(T.present.p, 0, words * 4, s));
-    unique_reset_aux(ctx, T.aux);
-    aux = T.aux.as<uint64_t>();
-    { LaunchTimer lt(ctx, "unique_presence");
-      launch_dense_presence(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, prows(), T.lo, T.range, T.present.as<uint32_t>(), aux); }
-    uint64_t od[8] = {0, 0, 0, 0, 0, 0, 0, 0};                          // [0] a key outside?  [1] distinct values ... [6], [7] the span of the present values
-    HIP_CHECK(hipMemcpyAsync(od, (char*)T.aux.p + 40, 64, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    distinct = od[1];
-    T.span_lo = od[6]; T.span_hi = od[7];
-    return od[0] == 0;
-  };
-  const int64_t nt = ceil_div(t->nrows, kTileRows);
-  bool placed = false;
-  if (dt_width(dt) <= 2) {                                             // the type's own range fits
-    const int bits = dt_width(dt) * 8;
-    if ((1ull << bits) > (uint64_t)limit) return false;
-    placed = presence(dt_issigned(dt) ? ((uint64_t)(-(int64_t)(1ull << (bits - 1))) ^ flip) : 0ull, (1ull << bits) - 1);
-  } else {
-    // where the keys lie is not known.  A SAMPLE (every nt/256-th tile) says where to expect them: the whole span the form can hold is laid around the sample's
-    // range and the presence pass reports any key outside it — then, and for a small table, the exact range costs a pass of its own (1.3 ms per 1e9 rows)
-    uint64_t mm[2];
-    const int64_t sample_opt = ctx_option(ctx, "unique_dense_sample", 1);
-    const int64_t sample_step = sample_opt == 2 ? std::max<int64_t>(2, nt / 256) : nt / 256;      // (2: a sample even of a small table, every other tile — tests of what follows a sample)
-    if ((sample_step >= 16 || sample_opt == 2) && sample_opt != 0) {
-      minmax(sample_step, mm);
-      if (mm[0] <= mm[1]) {
-        if (mm[1] - mm[0] >= (uint64_t)limit) return false;
-        const uint64_t slack = ((uint64_t)limit - 1 - (mm[1] - mm[0])) / 2;
-        uint64_t lo_im = mm[0] > slack ? mm[0] - slack : 0ull;
-        if (lo_im > ~0ull - ((uint64_t)limit - 1)) lo_im = ~0ull - ((uint64_t)limit - 1);
-        placed = presence(lo_im, (uint64_t)limit - 1);
-      }
-    }
-    if (!placed) {
-      T.head_only = false;                                              // (no sample, or a key outside what it suggested: the exact range, every row)
-      minmax(1, mm);
-      if (mm[0] > mm[1]) mm[0] = mm[1] = flip;                         // every selected key is missing
-      if (mm[1] - mm[0] >= (uint64_t)limit) return false;
-      placed = presence(mm[0], mm[1] - mm[0]);
-    }
-  }
-  if (!placed) fail(DFDB_ERR_DEVICE, "unique: a key outside the range of its column");
-  T.dense = true;
-  { LaunchTimer lt(ctx, "unique_first");
-    // launches of 1 M, 1 M, 2 M, 4 M rows, then four times the last: every row whose value has no first row yet costs an atomic, and rows that run side by side
-    // cannot see each other's — 1e6 values spread over the column are all met within 20 M rows, and met in small steps they cost 1.5 M atomics instead of 4 M
-    const bool sched_default = ctx_option(ctx, "unique_chunk_tiles", 0) <= 0;
-    int64_t step = sched_default ? 1024 : ctx_option(ctx, "unique_chunk_tiles", 0);
-    int launches = 0;
-    const int64_t nt_walk = T.head_only ? head_tiles : nt;
-    int64_t t0 = 0;
-    auto walk = [&](int64_t a, int64_t b) {
-      launch_dense_first(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, a * kTileRows, std::min(prows(), b * kTileRows), T.lo, T.range, distinct, T.first.as<uint64_t>(), aux);
-    };
-    // FEW values: the first 1 M rows in three steps of 16, 112 and 896 tiles — rows that run side by side all see "no first row yet" and all send their atomicMin,
-    // and with seven values those are a million atomics on seven words (2.1 ms: `tools/r5_fewgroups.py`); after sixteen tiles every value has its row and the
-    // launches that follow return at once
-    if (sched_default && distinct <= 4096 && nt_walk >= 1024) {
-      for (int64_t pre : {(int64_t)16, (int64_t)112, (int64_t)896}) { walk(t0, t0 + pre); t0 += pre; }
-      launches = 1;
-    }
-    for (; t0 < nt_walk; t0 += step, step *= (++launches < 2 ? 1 : (launches < 4 ? 2 : 4))) walk(t0, t0 + step);
-  }
-  HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
-  HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
-  { LaunchTimer lt(ctx, "unique_mark"); launch_dense_scatter(s, T.first.as<uint64_t>(), T.range, aux, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>()); }
-  uint64_t st[3];
-  HIP_CHECK(hipMemcpyAsync(st, (char*)T.aux.p + 40, 24, hipMemcpyDeviceToHost, s));      // outside flag, distinct values, values whose first row is known
-  stream_wait(ctx);
-  if (st[0] != 0 || st[1] != st[2]) fail(DFDB_ERR_DEVICE, "unique: the dense form lost a key (outside %llu, distinct %llu, found %llu)", (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2]);
-  return true;
-}
-
-// The radix-partitioned form of the general unique (k_radix.hip, round 6): when the hash table would outgrow the L2s — `d0` distinct values among the first `r0`
-// selected rows say how many the whole selection holds, assuming they turn up evenly: d0 = D (1 - exp(-r0 / D)) — every selected row is written once as a
-// {key image, row} record into one of P partitions (by the top bits of the key's hash) and each partition is reduced through a table in LDS.  Streams instead
-// of one random line per row.  false = not taken (too few or too many distinct values, no room for the 12 bytes per selected row, a partition that outgrew
-// its table): the caller goes on with the hash table; the selection is as it was.
-// What the two radix forms (unique, groupreduce) share on the host: the pool of pages for `nsel` records in 2^kbits partitions (k_radix.hip), its control words —
-// the sample's counts [P], the streams' running positions [P x share], the pool's counter, the hot keys' count, then `extra` bytes the caller lays out (64-byte aligned) — and the hot keys'
-// list.  The temporaries go back to the buffer pool (not through hipFree, which drains the device: 1.5 ms of a 16-ms call once), the stream drained first; the
-// records' scratch stays with the context between calls (hipMalloc / hipFree of 12 GB cost 3-4 ms; buffers above 1 GB never enter the pool; dfdb_ctx_destroy
-// releases it) unless it is more than a quarter of the device's memory.
-struct RadixRun {
-  dfdb_ctx* ctx; int kbits, P, C; int64_t PS; RadixPool pool{}; DevBuf ctl, pt, hot; size_t tail = 0;
-  RadixRun(dfdb_ctx* c, int kb) : ctx(c), kbits(kb), P(1 << kb), C((int)round_up(4 * std::max(1, c->prop.multiProcessorCount), radix_share())), PS((int64_t)(1 << kb) * radix_share()) {}
-  ~RadixRun() {
-    (void)hipStreamSynchronize(ctx->stream);
-    { RecycleScope rs; ctl.release(); pt.release(); hot.release(); }
-    if (ctx->radix_recs.bytes > ctx->prop.totalGlobalMem / 4) ctx->radix_recs.release();
-  }
-  char* extra() const { return (char*)ctl.p + tail; }
-  // false: no room, or more records than a 32-bit place in the pool can name
-  bool prepare(int64_t nsel, bool with_values, size_t extra_bytes) {
-    if (radix_pool_pages(nsel, kbits) * 8192 >= (1ll << 32)) return false;
-    pool.maxv = radix_pool_maxv(nsel, kbits);
-    pool.dump_page = (uint32_t)(radix_pool_pages(nsel, kbits) - 1);
-    pool.hot_cap = (uint32_t)C * (uint32_t)radix_hot_slots();
-    const size_t ctl_words = (size_t)P + (size_t)PS + 16;                 // the sample's counts [P], the streams' running positions [PS], the pool's counter, the hot keys' count
-    tail = (ctl_words * 4 + 63) / 64 * 64;
-    try {
-      ctl.ensure(tail + extra_bytes + 64); pt.ensure((size_t)PS * pool.maxv * 4 + 512);      // (+ 64 entries nobody owns: the table passes read 64 at a time)
-      hot.ensure((size_t)pool.hot_cap * 24 + 64);
-      ctx->radix_recs.ensure((size_t)radix_pool_record_bytes(nsel, kbits, with_values) + 256);
-    } catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); return false; }
-    pool.front = ctl.as<uint32_t>() + P; pool.next_page = ctl.as<uint32_t>() + P + PS; pool.hot_n = ctl.as<uint32_t>() + P + PS + 1; pool.pt = pt.as<uint32_t>(); pool.hot = hot.as<uint64_t>();
-    HIP_CHECK(hipMemsetAsync(ctl.p, 0, tail + extra_bytes, ctx->stream));
-    HIP_CHECK(hipMemsetAsync(pt.p, 0xFF, (size_t)PS * pool.maxv * 4, ctx->stream));
-    return true;
-  }
-  // unique: does some partition hold a large part of all the rows (a value that a third of the column has)?  Every 16th tile is counted (all of them in a small
-  // table: 0.1 ms per 1e9 rows) and the counts come back.  1 = skewed, 0 = not, -1 = the sample could not be launched
-  int skewed(const uint64_t* sel, const void* col, int dt, const uint64_t* miss, int64_t nrows, int times) {      // times: "large" = more than this many average partitions
-    const int step = radix_rows_per_chunk(nrows, C) / 8192 >= 32 ? 16 : 1;
-    { LaunchTimer lt(ctx, "radix_sample");
-      if (!launch_radix_sample(ctx->stream, sel, col, dt, miss, nrows, kbits, C, step, ctl.as<uint32_t>())) return -1; }
-    std::vector<uint32_t> cn((size_t)P);
-    HIP_CHECK(hipMemcpyAsync(cn.data(), ctl.p, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
-    stream_wait(ctx);
-    uint64_t maxp = 0, total = 0;
-    for (int p = 0; p < P; p++) { maxp = std::max<uint64_t>(maxp, cn[(size_t)p]); total += cn[(size_t)p]; }
-    return maxp * (uint64_t)step > 65536 && maxp * (uint64_t)P > (uint64_t)times * total ? 1 : 0;
-  }
-};
-// how many distinct values `cnt` selected rows hold when the first r0 of them held d0, assuming they turn up evenly: d0 = D (1 - exp(-r0 / D)), by bisection
-static double estimate_distinct(uint64_t d0, uint64_t r0, int64_t cnt) {
-  double D = (double)cnt;
-  if (d0 < r0) {
-    double lo = (double)d0, hi = (double)cnt;
-    for (int it = 0; it < 60 && hi - lo > 1.0; it++) { const double mid = 0.5 * (lo + hi); if (mid * (1.0 - std::exp(-(double)r0 / mid)) < (double)d0) lo = mid; else hi = mid; }
-    D = std::min((double)cnt, hi);
-  }
-  return D;
-}
-static bool unique_radix(dfdb_query* q, const Column& col, int64_t cnt, UniqueTables& T, uint64_t d0, uint64_t r0) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  // MEASURED, 1e9 Int64 / Float64 rows of 1e6 distinct values (profiles/r6_unique_radix.txt): sample 0.1 + partition 4.5 + LDS tables 3.2 ms = 8.8-9.3 ms end to end against the
-  // hash table's 19.8 (the first build, with splitmix64, a counting pass and the partition re-hashed on the way out, was 18.4).  The partition pass waits for its STORES
-  // (2.8 ms without them): 192-byte runs behind running positions that one XCD's workgroups share, so that whole lines leave that XCD's L2.  On by default; option = 0: the hash table.
-  const int64_t mode = ctx_option(ctx, "unique_radix", 1);
-  if (mode == 0 || t->nrows >= (1ll << 32) - 8192 || r0 == 0 || d0 == 0) return false;      // (rows and pool positions are 32-bit; all ones is "no row")
-  if (mode < 2 && cnt < (4ll << 20)) return false;                       // (2: a test knob — any size; measured against the hash table down to 3 M selected rows of 1e9: tools/r6_radix_selective.py)
-  const double D = estimate_distinct(d0, r0, cnt);
-  if (mode < 2 && D < 131072.0) return false;                            // the hash table stays in the L2s: nothing to gain
-  int kbits = 8;
-  while (kbits < 10 && D / (double)(1 << kbits) > 2500.0) kbits++;       // (fewer partitions = longer runs per tile of the partition pass; more = emptier tables in the unique pass: 1e6 values -> 512)
-  if (const char* e = getenv("DFDB_RADIX_KBITS")) kbits = std::min(10, std::max(6, atoi(e)));      // (an A/B switch for measurements)
-  if (mode < 2 && D / (double)(1 << kbits) > 5500.0) return false;       // the partitions' tables (8192 slots) would overflow
-  const int dt = dt_base(col.dtype);
-  const uint64_t* miss = dt_nullable(col.dtype) ? col.missing.as<uint64_t>() : nullptr;
-  const int64_t nt = ceil_div(t->nrows, kTileRows);
-  const size_t nw = padded_words(t->nrows);
-  struct Keep {                                                          // the selection, set aside (pooled like RadixRun's temporaries)
-    dfdb_ctx* ctx; DevBuf sel, tc;
-    ~Keep() { (void)hipStreamSynchronize(ctx->stream); RecycleScope rs; sel.release(); tc.release(); }
-  } keep{ctx, {}, {}};
-  DevBuf &sel_keep = keep.sel, &tc_keep = keep.tc;
-  RadixRun run(ctx, kbits);
-  if (!run.prepare(cnt, false, 0)) return false;
-  try { sel_keep.ensure(nw * 8); tc_keep.ensure((size_t)nt * 4 + 64); } catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); return false; }
-  const RadixPool& pool = run.pool; const int C = run.C;
-  DevBuf& recs = ctx->radix_recs;
-  // SKEW: one workgroup reduces one partition, so a value that a large part of the rows hold would be one CU's work while 255 wait.  The sample says whether some
-  // partition holds more than eight average ones; then the partition kernels that keep hot keys out of the records run (k_radix.hip, hot keys: 1.1 ms slower where
-  // nothing is hot, which is why they are not the only ones)
-  const int sk = run.skewed(q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t->nrows, 8);
-  if (sk < 0) return false;
-  if (sk) prof_note(ctx, "unique_radix.skewed");
-  { LaunchTimer lt(ctx, "radix_partition");
-    if (!launch_radix_partition(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t->nrows, kbits, C, pool, recs.as<uint32_t>(), T.aux.as<uint64_t>(), nullptr, sk != 0)) return false; }
-  // the selection is set aside (a partition that outgrows its table means: back to the hash table, over the same selection)
-  HIP_CHECK(hipMemcpyAsync(sel_keep.p, q->bitmap.p, nw * 8, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(tc_keep.p, q->tile_counts.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-  HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, nw * 8, s));
-  HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)nt * 4, s));
-  bool ok;
-  { LaunchTimer lt(ctx, "radix_unique");
-    ok = launch_radix_unique(s, recs.as<uint32_t>(), pool, kbits, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), T.aux.as<uint64_t>(), ctx->prop.multiProcessorCount); }
-  uint64_t aborted = 0;
-  if (ok) { HIP_CHECK(hipMemcpyAsync(&aborted, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s)); stream_wait(ctx); }
-  if (!ok || aborted || ctx_option(ctx, "unique_radix", 1) == 3) {        // (3: a test knob — behave as if a partition had overflowed)
-    HIP_CHECK(hipMemcpyAsync(q->bitmap.p, sel_keep.p, nw * 8, hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(q->tile_counts.p, tc_keep.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));
-    stream_wait(ctx);
-    prof_note(ctx, "unique_radix.fell_back");
-    return false;
-  }
-  prof_note(ctx, "unique_radix.taken");
-  stream_wait(ctx);                                                      // (the temporaries die with this frame)
-  return true;
-}
-
-// the general form: an open-addressing table of {key, first row} sized by the distinct values as they turn up (k_unique.hip)
-static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueTables& T) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  const bool is_str = T.is_str;
-  const int dt = dt_base(col.dtype);
-  const uint64_t* miss = (!is_str && dt_nullable(col.dtype)) ? col.missing.as<uint64_t>() : nullptr;
-  const int64_t nt = ceil_div(t->nrows, kTileRows);
-  const uint64_t capmax = pow2_at_least((uint64_t)cnt * 2);
-  const uint64_t cap0 = std::min(capmax, pow2_at_least(1ull << std::min<int64_t>(40, std::max<int64_t>(10, ctx_option(ctx, "unique_cap0_log2", 21)))));
-  const int64_t c0 = ctx_option(ctx, "unique_chunk_tiles", 0) > 0 ? ctx_option(ctx, "unique_chunk_tiles", 0) : 1024;
-  const int64_t bounds[3] = {std::min(nt, c0), std::min(nt, c0 * 17), nt};
-  auto alloc = [&](UniqueTables& U, uint64_t cap) {
-    U.cap = cap;
-    U.ent.ensure(cap * sizeof(UniqueEntry));
-    HIP_CHECK(hipMemsetAsync(U.ent.p, 0xFF, cap * sizeof(UniqueEntry), s));
-    if (is_str) { U.rep_off.ensure(cap * 8); U.rep_len.ensure(cap * 4); }
-  };
-  auto insert = [&](int64_t t0, int64_t t1) {
-    LaunchTimer lt(ctx, "unique_insert");
-    if (is_str) launch_unique_str(s, 0, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                                  t->nrows, t0, t1, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt);
-    else launch_unique_insert(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t0 * kTileRows, std::min(t->nrows, t1 * kTileRows), T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
-  };
-  uint64_t st[2] = {0, 0};                                             // claimed slots, abort flag
-  auto read_state = [&](uint64_t* selected_before, int64_t tile) {
-    HIP_CHECK(hipMemcpyAsync(st, (char*)T.aux.p + 16, 16, hipMemcpyDeviceToHost, s));
-    if (selected_before) HIP_CHECK(hipMemcpyAsync(selected_before, q->prefix.as<uint64_t>() + tile, 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-  };
-  auto grow = [&](uint64_t cap) {                                      // the entries move to a table of `cap` slots
-    LaunchTimer lt(ctx, "unique_migrate");
-    UniqueTables N; N.is_str = is_str;
-    alloc(N, cap);
-    HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 16, 0, 16, s));
-    launch_unique_migrate(s, T.ent.as<UniqueEntry>(), is_str ? T.rep_off.as<uint64_t>() : nullptr, is_str ? T.rep_len.as<uint32_t>() : nullptr, T.cap, N.ent.as<UniqueEntry>(),
-                          N.rep_off.as<uint64_t>(), N.rep_len.as<uint32_t>(), cap - 1, T.aux.as<uint64_t>());
-    read_state(nullptr, 0);
-    if (st[1]) fail(DFDB_ERR_DEVICE, "unique: %llu entries do not fit a table of %llu slots", (unsigned long long)st[0], (unsigned long long)cap);
-    T.ent = std::move(N.ent); T.rep_off = std::move(N.rep_off); T.rep_len = std::move(N.rep_len); T.cap = cap;
-  };
-  T.salt = 0x51ED270B27B4F3CFull;
-  for (int k = 0; k < T.salt_skip; k++) T.salt = splitmix64_host(T.salt);
-  for (int tries = T.salt_skip;; tries++, T.salt = splitmix64_host(T.salt)) {
-    if (!T.ent.p || T.cap != cap0) { T.ent.release(); alloc(T, cap0); } else HIP_CHECK(hipMemsetAsync(T.ent.p, 0xFF, T.cap * sizeof(UniqueEntry), s));
-    unique_reset_aux(ctx, T.aux);
-    int64_t t0 = 0;
-    uint64_t claims_c0 = 0, rows_c0 = 0;
-    T.optimistic = false;
-    // (a column of FEW keys: the rows of a chunk run side by side, all see an empty slot or a larger first row, and all send their atomic — 1 M rows on seven
-    // slots took 1.1 ms.  Sixteen tiles first: after them the chunk's rows find their key with a smaller row and send nothing.  Inserts are idempotent.)
-    if (bounds[0] > 64) insert(0, 16);
-    for (int c = 0; c < 3; c++) {
-      const int64_t t1 = bounds[c];
-      if (t1 <= t0) continue;
-      uint64_t r = 0;
-      // (numeric keys: only for a caller whose own pass over the rows can report a key without a slot — groupreduce's accumulate pass, defer_verify —, and only when
-      // the distinct keys are few beside the rows, so that the first rows come straight out of the table below)
-      // (String keys too.  After an optimistic break the mark step below must take the first rows straight out of the table — launch_unique_scatter,
-      // `st[0] * 8 <= cnt` — because the per-row mark pass looks every selected row up with an unbounded probe, and a row of the un-inserted tail whose
-      // string the table does not hold would never leave that loop: a GPU hang, which no host-side guard can catch.)
-      if (c == 2 && (is_str || T.defer_verify) && T.allow_optimistic && claims_c0 != ~0ull && st[0] * 8 <= (uint64_t)cnt) { T.optimistic = true; break; }
-      for (;;) {
-        insert(t0, t1);
-        read_state(&r, t1);
-        if (!st[1]) break;
-        if (T.cap >= capmax) fail(DFDB_ERR_DEVICE, "unique: probe sequences of a half-empty table got too long (%llu slots, %llu keys)", (unsigned long long)T.cap, (unsigned long long)st[0]);
-        grow(std::min(capmax, T.cap * 4));                             // (that clears the flag) and the chunk again: inserts are idempotent
-      }
-      // (optimistic: chunk 1 must have fed at least 64 K selected rows and claimed nothing that chunk 0 had not)
-      if (c == 0) { claims_c0 = st[0]; rows_c0 = r; }
-      if (c == 0 && !is_str && T.group_probe && r > 0) {               // groupreduce asks: more groups than LDS accumulators hold?  Then it reduces by radix, first rows included
-        const double D = estimate_distinct(st[0], r, cnt);
-        if (D > (double)kGroupsInLds) { T.group_estimate = (int64_t)D; return; }
-      }
-      if (c == 0 && !is_str && !T.defer_verify && unique_radix(q, col, cnt, T, st[0], r)) return;      // the radix-partitioned form took it: q's bitmap holds the first occurrences
-      else if (c == 1 && !(st[0] == claims_c0 && r >= rows_c0 + 65536)) claims_c0 = ~0ull;
-      if (c == 0 && bounds[1] <= bounds[0]) claims_c0 = ~0ull;
-      const uint64_t want = unique_capacity_wanted(st[0], r, (uint64_t)cnt - std::min<uint64_t>(r, (uint64_t)cnt), T.cap, capmax);
-      if (want > T.cap) grow(want);
-      t0 = t1;
-    }
-    if (!is_str || T.defer_verify) break;
-    // the pass that compares every selected row with its slot's representative.  After an optimistic insert it also meets the rows that were never inserted: a string
-    // the table does not hold raises the abort word and everything runs again with every row inserted (as groupreduce's accumulate pass does it)
-    if (T.optimistic) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));
-    launch_unique_str(s, T.optimistic ? 3 : 1, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                      t->nrows, 0, nt, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt);
-    int hit = 0; uint64_t unknown = 0;
-    HIP_CHECK(hipMemcpyAsync(&hit, (char*)T.aux.p + 32, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    if (T.optimistic && (unknown != 0 || ctx_option(ctx, "groupreduce_optimistic", 1) == 2)) { T.allow_optimistic = false; continue; }   // (2: the test knob, as in groupreduce)
-    if (!hit) break;                                                   // no two different strings shared a key: the table is exact
-    if (tries >= 8) fail(DFDB_ERR_DEVICE, "unique: hash collisions under 8 different salts");
-  }
-  LaunchTimer lt(ctx, "unique_mark");
-  if (st[0] * 8 <= (uint64_t)cnt) {                                    // few distinct values beside the rows: the first rows straight out of the table
-    HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
-    HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)nt * 4, s));
-    launch_unique_scatter(s, T.ent.as<UniqueEntry>(), T.cap, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>());
-  } else if (is_str) {
-    launch_unique_str(s, 2, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                      t->nrows, 0, nt, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt);
-  } else {
-    launch_unique_mark(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.p, dt, miss, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
-  }
-}
-
-static void unique_impl(dfdb_query* q, int32_t p, UniqueTables* keep) {
-  ensure_executed_checked(q);
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
-  if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
-  const Node& e = *q->proj[(size_t)p].expr;
-  if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "unique of a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  const Column& col = need_resident(t, e.col);
-  const int64_t cnt = query_count(q, -1);
-  if (cnt == 0 || t->nrows == 0) return;
-  if (!keep && col.dict_n > 0) { dict_unique(q, col, nullptr); return; }
-  UniqueTables local;
-  UniqueTables& T = keep ? *keep : local;
-  T.is_str = dt_base(col.dtype) == DFDB_STRING; T.dense = false;
-  if (!keep) local.allow_optimistic = ctx_option(ctx, "groupreduce_optimistic", 1) != 0;      // (unique's own compare pass meets every row: the same bargain)
-  {
-    LaunchTimer lt(ctx, "unique");
-    const bool dense = !T.is_str && unique_dense_dtype(dt_base(col.dtype)) && ctx_option(ctx, "unique_dense", 1) != 0 && unique_dense(q, col, T);
-    if (!dense) unique_hashed(q, col, cnt, T);
-  }
-  scan_prefix(q);
-  selection_changed(q); q->cap_col = -1; q->cap_col2 = -1; q->cap_str_col = -1; q->agg_col = -1;
-  stream_wait(ctx);                                        // the tables die here (or stay with the caller: groupreduce looks rows up in them)
-  if (!keep) { RecycleScope rs; local = UniqueTables(); }
-}
-void query_unique(dfdb_query* q, int32_t p) { unique_impl(q, p, nullptr); }
-
-// groupreduce over MORE groups than a workgroup's LDS accumulators hold, by radix (k_radix.hip, round 6): with the first occurrences already in q's bitmap (unique
-// made them: `ng` groups, q->prefix scanned) every selected row of `sel` is written as a {key, row, value} record into one of P partitions, each partition is reduced
-// through a table in LDS, and a key's result goes to the place its first row's rank names.  false = not taken (nothing was written to the outputs): too many groups
-// for the tables, a skewed column, no room — the caller's accumulate pass (global atomics) runs.  85-135 ms -> see profiles/r6_groupreduce_radix.txt.
-// mark: q's bitmap does NOT hold every group's first row yet (unique looked at the head of the column only): the table pass marks them itself — the bitmap is
-// cleared first, scanned afterwards, and *ng_io becomes the number of groups; on false the bitmap is whatever the pass left (the caller restores the selection).
-// (keys: the key column's values, their base dtype and missing bits — or a dictionary's 16-bit codes)
-static bool group_radix(dfdb_query* q, const void* keys, int dt, const uint64_t* kmiss, const Column* vc, int op, int64_t nsel, int64_t* ng_io, const uint64_t* sel, bool mark) {
-  int64_t ng = mark ? *ng_io + *ng_io / 4 + 1024 : *ng_io;                // (marking: an estimate from the head — the tables are sized with room to spare)
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  const int64_t mode = ctx_option(ctx, "unique_radix", 1);
-  if (mode == 0 || t->nrows >= (1ll << 32) - 8192 || dt == DFDB_STRING) return false;
-  int kbits = 9;                                                         // (512 partitions at least: one workgroup reduces one partition, and there are 256 CUs)
-  while (kbits < 10 && ng / (1ll << kbits) > 1200) kbits++;              // (a 4096-slot table at 30 % load)
-  if ((mark ? *ng_io : ng) / (1ll << kbits) > 2400) return false;        // (59 % load: the claims stop a table at 7/8, and that raises the abort word)
-  const int P = 1 << kbits;
-  struct Res { dfdb_ctx* ctx; DevBuf res; ~Res() { (void)hipStreamSynchronize(ctx->stream); RecycleScope rs; res.release(); } } tmp{ctx, {}};
-  RadixRun run(ctx, kbits);
-  if (!run.prepare(nsel, true, 128)) return false;
-  try { tmp.res.ensure((size_t)(mark ? (int64_t)P * radix_group_slots() : ng) * 16 + 256); } catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); return false; }
-  const RadixPool& pool = run.pool; const int C = run.C;
-  DevBuf& recs = ctx->radix_recs;
-  uint64_t* aux = (uint64_t*)run.extra();                                // [0] the unstorable key's first row, [1] the missing key's, [3] abort; [4..7] gspec; [8] nres
-  RadixGroup g{};
-  g.valcol = vc ? vc->data.p : nullptr; g.valdt = vc ? dt_base(vc->dtype) : 0;
-  g.gop = op == DFDB_AGG_SUM ? (q->gr_kind == 2 ? 2 : 1) : (op == DFDB_AGG_MIN ? 3 : (op == DFDB_AGG_MAX ? 4 : 0));
-  if (!vc) g.gop = 0;
-  g.vkind = q->gr_kind; g.results = tmp.res.p; g.gspec = aux + 4; g.nres = (uint32_t*)(aux + 8);
-  HIP_CHECK(hipMemsetAsync(aux, 0xFF, 16, s));                           // aux[0], aux[1] = none
-  if (g.gop == 3) { HIP_CHECK(hipMemsetAsync(aux + 5, 0xFF, 8, s)); HIP_CHECK(hipMemsetAsync(aux + 7, 0xFF, 8, s)); }      // gspec[1], [3]: a minimum starts at all ones
-  // a key that a large part of the rows hold is reduced by the partition pass itself (k_radix.hip, hot keys: the form this replaces sent every one of its rows
-  // through a global atomic on ONE address — 3.6 s per 1e9 rows with a key that 30 % of them hold); the kernels that do so are 0.8-1.1 ms slower where nothing is
-  // hot, so the sample picks: some partition above THREE average ones, and they run
-  const int sk = run.skewed(sel, keys, dt, kmiss, t->nrows, 3);
-  if (sk < 0) return false;
-  if (sk) prof_note(ctx, "group_radix.skewed");
-  { LaunchTimer lt(ctx, "radix_partition");
-    if (!launch_radix_partition(s, sel, keys, dt, kmiss, t->nrows, kbits, C, pool, recs.as<uint32_t>(), aux, &g, sk != 0)) return false; }
-  if (mark) {
-    HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
-    HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
-  }
-  { LaunchTimer lt(ctx, "radix_group");
-    if (!launch_radix_group(s, recs.as<uint32_t>(), pool, kbits, mark, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), aux, g, ctx->prop.multiProcessorCount)) return false; }
-  uint64_t tailw[9] = {};
-  HIP_CHECK(hipMemcpyAsync(tailw, aux, 72, hipMemcpyDeviceToHost, s));
-  stream_wait(ctx);
-  const uint32_t nres = (uint32_t)tailw[8];
-  if (tailw[3] != 0) { prof_note(ctx, "group_radix.fell_back"); return false; }
-  if (mark) {
-    scan_prefix(q);
-    selection_changed(q);
-    ng = query_count(q, -1);
-    *ng_io = ng;
-  }
-  if ((int64_t)nres + (tailw[0] != ~0ull ? 1 : 0) + (tailw[1] != ~0ull ? 1 : 0) != ng) { prof_note(ctx, "group_radix.mismatch"); return false; }     // (cannot happen: the table pass saw every key unique saw)
-  q->gr_cnt.ensure((size_t)ng * 8 + 64); q->gr_val.ensure((size_t)ng * 8 + 64);
-  HIP_CHECK(hipMemsetAsync(q->gr_cnt.p, 0, (size_t)ng * 8 + 64, s));
-  HIP_CHECK(hipMemsetAsync(q->gr_val.p, op == DFDB_AGG_MIN ? 0xFF : 0, (size_t)ng * 8 + 64, s));
-  launch_radix_group_finish(s, g, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), aux, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>());
-  prof_note(ctx, "group_radix.taken");
-  return true;                                                           // (the temporaries' destructor drains the stream)
-}
-
-// groupreduce(view, (:key,); out = :val => Stat()) (src/tables/aggregate.jl:1-36; unfinished in the reference: it numbers the groups in order of
-// first appearance of the key and prints the map).  Completed to that intent: one group per distinct key (isequal), groups in order of first
-// appearance, count and one reduced value per group.  Device side: unique's table + k_group_ids + k_group_accumulate (k_unique.hip).
-void launch_group_ids(hipStream_t s, UniqueEntry* ent, uint64_t cap, uint64_t* special, const uint64_t* ubits, const uint64_t* uprefix);
-int launch_group_accumulate(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
-                            int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* special, uint64_t* cnt, uint64_t* val,
-                            int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag = nullptr, const void* gkeys = nullptr);
-void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const void* valcol, int valdt,
-                                 int op, int64_t nrows, const UniqueEntry* ent, const uint64_t* rep_off, const uint32_t* rep_len, uint64_t mask, uint64_t* special, uint64_t salt,
-                                 uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
-void launch_group_finish(hipStream_t s, uint64_t* val, int64_t ng, int kind, int op);
-
-void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes) {
-  ensure_executed_checked(q);
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  if (key_p < 0 || (size_t)key_p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", key_p);
-  const Node& ke = *q->proj[(size_t)key_p].expr;
-  if (ke.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
-  const Column* vc = nullptr;
-  if (op != DFDB_AGG_COUNT) {
-    if (val_p < 0 || (size_t)val_p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", val_p);
-    const Node& ve = *q->proj[(size_t)val_p].expr;
-    if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
-    vc = &need_resident(t, ve.col);
-  }
-  const Column& kc = need_resident(t, ke.col);
-  q->gr_n = 0; q->gr_key = key_p; q->gr_op = op; q->gr_kind = 0;
-  if (vc) { const int b = dt_base(vc->dtype); q->gr_kind = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1); }
-  if (ngroups) *ngroups = 0;
-  if (key_bytes) *key_bytes = 0;
-  const int64_t nsel = query_count(q, -1);
-  if (nsel == 0 || t->nrows == 0) { q->gr_state = 1; return; }
-  // the full selection is kept aside: unique narrows q's bitmap to the first occurrences (= the groups, in order)
-  const size_t nw = padded_words(t->nrows);
-  q->gr_sel.ensure(nw * 8);
-  HIP_CHECK(hipMemcpyAsync(q->gr_sel.p, q->bitmap.p, nw * 8, hipMemcpyDeviceToDevice, s));
-  if (kc.dict_n > 0) {                                       // K9: group by the dictionary codes
-    DevBuf& rank = q->du_rank;
-    int64_t ng = dict_unique(q, kc, &rank);
-    // more codes in use than LDS accumulators hold: the codes are the keys of the radix form (the first occurrences are in the bitmap already)
-    if (ng > kGroupsInLds && group_radix(q, kc.dict_codes.p, DFDB_U16, nullptr, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), false)) {
-      launch_group_finish(s, q->gr_val.as<uint64_t>(), ng, q->gr_kind, op);
-      stream_wait(ctx);
-      q->gr_n = ng; q->gr_state = 2;
-      if (ngroups) *ngroups = ng;
-      if (key_bytes) *key_bytes = query_string_bytes(q, key_p);
-      return;
-    }
-    q->gr_cnt.ensure((size_t)ng * 8 + 64); q->gr_val.ensure((size_t)ng * 8 + 64);
-    const uint64_t init = op == DFDB_AGG_MIN ? ~0ull : 0ull;
-    HIP_CHECK(hipMemsetAsync(q->gr_cnt.p, 0, (size_t)ng * 8 + 64, s));
-    HIP_CHECK(hipMemsetAsync(q->gr_val.p, op == DFDB_AGG_MIN ? 0xFF : 0, (size_t)ng * 8 + 64, s));
-    { LaunchTimer lt(ctx, "group_accumulate");
-      launch_group_accumulate_codes(s, q->gr_sel.as<uint64_t>(), kc.dict_codes.as<uint16_t>(), rank.as<uint32_t>(), vc ? vc->data.p : nullptr, vc ? dt_base(vc->dtype) : 0, op,
-                                    t->nrows, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init); }
-    launch_group_finish(s, q->gr_val.as<uint64_t>(), ng, q->gr_kind, op);
-    stream_wait(ctx);
-    q->gr_n = ng; q->gr_state = 2;
-    if (ngroups) *ngroups = ng;
-    if (key_bytes) *key_bytes = query_string_bytes(q, key_p);
-    return;
-  }
-  UniqueTables T;
-  int64_t ng = 0;
-  bool pessimistic = false, whole_dense = false, radix_failed = false;
-  // integer keys, dense form: the table of first rows / group numbers is made from the HEAD of the column (4 M rows) when the accumulate pass can be the one with
-  // the table in LDS — that pass meets every row anyway and raises a flag for a key that has no group, after which everything runs again over every row
-  // (the presence pass over the whole key column was 1.3 of the 5.0 ms of 1e9 rows by 5000 keys)
-  const bool head_ok = ctx_option(ctx, "groupreduce_optimistic", 1) != 0 && (dt_base(kc.dtype) == DFDB_I64 || dt_base(kc.dtype) == DFDB_U64) &&
-                       (!vc || dt_width(vc->dtype) == 8);
-  for (;;) {
-    // String keys: the pass that compares every row with its slot's representative (unique's verify pass) is folded into the accumulate pass below, which
-    // hashes every row and finds its slot anyway; should two different strings share a key the selection is put back and everything runs again under the next salt
-    T.defer_verify = true;
-    T.allow_optimistic = !pessimistic && ctx_option(ctx, "groupreduce_optimistic", 1) != 0;
-    T.allow_head = head_ok && !whole_dense;
-    T.group_probe = !radix_failed && ctx_option(ctx, "unique_radix", 1) != 0 && dt_base(kc.dtype) != DFDB_STRING;
-    T.group_estimate = 0;
-    unique_impl(q, key_p, &T);
-    if (T.group_estimate > 0) {                                  // the first chunk of rows promises more groups than any accumulate pass's LDS holds: by radix, first rows and all
-      ng = T.group_estimate;
-      if (group_radix(q, kc.data.p, dt_base(kc.dtype), dt_nullable(kc.dtype) ? kc.missing.as<uint64_t>() : nullptr, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), true)) break;
-      radix_failed = true;                                       // (skewed, too many groups, no room: the bitmap may have been cleared — everything again, the old way)
-      launch_missing_mask(s, q->gr_sel.as<uint64_t>(), false, false, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows);
-      scan_prefix(q);
-      selection_changed(q);
-      continue;
-    }
-    const bool head_table = T.dense && T.head_only;
-    if (head_table) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));        // (the word the accumulate pass raises: aux[3])
-    if (T.optimistic) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));      // the accumulate pass raises this word when it meets a string the table does not hold
-    ng = query_count(q, -1);
-    uint64_t* special = T.aux.as<uint64_t>();
-    if (T.dense) launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, special, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
-    else launch_group_ids(s, T.ent.as<UniqueEntry>(), T.cap, special, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
-    q->gr_cnt.ensure((size_t)ng * 8 + 64); q->gr_val.ensure((size_t)ng * 8 + 64);
-    const uint64_t init = op == DFDB_AGG_MIN ? ~0ull : 0ull;
-    HIP_CHECK(hipMemsetAsync(q->gr_cnt.p, 0, (size_t)ng * 8 + 64, s));
-    HIP_CHECK(hipMemsetAsync(q->gr_val.p, op == DFDB_AGG_MIN ? 0xFF : 0, (size_t)ng * 8 + 64, s));
-    // more groups than the LDS accumulators of any accumulate pass hold: by radix (group_radix) — which needs EVERY group's first row in the bitmap: a table made
-    // from the head of the column / a prefix of the rows is made again from all of them first
-    if (!radix_failed && !T.is_str && ng > kGroupsInLds && ctx_option(ctx, "unique_radix", 1) != 0 && ng <= 2400 * 1024) {
-      const bool partial = head_table || T.optimistic;          // unique looked at the head of the column / a prefix of the rows: not every group's first row is marked
-      if (group_radix(q, kc.data.p, dt_base(kc.dtype), dt_nullable(kc.dtype) ? kc.missing.as<uint64_t>() : nullptr, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), partial)) break;
-      radix_failed = true;
-      if (partial) {                                             // not taken, and the bitmap may have been cleared: everything again, every row looked at
-        whole_dense = true; pessimistic = true;
-        launch_missing_mask(s, q->gr_sel.as<uint64_t>(), false, false, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows);     // the full selection again
-        scan_prefix(q);
-        selection_changed(q);
-        continue;
-      }
-    }
-    int dense_lds = 0;
-    { LaunchTimer lt(ctx, "group_accumulate");
-      const uint64_t* kmiss = dt_nullable(kc.dtype) ? kc.missing.as<uint64_t>() : nullptr;
-      if (T.dense)
-        dense_lds = launch_group_accumulate_dense(s, q->gr_sel.as<uint64_t>(), kc.data.p, dt_base(kc.dtype), kmiss, vc ? vc->data.p : nullptr, vc ? dt_base(vc->dtype) : 0, op, t->nrows, T.lo,
-                                      T.range, T.span_lo, T.span_hi, T.first.as<uint64_t>(), special, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init,
-                                      head_table ? T.aux.as<uint64_t>() + 3 : nullptr);
-      else if (T.is_str)
-        launch_group_accumulate_str(s, q->gr_sel.as<uint64_t>(), kc.data.as<int32_t>(), (const int64_t*)kc.tile_off.p, kc.bytes.as<uint8_t>(), vc ? vc->data.p : nullptr,
-                                    vc ? dt_base(vc->dtype) : 0, op, t->nrows, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, special, T.salt,
-                                    q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init);
-      else {
-        // few groups of an 8-byte key: their keys (the key column at the first rows q's bitmap now holds, i.e. in group order) for the accumulate pass's LDS table
-        const void* gkeys = nullptr;
-        if (ng <= kGroupsInLds && dt_width(kc.dtype) == 8) {
-          q->gr_keys.ensure((size_t)ng * 8 + 64);
-          launch_gather(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), kc.data.p, q->gr_keys.p, 8, t->nrows, ng);
-          gkeys = q->gr_keys.p;
-        }
-        if (launch_group_accumulate(s, q->gr_sel.as<uint64_t>(), kc.data.p, dt_base(kc.dtype), kmiss, vc ? vc->data.p : nullptr,
-                                    vc ? dt_base(vc->dtype) : 0, op, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, special,
-                                    q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init, T.optimistic ? T.aux.as<uint64_t>() + 3 : nullptr, gkeys) > 0)
-          prof_note(ctx, "group_accumulate.hash_lds");
-      } }
-    if (dense_lds > 0) prof_note(ctx, "group_accumulate.dense_lds");
-    if (head_table) {
-      uint64_t unknown = dense_lds < 0 ? 1ull : 0ull;                  // (-1: the LDS form could not take the job and nothing ran)
-      if (!unknown) {
-        HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
-        stream_wait(ctx);
-      }
-      if (unknown || ctx_option(ctx, "groupreduce_optimistic", 1) == 2) {          // (2: the test knob — as if a key had been missing)
-        whole_dense = true;
-        prof_note(ctx, "group_accumulate.head_redo");
-        launch_missing_mask(s, q->gr_sel.as<uint64_t>(), false, false, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows);     // the full selection again
-        scan_prefix(q);
-        selection_changed(q);
-        continue;
-      }
-      prof_note(ctx, "group_accumulate.head_table");
-    }
-    if (!T.is_str && !T.optimistic) break;
-    int hit = 0; uint64_t unknown = 0;
-    HIP_CHECK(hipMemcpyAsync(&hit, (char*)T.aux.p + 32, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    const bool redo_all = T.optimistic && (unknown != 0 || ctx_option(ctx, "groupreduce_optimistic", 1) == 2);      // (2: a test knob — behave as if a string had been missing)
-    if (!T.is_str && !redo_all) break;                       // (numeric keys: nothing to collide)
-    if (!hit && !redo_all && ctx_option(ctx, "unique_test_collide", 0) <= T.salt_skip) break;
-    if (redo_all) pessimistic = true;                         // a string first met after the inserted prefix: everything again, every row inserted
-    else if (++T.salt_skip > 8) fail(DFDB_ERR_DEVICE, "unique: hash collisions under 8 different salts");
-    launch_missing_mask(s, q->gr_sel.as<uint64_t>(), false, false, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows);     // the full selection again
-    scan_prefix(q);
-    selection_changed(q);
-  }
-  launch_group_finish(s, q->gr_val.as<uint64_t>(), ng, q->gr_kind, op);
-  stream_wait(ctx);                                        // the tables die here
-  { RecycleScope rs; T = UniqueTables(); }
-  q->gr_n = ng; q->gr_state = 2;
-  if (ngroups) *ngroups = ng;
-  if (key_bytes && dt_base(kc.dtype) == DFDB_STRING) *key_bytes = query_string_bytes(q, key_p);
-}
-
-// the groups' keys (gathered over the first occurrences, i.e. in order of first appearance), counts and values -> caller buffers (host);
-// restores the query's full selection afterwards
-void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  if (q->gr_state == 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce has not been called (or the query was executed, reset or changed since)");
-  if (q->bitmap_rows != t->nrows) { q->gr_state = 0; fail(DFDB_ERR_ARGUMENT, "ArgumentError: the table changed between dfdb_query_groupreduce and its fetch"); }
-  const int64_t ng = q->gr_n;
-  if (ng > 0) {
-    if (keys) { keys->memkind = keys->memkind == DFDB_MEM_DEVICE ? DFDB_MEM_DEVICE : DFDB_MEM_HOST; materialize_col(q, q->gr_key, *keys, ng); }
-    std::vector<uint64_t> c((size_t)ng), v((size_t)ng);
-    HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    for (int64_t g = 0; g < ng; g++) {
-      if (counts) counts[g] = (int64_t)c[(size_t)g];
-      const uint64_t b = v[(size_t)g];
-      double d; memcpy(&d, &b, 8);
-      if (q->gr_kind == 2) { if (vals_f) vals_f[g] = d; if (vals_i) vals_i[g] = (int64_t)d; }
-      else { if (vals_i) vals_i[g] = (int64_t)b; if (vals_f) vals_f[g] = q->gr_kind == 1 ? (double)b : (double)(int64_t)b; }
-    }
-  } else if (keys) { keys->count = 0; keys->nbytes = 0; }
-  if (q->gr_state == 2) {                                  // back to the full selection: bitmap + tile counts + prefix
-    launch_missing_mask(s, q->gr_sel.as<uint64_t>(), false, false, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows);
-    scan_prefix(q);
-    selection_changed(q);
-  }
-  q->gr_state = 0;
-}
-
-
 
 // the device half of an aggregate: leaves {value, selected count} (16 bytes) of sum / min / max over projection column i in
 // q->red_result on the engine stream and returns the accumulator dtype (DFDB_I64 / DFDB_U64 / DFDB_F64).  No host wait: the group

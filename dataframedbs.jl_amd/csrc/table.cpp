@@ -119,9 +119,6 @@ static Column& new_column(dfdb_table* t, const char* name, int32_t dtype) {
   return t->cols.back();
 }
 
-// bitmap words for n rows, padded so that K2's 64-word (4096-row) reads stay in bounds
-static size_t padded_words(int64_t nrows) { return (size_t)(round_up(nrows > 0 ? nrows : 1, kCTileRows) / 64 + 64); }
-
 // K4: byte offset of every 1024-row string tile = exclusive scan of the per-tile sums of max(size,0)
 // (the parallel form of unsafe_remake_offsets!: FlatStringsVectors.jl:61-70)
 void set_string_tile_offsets(dfdb_ctx* ctx, Column& c) {

@@ -1,5 +1,5 @@
 """groupreduce over MORE groups than a workgroup's LDS accumulators hold (9216), by radix (csrc/k_radix.hip: 20-byte {key, row, value} records, a table with
-accumulators per partition in LDS, results placed by the rank of a group's first row; csrc/query.cpp group_radix).  The reference's groupreduce numbers the groups
+accumulators per partition in LDS, results placed by the rank of a group's first row; csrc/unique.cpp group_radix).  The reference's groupreduce numbers the groups
 in order of first appearance and stops (src/tables/aggregate.jl:1-36: it prints the map); counts and one statistic per group are this repository's completion.
 Checked against a numpy restatement: groups in order of first appearance, exact counts, integer sums / extrema exact, Float64 sums within n * eps * sum|x| (the
 order of the additions is not fixed), isequal keys (one NaN, -0.0 apart from 0.0), the key whose image cannot be stored (-1), a predicate, and the same answers

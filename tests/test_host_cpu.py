@@ -373,6 +373,22 @@ def test_every_context_option_the_engine_reads_is_documented_in_the_header():
     assert (public | knobs) - read == set(), sorted((public | knobs) - read)
 
 
+def test_every_environment_variable_the_engine_reads_is_in_the_knobs_table():
+    """every getenv("DFDB_...") in csrc/ is listed in csrc/KNOBS.md's table of environment variables, and nothing is listed there that the library no
+    longer reads."""
+    import glob
+    import re
+    files = glob.glob(os.path.join(ROOT, "dataframedbs.jl_amd", "csrc", "*.[ch]pp")) + glob.glob(os.path.join(ROOT, "dataframedbs.jl_amd", "csrc", "*.hip"))
+    src = "".join(open(f).read() for f in files)
+    read = set(re.findall(r'getenv\("(DFDB_[A-Z0-9_]+)"\)', src))
+    assert len(read) >= 5, read
+    knobs_md = open(os.path.join(ROOT, "dataframedbs.jl_amd", "csrc", "KNOBS.md")).read()
+    table = knobs_md[knobs_md.index("## Environment variables the library reads"):]
+    listed = set(re.findall(r'`(DFDB_[A-Z0-9_]+)', "\n".join(l.split(" | ")[0] for l in table.splitlines() if l.startswith("| `"))))
+    assert read - listed == set(), sorted(read - listed)
+    assert listed - read == set(), sorted(listed - read)
+
+
 # ------------------------------------------------------------------ round 5: host-side hardening that needs no GPU
 def test_a_failed_collective_always_closes_its_rccl_group_and_marks_the_communicator_dead():
     """csrc/group.cpp's ncclGroupStart / ncclGroupEnd bracket, driven by a stub collective table (dfdb_selftest "rccl_bracket"): whichever of
