@@ -1360,4 +1360,230 @@ int launch_group_accumulate_dense(hipStream_t s, const uint64_t* sel, const void
   return 0;
 }
 
+// ---------------------------------------------------------------- groupreduce by a tuple of keys with several reducers (dfdb_query_groupreduce_n, unique.cpp)
+// A row's group is numbered in two steps.  RANK: per key column i, the rank r_i of the row's key among that column's distinct values in order of first appearance —
+// the forms above made the table (dense, hash, dictionary codes, String hash) and turned its first rows into group numbers (k_group_ids / k_dense_group_ids), and the
+// kernels here only LOOK UP and STORE: G = r_1 for the first key, image = G * n_i + r_i (a u64: both factors are below 2^32) for every later one, which unique.cpp then
+// ranks again as a transient UInt64 column.  The existing accumulate kernels stay as they are (the lookups are the same, the stores are new).
+// Every stored rank is checked against the number of groups the host counted (`n`); a rank outside raises `flag` and the host refuses the result.
+__device__ __forceinline__ void rank_emit(const RankArgs& A, int64_t row, uint64_t r, uint32_t gp, bool& bad) {
+  if (r >= A.n) { bad = true; return; }
+  if (A.img_out) A.img_out[row] = (uint64_t)gp * A.n + r; else A.g_out[row] = (uint32_t)r;
+}
+// SRC 0: the hash table (special: unique's aux — [0] the group of the unstorable key, [1] of missing), 1: dictionary codes, 2: the dense form's table, 3: the same
+// table copied into LDS first (a range of at most kRankLdsRange values: the lookup is a ds_read, not a random 8-byte load per row — that load made the pass
+// 6.0 ms at 1e9 rows by 5000 keys)
+constexpr uint32_t kRankLdsRange = 16000;           // (+1 for missing: under 64 KB of static LDS)
+template <int SRC>
+__global__ __launch_bounds__(kBlock) void k_group_rank(const RankArgs A) {
+  __shared__ uint32_t ltab[SRC == 3 ? kRankLdsRange + 1 : 1];
+  if (SRC == 3) {
+    for (uint32_t i = threadIdx.x; i < A.range; i += kBlock) { const uint64_t v = A.gids[i]; ltab[i] = v < 0xFFFFFFFFull ? (uint32_t)v : 0xFFFFFFFFu; }
+    if (threadIdx.x == 0) { const uint64_t v = A.special[1]; ltab[A.range] = v < 0xFFFFFFFFull ? (uint32_t)v : 0xFFFFFFFFu; }
+    __syncthreads();
+  }
+  constexpr int U = 4;                                          // (every load of a trip before any is used, as in k_group_acc)
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  bool bad = false;
+  for (int64_t row0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; row0 < A.nrows; row0 += U * stride) {
+    uint64_t w[U], mw[U], key[U]; uint32_t gp[U];
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      const int64_t row = row0 + k * stride;
+      const bool inb = row < A.nrows;
+      w[k] = inb ? A.sel[row >> 6] : 0ull;
+      mw[k] = (SRC != 1 && inb && A.missing) ? A.missing[row >> 6] : 0ull;
+      if (SRC == 1) key[k] = inb ? (uint64_t)A.codes[row] : 0ull;
+      else key[k] = inb ? key_fixed(A.keycol, A.keydt, row) : 0ull;
+      gp[k] = (inb && A.gprev) ? A.gprev[row] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      const int64_t row = row0 + k * stride;
+      if (!((w[k] >> (row & 63)) & 1ull)) continue;
+      const bool miss = (mw[k] >> (row & 63)) & 1ull;
+      uint64_t r;
+      if (SRC == 1) r = A.rank_of_code[key[k]];
+      else if (SRC == 3) { const uint64_t i = key[k] - A.lo; r = miss ? (uint64_t)ltab[A.range] : (i < (uint64_t)A.range ? (uint64_t)ltab[i] : kEmpty); if (r == 0xFFFFFFFFull) r = kEmpty; }
+      else if (miss) r = A.special[1];
+      else if (SRC == 2) r = key[k] - A.lo < (uint64_t)A.range ? A.gids[key[k] - A.lo] : kEmpty;
+      else if (key[k] == kEmpty) r = A.special[0];
+      else r = table_row_maybe(A.ent, A.mask, key[k], slot_of(key[k], A.mask));
+      rank_emit(A, row, r, gp[k], bad);
+    }
+  }
+  if (bad) __atomic_store_n(A.flag, 1ull, __ATOMIC_RELAXED);
+}
+// flat String keys: a wave per 1024-row tile, the byte offsets by a wave prefix sum of the sizes (k_unique_str_mark's walk), the key hashed as the insert pass hashed it
+__global__ __launch_bounds__(kBlock) void k_group_rank_str(const RankArgs A, const int32_t* __restrict__ sizes, const int64_t* __restrict__ tile_off,
+                                                           const uint8_t* __restrict__ bytes, uint64_t salt, int64_t ntiles) {
+  const int lane = lane_id();
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  bool bad = false;
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    const uint64_t mine = lane < 16 ? A.sel[tile * 16 + lane] : 0ull;
+    if (__ballot(mine != 0) == 0) continue;
+    int64_t run = tile_off[tile];
+    for (int j = 0; j < 16; j++) {
+      const int64_t row = tile * kTile + j * 64 + lane;
+      const int32_t sz = row < A.nrows ? sizes[row] : 0;
+      const uint32_t c = sz > 0 ? (uint32_t)sz : 0u;
+      const uint32_t incl = wave_incl_scan(c);
+      const int64_t off = run + (int64_t)(incl - c);
+      run += (int64_t)__shfl(incl, 63, 64);
+      const uint64_t w = __shfl(mine, j, 64);
+      if (row < A.nrows && ((w >> lane) & 1ull)) {
+        uint64_t r;
+        if (sz < 0) r = A.special[1];
+        else {
+          const uint8_t* p = bytes + off;
+          uint64_t key = hash_bytes(p, sz, salt, sz > 0 ? load8(p) : 0ull, sz > 8 ? load8(p + 8) : 0ull);
+          if (key == kEmpty) key = 0x1234567ull;
+          r = table_row_maybe(A.ent, A.mask, key, key & A.mask);
+        }
+        const uint32_t gp = A.gprev ? A.gprev[row] : 0u;
+        rank_emit(A, row, r, gp, bad);
+      }
+    }
+  }
+  if (bad) __atomic_store_n(A.flag, 1ull, __ATOMIC_RELAXED);
+}
+bool launch_group_rank(hipStream_t s, int src, const RankArgs& A) {
+  if (A.nrows <= 0) return true;
+  (void)hipGetLastError();
+  const dim3 g((unsigned)std::min<int64_t>(8192, std::max<int64_t>(1, (A.nrows + kBlock - 1) / kBlock))), b(kBlock);
+  if (src == 1) hipLaunchKernelGGL(k_group_rank<1>, g, b, 0, s, A);
+  else if (src == 2 && A.range <= kRankLdsRange) hipLaunchKernelGGL(k_group_rank<3>, dim3(std::min(g.x, 2048u)), b, 0, s, A);
+  else if (src == 2) hipLaunchKernelGGL(k_group_rank<2>, g, b, 0, s, A);
+  else hipLaunchKernelGGL(k_group_rank<0>, g, b, 0, s, A);
+  return hipGetLastError() == hipSuccess;
+}
+bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, uint64_t salt) {
+  if (A.nrows <= 0) return true;
+  (void)hipGetLastError();
+  const int64_t nt = (A.nrows + kTile - 1) / kTile;
+  hipLaunchKernelGGL(k_group_rank_str, dim3(grid_tiles(nt)), dim3(kBlock), 0, s, A, sizes, tile_off, bytes, salt, nt);
+  return hipGetLastError() == hipSuccess;
+}
+
+// ONE accumulate pass for every reducer: the row's group G (k_group_rank), its selection bit and the M value columns; the count and M accumulators per group.
+// LDS: the workgroup's own accumulators while ngroups x (M + 1) fit (counts 4 bytes: a workgroup meets fewer than 2^32 rows), flushed with one global atomic each.
+// Otherwise global atomics, with kHotGroups LDS slots for HOT groups exactly as k_group_acc<0> keeps them (a group that 30 % of the rows hold was 3.6 s per 1e9 rows
+// through plain atomics): a group that three of the 64 rows a wave looks at belong to is given a free slot, and its later rows are added there.
+// The reducers are a loop at run time (their columns, dtypes and operators are wave-uniform); the next reducer's values are loaded before the current one's are added.
+__device__ __forceinline__ void multi_add(uint64_t* v, uint64_t bits, int kind, int op) {      // one row's value into an accumulator (LDS or global)
+  if (op == DFDB_AGG_SUM) { if (kind == 2) atomicAdd((double*)v, __longlong_as_double((long long)bits)); else atomicAdd((unsigned long long*)v, (unsigned long long)bits); }
+  else if (op == DFDB_AGG_MIN) atomicMin((unsigned long long*)v, (unsigned long long)order_image(bits, kind, op));
+  else if (op == DFDB_AGG_MAX) atomicMax((unsigned long long*)v, (unsigned long long)order_image(bits, kind, op));
+}
+__device__ __forceinline__ void multi_merge(uint64_t* v, uint64_t acc, int kind, int op) {      // an accumulator (an order image for min / max) into the global one
+  if (op == DFDB_AGG_SUM) { if (kind == 2) atomicAdd((double*)v, __longlong_as_double((long long)acc)); else atomicAdd((unsigned long long*)v, (unsigned long long)acc); }
+  else if (op == DFDB_AGG_MIN) atomicMin((unsigned long long*)v, (unsigned long long)acc);
+  else if (op == DFDB_AGG_MAX) atomicMax((unsigned long long*)v, (unsigned long long)acc);
+}
+template <bool LDS>
+__global__ __launch_bounds__(1024) void k_group_acc_multi(const MultiAccArgs A, int slots) {
+  // dynamic LDS: [M][slots] 8-byte accumulators, then [slots] 4-byte counts; slots = the groups (LDS) or kHotGroups
+  extern __shared__ uint64_t dyn_sh[];
+  __shared__ uint64_t hg_gid[LDS ? 1 : (int)kHotGroups];
+  __shared__ uint32_t hg_any;
+  uint64_t* lval = dyn_sh; uint32_t* lcnt = (uint32_t*)(dyn_sh + (size_t)A.nvals * slots);
+  const int M = A.nvals;
+  for (int i = threadIdx.x; i < M * slots; i += 1024) lval[i] = A.op[i / slots] == DFDB_AGG_MIN ? ~0ull : 0ull;
+  for (int i = threadIdx.x; i < slots; i += 1024) lcnt[i] = 0;
+  if (!LDS) { for (int i = threadIdx.x; i < kHotGroups; i += 1024) hg_gid[i] = kEmpty; if (threadIdx.x == 0) hg_any = 0; }
+  __syncthreads();
+  constexpr int U = 4;
+  const int64_t stride = (int64_t)gridDim.x * 1024;
+  const uint64_t ng = (uint64_t)A.ngroups;
+  bool bad = false, hot_on = false;
+  for (int64_t row0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; row0 < A.nrows; row0 += U * stride) {
+    uint64_t w[U], bits[U]; uint32_t g[U]; bool on[U]; int sl[U];
+#pragma unroll
+    for (int k = 0; k < U; k++) {                              // the selection words, the group numbers and the first reducer's values: all in flight together
+      const int64_t row = row0 + k * stride;
+      const bool inb = row < A.nrows;
+      w[k] = inb ? A.sel[row >> 6] : 0ull;
+      g[k] = inb ? A.gid[row] : 0u;
+      int kd = 0; bits[k] = (inb && M > 0 && A.op[0] != DFDB_AGG_COUNT) ? value_bits(A.valcol[0], A.valdt[0], row, kd) : 0ull;      // (a count has no column)
+    }
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      const int64_t row = row0 + k * stride;
+      on[k] = (w[k] >> (row & 63)) & 1ull;
+      if (on[k] && (uint64_t)g[k] >= ng) { bad = true; on[k] = false; }
+      sl[k] = LDS ? (int)g[k] : -1;
+    }
+    if (!LDS) {                                                // hot groups (k_group_acc<0>'s rules): rows of a group that has a slot are added in LDS
+      if (!hot_on) hot_on = __builtin_amdgcn_readfirstlane((int)*(volatile uint32_t*)&hg_any) != 0;
+#pragma unroll
+      for (int k = 0; k < U; k++) {
+        if (hot_on && on[k] && ((volatile uint64_t*)hg_gid)[g[k] & (kHotGroups - 1)] == (uint64_t)g[k]) sl[k] = (int)(g[k] & (kHotGroups - 1));
+        const uint64_t m = __ballot(on[k] && sl[k] < 0);
+        if (k == 0 && m) {
+          const int fl = __builtin_ctzll(m);
+          const uint32_t fg = (uint32_t)__builtin_amdgcn_readlane((int)g[k], fl);
+          if (__builtin_popcountll(m & __ballot(on[k] && sl[k] < 0 && g[k] == fg)) >= 3 && (threadIdx.x & 63) == 0) {
+            const uint32_t s2 = fg & (kHotGroups - 1);
+            if (((volatile uint64_t*)hg_gid)[s2] == kEmpty) { atomicCAS((unsigned long long*)&hg_gid[s2], (unsigned long long)kEmpty, (unsigned long long)fg); *(volatile uint32_t*)&hg_any = 1; }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+      if (!on[k]) continue;
+      if (sl[k] >= 0) atomicAdd(&lcnt[sl[k]], 1u); else atomicAdd((unsigned long long*)&A.cnt[g[k]], 1ull);
+    }
+    for (int r = 0; r < M; r++) {
+      uint64_t nxt[U];
+      const bool more = r + 1 < M && A.op[r + 1] != DFDB_AGG_COUNT;
+#pragma unroll
+      for (int k = 0; k < U; k++) {                            // the next reducer's values, before this one's are added
+        const int64_t row = row0 + k * stride;
+        int kd = 0; nxt[k] = (more && row < A.nrows) ? value_bits(A.valcol[r + 1], A.valdt[r + 1], row, kd) : 0ull;
+      }
+      const int op = A.op[r], kind = A.kind[r];
+      if (op != DFDB_AGG_COUNT) {
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+          if (!on[k]) continue;
+          multi_add(sl[k] >= 0 ? &lval[(size_t)r * slots + sl[k]] : &A.val[(size_t)r * ng + g[k]], bits[k], kind, op);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < U; k++) bits[k] = nxt[k];
+    }
+  }
+  if (bad) __atomic_store_n(A.flag, 1ull, __ATOMIC_RELAXED);
+  __syncthreads();
+  for (int i = threadIdx.x; i < slots; i += 1024) {            // the workgroup's accumulators -> the global ones
+    const uint32_t c = lcnt[i];
+    if (!c) continue;
+    const uint64_t gg = LDS ? (uint64_t)i : hg_gid[i];
+    if (gg == kEmpty) continue;
+    atomicAdd((unsigned long long*)&A.cnt[gg], (unsigned long long)c);
+    for (int r = 0; r < M; r++) if (A.op[r] != DFDB_AGG_COUNT) multi_merge(&A.val[(size_t)r * ng + gg], lval[(size_t)r * slots + i], A.kind[r], A.op[r]);
+  }
+}
+constexpr size_t kMultiLdsBytes = 156 * 1024;
+int64_t group_multi_lds_groups(int nvals) { return (int64_t)(kMultiLdsBytes / (4 + 8 * (size_t)nvals)) & ~1ll; }
+// 1: the LDS form ran, 0: the global form, -1: the launch was refused (nothing ran)
+int launch_group_accumulate_multi(hipStream_t s, const MultiAccArgs& A) {
+  if (A.nrows <= 0) return 1;
+  const bool lds = A.ngroups <= group_multi_lds_groups(A.nvals);
+  const int slots = lds ? (int)((A.ngroups + 1) & ~1ll) : kHotGroups;
+  const size_t bytes = (size_t)slots * (4 + 8 * (size_t)A.nvals);
+  const void* kern = lds ? (const void*)k_group_acc_multi<true> : (const void*)k_group_acc_multi<false>;
+  if (!allow_dynamic_lds(kern, kMultiLdsBytes)) return -1;
+  // (one 1024-thread workgroup per CU when the accumulators take most of its LDS, two when they leave room: few groups, many rows per workgroup either way)
+  const int64_t cap = lds ? (bytes <= kMultiLdsBytes / 2 ? 512 : 256) : 2048;
+  const unsigned g = (unsigned)std::min<int64_t>(cap, std::max<int64_t>(1, (A.nrows + 1023) / 1024));
+  if (lds) hipLaunchKernelGGL(k_group_acc_multi<true>, dim3(g), dim3(1024), bytes, s, A, slots);
+  else hipLaunchKernelGGL(k_group_acc_multi<false>, dim3(g), dim3(1024), bytes, s, A, slots);
+  if (hipGetLastError() != hipSuccess) return -1;
+  return lds ? 1 : 0;
+}
+
 }  // namespace dfdb

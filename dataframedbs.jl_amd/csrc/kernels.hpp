@@ -218,6 +218,27 @@ void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32
                                  int op, int64_t nrows, const UniqueEntry* ent, const uint64_t* rep_off, const uint32_t* rep_len, uint64_t mask, uint64_t* special, uint64_t salt,
                                  uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
 void launch_group_finish(hipStream_t s, uint64_t* val, int64_t ng, int kind, int op);
+// groupreduce by a tuple of keys (dfdb_query_groupreduce_n): per selected row of `sel`, the rank of its key out of one of the tables above -> g_out (gprev null)
+// or image = gprev[row] * n + rank -> img_out; a rank >= n raises *flag.  src 0: hash table (special = unique's aux), 1: dictionary codes, 2: the dense form (its table in LDS when the range is small)
+struct RankArgs {
+  const uint64_t* sel; const void* keycol; int keydt; const uint64_t* missing; int64_t nrows;
+  const UniqueEntry* ent; uint64_t mask; const uint64_t* special;
+  const uint16_t* codes; const uint32_t* rank_of_code;
+  uint64_t lo; uint32_t range; const uint64_t* gids;
+  const uint32_t* gprev; uint64_t n; uint32_t* g_out; uint64_t* img_out; uint64_t* flag;
+};
+bool launch_group_rank(hipStream_t s, int src, const RankArgs& A);
+bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, uint64_t salt);
+// one accumulate pass for up to kMaxReducers reducers over the rows' group numbers: cnt [ngroups], val [nvals][ngroups] (min / max as order images until
+// launch_group_finish); kind: value_bits' kind of each value column; a group number >= ngroups raises *flag.  1: LDS form, 0: global form, -1: not launched
+constexpr int kMaxReducers = 16;
+struct MultiAccArgs {
+  const uint64_t* sel; const uint32_t* gid; int64_t nrows; int nvals;
+  const void* valcol[kMaxReducers]; int valdt[kMaxReducers], op[kMaxReducers], kind[kMaxReducers];
+  uint64_t* cnt; uint64_t* val; int64_t ngroups; uint64_t* flag;
+};
+int launch_group_accumulate_multi(hipStream_t s, const MultiAccArgs& A);
+int64_t group_multi_lds_groups(int nvals);      // the most groups the LDS form holds with nvals reducers
 
 // ---- K7: LZ4 block decode, K8: missing bitmaps, block bodies ---------------------------------------
 // (dst: the decoders may READ up to 32 bytes past the end of the last block's output — far-match sources are fetched 24 bytes at a time — so the

@@ -77,6 +77,44 @@ void GroupMerger::add(GroupMerged& m, const GroupPart& p) {
   }
 }
 
+void GroupMergerN::add(GroupMergedN& m, const GroupPartN& p) {
+  const size_t nk = m.keys.size(), nv = m.ops.size();
+  std::vector<int64_t> boff(nk, 0), b0(nk);
+  std::vector<std::string> ki(nk);
+  for (int64_t j = 0; j < p.ng; j++) {                     // part order = table order: a tuple keeps the place of its first appearance
+    std::string k;
+    for (size_t i = 0; i < nk; i++) {
+      b0[i] = boff[i];
+      ki[i] = merge_key(m.keys[i].key_dtype, p.keys[i], j, boff[i]);
+      const uint32_t len = (uint32_t)ki[i].size();
+      k.append((const char*)&len, 4); k.append(ki[i]);
+    }
+    auto it = slot.find(k);
+    if (it == slot.end()) {
+      slot.emplace(std::move(k), m.ng++);
+      for (size_t i = 0; i < nk; i++) {
+        GroupMerged& km = m.keys[i]; const GroupPart& kp = p.keys[i];
+        const bool is_str = dt_base(km.key_dtype) == DFDB_STRING;
+        const int w = is_str ? 4 : dt_width(km.key_dtype);
+        km.key_data.insert(km.key_data.end(), kp.key_data.begin() + j * w, kp.key_data.begin() + (j + 1) * w);
+        km.key_missing.push_back(ki[i][0] == '\1' ? 1 : 0);
+        if (is_str) km.key_bytes.insert(km.key_bytes.end(), kp.key_bytes.begin() + b0[i], kp.key_bytes.begin() + boff[i]);
+        km.ng++;
+      }
+      m.counts.push_back(p.counts[(size_t)j]);
+      for (size_t r = 0; r < nv; r++) m.vals[r].push_back(p.vals[r][(size_t)j]);
+      continue;
+    }
+    const size_t s = (size_t)it->second;
+    m.counts[s] += p.counts[(size_t)j];
+    for (size_t r = 0; r < nv; r++) {
+      const uint64_t a = m.vals[r][s], b = p.vals[r][(size_t)j];
+      if (m.ops[r] == DFDB_AGG_COUNT) m.vals[r][s] = a + b;
+      else m.vals[r][s] = fold_bits(a, b, m.kinds[r] == 2 ? DFDB_F64 : (m.kinds[r] == 1 ? DFDB_U64 : DFDB_I64), m.ops[r]);
+    }
+  }
+}
+
 void fetch_group_part(dfdb_query* q, int32_t key_p, int64_t ng, int64_t kb, bool with_rows, GroupPart& part) {
   const int32_t kdt = q->proj[(size_t)key_p].expr->dtype;
   const bool is_str = dt_base(kdt) == DFDB_STRING;
@@ -117,6 +155,20 @@ void merged_fetch(const GroupMerged& m, dfdb_outcol* keys, int64_t* counts, int6
     double d; memcpy(&d, &b, 8);
     if (m.kind == 2) { if (vals_f) vals_f[j] = d; if (vals_i) vals_i[j] = (int64_t)d; }
     else { if (vals_i) vals_i[j] = (int64_t)b; if (vals_f) vals_f[j] = m.kind == 1 ? (double)b : (double)(int64_t)b; }
+  }
+}
+
+// one key column of a merged result -> a caller buffer (HOST)
+static void merged_keys_fetch(const GroupMerged& km, int64_t ng, dfdb_outcol* o) {
+  if (o->memkind != DFDB_MEM_HOST) fail(DFDB_ERR_ARGUMENT, "merged keys are written to host buffers");
+  o->dtype = km.key_dtype; o->count = ng; o->nbytes = (int64_t)km.key_bytes.size();
+  if (ng == 0) return;
+  if (!o->data) fail(DFDB_ERR_ARGUMENT, "the key column has no data buffer");
+  memcpy(o->data, km.key_data.data(), km.key_data.size());
+  if (o->missing) memcpy(o->missing, km.key_missing.data(), (size_t)ng);
+  if (dt_base(km.key_dtype) == DFDB_STRING && !km.key_bytes.empty()) {
+    if ((int64_t)km.key_bytes.size() > o->bytes_cap || !o->bytes) fail(DFDB_ERR_ARGUMENT, "the key column needs %zu string bytes, capacity is %lld", km.key_bytes.size(), (long long)o->bytes_cap);
+    memcpy(o->bytes, km.key_bytes.data(), km.key_bytes.size());
   }
 }
 
@@ -463,6 +515,105 @@ void ooc_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, in
   if (!o.gr_pending || !o.merged.valid) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce has not been called (or the query was executed, reset or changed since)");
   merged_fetch(o.merged, keys, counts, vals_i, vals_f);
   o.merged = GroupMerged{}; o.gr_pending = false; o.merged_col = -1;
+}
+
+// groupreduce by a tuple of keys: the resident dfdb_query_groupreduce_n per chunk, the chunks merged by tuple in chunk order (= first appearance)
+void ooc_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, int64_t* ngroups,
+                       int64_t* key_bytes) {
+  if (nkeys < 1 || nkeys > 8 || !key_cols) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 1 to 8 key columns, not %d", nkeys);
+  if (nvals < 0 || nvals > kMaxReducers || (nvals > 0 && (!val_cols || !stats))) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 0 to %d reducers, not %d", kMaxReducers, nvals);
+  GroupMergedN m;
+  for (int k = 0; k < nkeys; k++) {
+    const int32_t p = key_cols[k];
+    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+    const Node& ke = *q->proj[(size_t)p].expr;
+    if (ke.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
+    m.keys.emplace_back(); m.keys.back().key_dtype = ke.dtype;
+  }
+  for (int r = 0; r < nvals; r++) {
+    const int32_t op = stats[r];
+    if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
+    int kind = 0;
+    if (op != DFDB_AGG_COUNT) {
+      const int32_t p = val_cols[r];
+      if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+      const Node& ve = *q->proj[(size_t)p].expr;
+      if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
+      const int b = dt_base(ve.dtype); kind = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
+    }
+    m.kinds.push_back(kind); m.ops.push_back(op);
+  }
+  m.vals.resize((size_t)nvals);
+  OocState& o = state(q);
+  if (o.narrowed) fail(DFDB_ERR_ARGUMENT, "ArgumentError: the query's selection is narrowed by dfdb_query_unique: dfdb_query_reset it first");
+  // the chunk query projects the keys, then the reducers' columns (a count reads none)
+  TempQuery tq(q, true);
+  std::vector<int32_t> kidx((size_t)nkeys), vidx((size_t)nvals, -1);
+  for (int k = 0; k < nkeys; k++) { kidx[(size_t)k] = (int32_t)tq.q.proj.size(); tq.project(q->proj[(size_t)key_cols[k]]); }
+  for (int r = 0; r < nvals; r++) if (stats[r] != DFDB_AGG_COUNT) { vidx[(size_t)r] = (int32_t)tq.q.proj.size(); tq.project(q->proj[(size_t)val_cols[r]]); }
+  GroupMergerN mg;
+  int64_t rows = 0;
+  {
+    StreamPass pass(q, &tq.q);
+    while (dfdb_query* c = pass.next()) {
+      const int64_t n = query_count(c, -1);
+      if (n == 0) continue;
+      rows += n;
+      int64_t ng = 0;
+      std::vector<int64_t> kb((size_t)nkeys, 0);
+      query_groupreduce_n(c, kidx.data(), nkeys, vidx.data(), stats, nvals, &ng, kb.data());
+      GroupPartN part;
+      part.ng = ng; part.keys.resize((size_t)nkeys);
+      std::vector<dfdb_outcol> outs((size_t)nkeys);
+      for (int k = 0; k < nkeys; k++) {
+        const int32_t kdt = m.keys[(size_t)k].key_dtype;
+        const bool is_str = dt_base(kdt) == DFDB_STRING;
+        GroupPart& kp = part.keys[(size_t)k];
+        kp.ng = ng;
+        kp.key_data.resize((size_t)ng * (size_t)(is_str ? 4 : dt_width(kdt)));
+        if (dt_nullable(kdt) && !is_str) kp.key_missing.assign((size_t)ng, 0);
+        kp.key_bytes.resize((size_t)kb[(size_t)k]);
+        dfdb_outcol& oc = outs[(size_t)k];
+        oc = dfdb_outcol{}; oc.memkind = DFDB_MEM_HOST; oc.data = kp.key_data.data(); oc.bytes = kp.key_bytes.data(); oc.bytes_cap = kb[(size_t)k];
+        oc.missing = kp.key_missing.empty() ? nullptr : kp.key_missing.data();
+      }
+      part.counts.assign((size_t)ng, 0);
+      std::vector<int64_t> vi((size_t)ng * (size_t)nvals); std::vector<double> vf((size_t)ng * (size_t)nvals);
+      query_groupreduce_n_fetch(c, outs.data(), part.counts.data(), vi.data(), vf.data());   // (puts the chunk's full selection back)
+      part.vals.assign((size_t)nvals, std::vector<uint64_t>((size_t)ng));
+      for (int r = 0; r < nvals; r++)
+        for (int64_t j = 0; j < ng; j++) {
+          const size_t i = (size_t)r * (size_t)ng + (size_t)j;
+          if (stats[r] != DFDB_AGG_COUNT && m.kinds[(size_t)r] == 2) memcpy(&part.vals[(size_t)r][(size_t)j], &vf[i], 8); else part.vals[(size_t)r][(size_t)j] = (uint64_t)vi[i];
+        }
+      mg.add(m, part);
+    }
+  }
+  m.valid = true;
+  o.count = rows;
+  o.merged_n = std::move(m);
+  o.grn_pending = true;
+  if (ngroups) *ngroups = o.merged_n.ng;
+  if (key_bytes) for (int k = 0; k < nkeys; k++) key_bytes[k] = (int64_t)o.merged_n.keys[(size_t)k].key_bytes.size();
+}
+
+void ooc_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
+  OocState& o = state(q);
+  if (!o.grn_pending || !o.merged_n.valid) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce_n has not been called (or the query was executed, reset or changed since)");
+  const GroupMergedN& m = o.merged_n;
+  const int64_t ng = m.ng;
+  if (keys) for (size_t k = 0; k < m.keys.size(); k++) merged_keys_fetch(m.keys[k], ng, &keys[k]);
+  for (int64_t j = 0; j < ng; j++) if (counts) counts[j] = m.counts[(size_t)j];
+  for (size_t r = 0; r < m.ops.size(); r++)
+    for (int64_t j = 0; j < ng; j++) {
+      const size_t i = r * (size_t)ng + (size_t)j;
+      const uint64_t b = m.vals[r][(size_t)j];
+      const int kind = m.ops[r] == DFDB_AGG_COUNT ? 0 : m.kinds[r];
+      double d; memcpy(&d, &b, 8);
+      if (kind == 2) { if (vals_f) vals_f[i] = d; if (vals_i) vals_i[i] = (int64_t)d; }
+      else { if (vals_i) vals_i[i] = (int64_t)b; if (vals_f) vals_f[i] = kind == 1 ? (double)b : (double)(int64_t)b; }
+    }
+  o.merged_n = GroupMergedN{}; o.grn_pending = false;
 }
 
 // ------------------------------------------------------------------ what a multi-GPU group asks of a shard that is not resident (group.cpp)

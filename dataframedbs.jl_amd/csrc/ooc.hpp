@@ -39,6 +39,21 @@ struct GroupMerger {
   // minimum / maximum fold with Julia's NaN and signed-zero rules
   void add(GroupMerged& m, const GroupPart& part);
 };
+// the same by a TUPLE of key columns with several reducers (dfdb_query_groupreduce_n): one GroupPart / GroupMerged per key column carries that column's keys
+// (its counts and vals stay empty); the counts and the value arrays (one per reducer) belong to the tuple.  The merge key is the concatenation of every key's
+// isequal image (merge_key), each prefixed with its length; counts add, sums add, minimum / maximum fold with fold_bits — the single-key merge's rules
+struct GroupPartN { int64_t ng = 0; std::vector<GroupPart> keys; std::vector<int64_t> counts; std::vector<std::vector<uint64_t>> vals; };
+struct GroupMergedN {
+  bool valid = false;
+  std::vector<GroupMerged> keys;                     // per key column: key_dtype and the key arrays
+  std::vector<int> kinds, ops;                       // per reducer: the value column's kind (GroupMerged::kind) and the statistic
+  int64_t ng = 0;
+  std::vector<int64_t> counts; std::vector<std::vector<uint64_t>> vals;
+};
+struct GroupMergerN {
+  std::unordered_map<std::string, int64_t> slot;
+  void add(GroupMergedN& m, const GroupPartN& part);
+};
 // one part out of a query on which query_groupreduce(q, key_p, val_p, op) has just returned ng groups and kb key string bytes: the fetch (which puts the
 // query's full selection back) into host vectors; with_rows also records the first occurrences' table rows (taken before the fetch, while q is narrowed)
 void fetch_group_part(dfdb_query* q, int32_t key_p, int64_t ng, int64_t kb, bool with_rows, GroupPart& part);
@@ -54,6 +69,8 @@ struct OocState {
   int merged_col = -1;
   GroupMerged merged;                                // unique: keys + rows; groupreduce: the groups until their fetch
   bool gr_pending = false;
+  GroupMergedN merged_n;                             // groupreduce_n: the groups until their fetch
+  bool grn_pending = false;
   dfdb_sizestats read{0, 0, 0};                      // what the streams this query ran have read (dfdb_query_read_stats)
 };
 
@@ -66,6 +83,9 @@ void ooc_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double*
 void ooc_unique(dfdb_query* q, int32_t p);
 void ooc_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes);
 void ooc_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f);
+void ooc_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, int64_t* ngroups,
+                       int64_t* key_bytes);
+void ooc_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f);
 void ooc_reset(dfdb_query* q);
 // projection column p alone into ONE caller buffer (dfdb_table_add_from_query over a view whose columns are not resident)
 void ooc_materialize_column(dfdb_query* q, int32_t p, dfdb_outcol* o);

@@ -30,6 +30,7 @@ struct UniqueTables {
   // in: the caller can reduce by radix (group_radix: more groups than LDS accumulators hold) and wants to know EARLY whether that is the case; out: the number of
   // distinct keys the first chunk's rows promise when it is more than 9216 — and then nothing else was done: the selection is as it was, no table was finished
   bool group_probe = false; int64_t group_estimate = 0;
+  bool allow_radix = true;       // in: the radix form of unique may take the job (it leaves no table to look keys up in: groupreduce_n's rank pass says no)
 };
 // K9: unique over a String column that has a dictionary — the first selected row of every code, no hash table.  Leaves what unique_impl leaves (the
 // bitmap holds exactly the first occurrences, prefix scanned); rank_of_code (optional) maps a code to its group number in order of first appearance.
@@ -395,7 +396,7 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
           const double D = estimate_distinct(st[0], r, cnt);
           if (D > (double)kGroupsInLds) { T.group_estimate = (int64_t)D; return; }
         }
-        if (!T.defer_verify && unique_radix(q, col, cnt, T, st[0], r)) return;      // the radix-partitioned form took it: q's bitmap holds the first occurrences
+        if (!T.defer_verify && T.allow_radix && unique_radix(q, col, cnt, T, st[0], r)) return;      // the radix-partitioned form took it: q's bitmap holds the first occurrences
       }
       if (c == 0 && bounds[1] <= bounds[0]) claims_c0 = ~0ull;
       const uint64_t want = unique_capacity_wanted(st[0], r, (uint64_t)cnt - std::min<uint64_t>(r, (uint64_t)cnt), T.cap, capmax);
@@ -429,13 +430,9 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
   }
 }
 
-static void unique_impl(dfdb_query* q, int32_t p, UniqueTables* keep) {
-  ensure_executed_checked(q);
+// (col: a column of the table, or a transient one that belongs to no table's column list — groupreduce_n's images)
+static void unique_impl_col(dfdb_query* q, const Column& col, UniqueTables* keep) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
-  if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
-  const Node& e = *q->proj[(size_t)p].expr;
-  if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "unique of a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  const Column& col = need_resident(t, e.col);
   const int64_t cnt = query_count(q, -1);
   if (cnt == 0 || t->nrows == 0) return;
   if (!keep && col.dict_n > 0) { dict_unique(q, col, nullptr); return; }
@@ -452,6 +449,13 @@ static void unique_impl(dfdb_query* q, int32_t p, UniqueTables* keep) {
   selection_changed(q); q->cap_col = -1; q->cap_col2 = -1; q->cap_str_col = -1; q->agg_col = -1;
   stream_wait(ctx);                                        // the tables die here (or stay with the caller: groupreduce looks rows up in them)
   if (!keep) { RecycleScope rs; local = UniqueTables(); }
+}
+static void unique_impl(dfdb_query* q, int32_t p, UniqueTables* keep) {
+  ensure_executed_checked(q);
+  if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+  const Node& e = *q->proj[(size_t)p].expr;
+  if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "unique of a computed column: materialise it as a column first (dfdb_table_add_from_query)");
+  unique_impl_col(q, need_resident(q->t, e.col), keep);
 }
 void query_unique(dfdb_query* q, int32_t p) { unique_impl(q, p, nullptr); }
 
@@ -650,7 +654,7 @@ void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, 
     vc = &need_resident(t, ve.col);
   }
   const Column& kc = need_resident(t, ke.col);
-  q->gr_n = 0; q->gr_key = key_p; q->gr_op = op; q->gr_kind = 0;
+  q->gr_n = 0; q->gr_key = key_p; q->gr_op = op; q->gr_kind = 0; q->gr_multi = 0;
   if (vc) { const int b = dt_base(vc->dtype); q->gr_kind = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1); }
   if (ngroups) *ngroups = 0;
   if (key_bytes) *key_bytes = 0;
@@ -686,7 +690,7 @@ void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, 
 // restores the query's full selection afterwards
 void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  if (q->gr_state == 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce has not been called (or the query was executed, reset or changed since)");
+  if (q->gr_state == 0 || q->gr_multi == 2) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce has not been called (or the query was executed, reset or changed since)");
   if (q->bitmap_rows != t->nrows) { q->gr_state = 0; fail(DFDB_ERR_ARGUMENT, "ArgumentError: the table changed between dfdb_query_groupreduce and its fetch"); }
   const int64_t ng = q->gr_n;
   if (ng > 0) {
@@ -705,6 +709,190 @@ void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, 
   } else if (keys) { keys->count = 0; keys->nbytes = 0; }
   if (q->gr_state == 2) restore_group_selection(q);      // back to the full selection: bitmap + tile counts + prefix
   q->gr_state = 0;
+}
+
+// ---- groupreduce by a tuple of key columns with several reducers (dfdb_query_groupreduce_n; aggregate.jl:1-14 takes `by::Tuple{Vararg{Symbol}}` and any number of
+// `name = col => Stat()`).  One group per distinct tuple (isequal, element by element), groups in order of the first selected row that holds the tuple.
+// Device side, per call: G (4 bytes per row) and image (8 bytes per row) from the buffer pool —
+//   rank    per key column, unique's forms over the full selection (the table complete and verified: no deferred verify, no optimistic prefix, no head-only dense
+//           table, no radix form) and k_group_rank: the rank r_i of every selected row's key -> G for the first key, image = G * n_i + r_i for every later one;
+//   fold    the image is ranked again, as a transient UInt64 column, into G: the first appearance of image is the first appearance of the tuple so far.  The last
+//           ranking leaves q's bitmap narrowed to the groups' first rows — what the fetch gathers the keys from;
+//   reduce  one pass for the count and every reducer (k_group_acc_multi), launch_group_finish per reducer at the end.
+// A column that has no room for its scratch is DFDB_ERR_NOMEM, never a wrong answer.
+struct PooledColumn {                                          // a transient column over pooled memory: back to the pool when the call ends, the stream drained first
+  dfdb_ctx* ctx; Column col;
+  explicit PooledColumn(dfdb_ctx* c) : ctx(c) {}
+  ~PooledColumn() { (void)hipStreamSynchronize(ctx->stream); RecycleScope rs; col.data.release(); }
+};
+static uint64_t read_flag(dfdb_ctx* ctx, const DevBuf& flag) {
+  uint64_t f = 0;
+  HIP_CHECK(hipMemcpyAsync(&f, flag.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  stream_wait(ctx);
+  return f;
+}
+// the rank of every selected row's key in column kc (q's bitmap holds the full selection, gr_sel a copy of it) -> g_out, or the image gprev * n + rank -> img_out;
+// q's bitmap narrowed to the key's first occurrences on return.  Returns n, the key's distinct values
+static int64_t group_rank_key(dfdb_query* q, const Column& kc, const uint32_t* gprev, uint32_t* g_out, uint64_t* img_out, DevBuf& flag) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  RankArgs A{};
+  A.sel = q->gr_sel.as<uint64_t>(); A.nrows = t->nrows; A.gprev = gprev; A.g_out = g_out; A.img_out = img_out; A.flag = flag.as<uint64_t>();
+  HIP_CHECK(hipMemsetAsync(flag.p, 0, 8, s));
+  int64_t n = 0;
+  bool ok;
+  if (kc.dict_n > 0) {                                         // K9: the dictionary codes' ranks, no table
+    n = dict_unique(q, kc, &q->du_rank);
+    A.codes = kc.dict_codes.as<uint16_t>(); A.rank_of_code = q->du_rank.as<uint32_t>(); A.n = (uint64_t)n;
+    LaunchTimer lt(ctx, "group_rank");
+    ok = launch_group_rank(s, 1, A);
+  } else {
+    UniqueTables T;
+    T.allow_radix = false;                                      // (defer_verify, allow_optimistic, allow_head, group_probe: all off by default)
+    unique_impl_col(q, kc, &T);
+    n = query_count(q, -1);
+    A.n = (uint64_t)n; A.special = T.aux.as<uint64_t>();
+    A.keycol = kc.data.p; A.keydt = dt_base(kc.dtype); A.missing = dt_nullable(kc.dtype) && !T.is_str ? kc.missing.as<uint64_t>() : nullptr;
+    LaunchTimer lt(ctx, "group_rank");
+    if (T.dense) {
+      launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
+      A.lo = T.lo; A.range = T.range; A.gids = T.first.as<uint64_t>();
+      if (T.span_lo <= T.span_hi && T.span_hi < (uint64_t)T.range) {      // the table is laid out wider than the keys: only the span they cover (small: in LDS)
+        A.lo = T.lo + T.span_lo; A.range = (uint32_t)(T.span_hi - T.span_lo + 1); A.gids = T.first.as<uint64_t>() + T.span_lo;
+      }
+      ok = launch_group_rank(s, 2, A);
+    } else {
+      launch_group_ids(s, T.ent.as<UniqueEntry>(), T.cap, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
+      A.ent = T.ent.as<UniqueEntry>(); A.mask = T.cap - 1;
+      if (T.is_str) ok = launch_group_rank_str(s, A, kc.data.as<int32_t>(), (const int64_t*)kc.tile_off.p, kc.bytes.as<uint8_t>(), T.salt);
+      else ok = launch_group_rank(s, 0, A);
+    }
+    stream_wait(ctx);                                          // the tables die here
+    { RecycleScope rs; T = UniqueTables(); }
+  }
+  if (!ok) fail(DFDB_ERR_DEVICE, "groupreduce: the rank pass could not be launched");
+  if (read_flag(ctx, flag)) fail(DFDB_ERR_DEVICE, "groupreduce: a selected row's key has no rank among %lld distinct values", (long long)n);
+  return n;
+}
+
+void query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, int64_t* ngroups,
+                         int64_t* key_bytes) {
+  ensure_executed_checked(q);
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  if (nkeys < 1 || nkeys > 8 || !key_cols) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 1 to 8 key columns, not %d", nkeys);
+  if (nvals < 0 || nvals > kMaxReducers || (nvals > 0 && (!val_cols || !stats))) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 0 to %d reducers, not %d", kMaxReducers, nvals);
+  std::vector<const Column*> kcs((size_t)nkeys), vcs((size_t)nvals, nullptr);
+  for (int k = 0; k < nkeys; k++) {
+    const int32_t p = key_cols[k];
+    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+    if (q->proj[(size_t)p].expr->op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
+  }
+  std::vector<int> kinds((size_t)nvals, 0);
+  for (int m = 0; m < nvals; m++) {
+    const int32_t op = stats[m];
+    if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
+    if (op == DFDB_AGG_COUNT) continue;
+    const int32_t p = val_cols[m];
+    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+    const Node& ve = *q->proj[(size_t)p].expr;
+    if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
+    const int b = dt_base(ve.dtype);
+    kinds[(size_t)m] = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
+  }
+  // the shape that dfdb_query_groupreduce answers: handed to it (the same answers, bit for bit, at the same speed)
+  if (nkeys == 1 && nvals <= 1) {
+    query_groupreduce(q, key_cols[0], nvals ? val_cols[0] : -1, nvals ? stats[0] : DFDB_AGG_COUNT, ngroups, key_bytes);
+    q->gr_multi = 1;
+    q->gr_keys_n.assign(key_cols, key_cols + 1); q->gr_ops_n.assign(stats, stats + nvals); q->gr_kinds_n = kinds;
+    return;
+  }
+  for (int k = 0; k < nkeys; k++) kcs[(size_t)k] = &need_resident(t, q->proj[(size_t)key_cols[k]].expr->col);
+  for (int m = 0; m < nvals; m++) if (stats[m] != DFDB_AGG_COUNT) vcs[(size_t)m] = &need_resident(t, q->proj[(size_t)val_cols[m]].expr->col);
+  q->gr_state = 0; q->gr_n = 0; q->gr_multi = 2;
+  q->gr_keys_n.assign(key_cols, key_cols + nkeys); q->gr_ops_n.assign(stats, stats + nvals); q->gr_kinds_n = kinds;
+  if (ngroups) *ngroups = 0;
+  if (key_bytes) for (int k = 0; k < nkeys; k++) key_bytes[k] = 0;
+  const int64_t nsel = query_count(q, -1);
+  if (nsel == 0 || t->nrows == 0) { q->gr_state = 1; return; }
+  if (t->nrows >= (1ll << 32)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by several keys: group numbers are 32-bit, the table has %lld rows", (long long)t->nrows);
+  const size_t nw = padded_words(t->nrows);
+  q->gr_sel.ensure(nw * 8);
+  HIP_CHECK(hipMemcpyAsync(q->gr_sel.p, q->bitmap.p, nw * 8, hipMemcpyDeviceToDevice, s));
+  PooledScratch gbuf(ctx), flag(ctx);
+  PooledColumn image(ctx);
+  image.col.dtype = DFDB_U64; image.col.resident = true; image.col.nrows = t->nrows; image.col.name = "(groupreduce image)";
+  if (!try_ensure(gbuf.buf, (size_t)t->nrows * 4 + 256) || !try_ensure(flag.buf, 64) || (nkeys > 1 && !try_ensure(image.col.data, (size_t)t->nrows * 8 + 256)))
+    fail(DFDB_ERR_NOMEM, "groupreduce: no room for the group numbers of %lld rows", (long long)t->nrows);
+  uint32_t* G = gbuf.buf.as<uint32_t>();
+  int64_t ng = group_rank_key(q, *kcs[0], nullptr, G, nullptr, flag.buf);
+  for (int k = 1; k < nkeys; k++) {
+    restore_group_selection(q);                               // (the rank pass narrowed the bitmap: the full selection again)
+    (void)group_rank_key(q, *kcs[(size_t)k], G, nullptr, image.col.data.as<uint64_t>(), flag.buf);
+    restore_group_selection(q);
+    ng = group_rank_key(q, image.col, nullptr, G, nullptr, flag.buf);
+  }
+  // q's bitmap holds the groups' first rows (prefix scanned): G numbers them in that order
+  q->gr_cnt.ensure((size_t)ng * 8 + 64); q->gr_val.ensure((size_t)std::max(nvals, 1) * (size_t)ng * 8 + 64);
+  HIP_CHECK(hipMemsetAsync(q->gr_cnt.p, 0, (size_t)ng * 8 + 64, s));
+  for (int m = 0; m < nvals; m++) HIP_CHECK(hipMemsetAsync(q->gr_val.as<uint64_t>() + (size_t)m * ng, stats[m] == DFDB_AGG_MIN ? 0xFF : 0, (size_t)ng * 8, s));
+  MultiAccArgs A{};
+  A.sel = q->gr_sel.as<uint64_t>(); A.gid = G; A.nrows = t->nrows; A.nvals = nvals;
+  for (int m = 0; m < nvals; m++) { A.valcol[m] = vcs[(size_t)m] ? vcs[(size_t)m]->data.p : nullptr; A.valdt[m] = vcs[(size_t)m] ? dt_base(vcs[(size_t)m]->dtype) : 0; A.op[m] = stats[m]; A.kind[m] = kinds[(size_t)m]; }
+  A.cnt = q->gr_cnt.as<uint64_t>(); A.val = q->gr_val.as<uint64_t>(); A.ngroups = ng; A.flag = flag.buf.as<uint64_t>();
+  HIP_CHECK(hipMemsetAsync(flag.buf.p, 0, 8, s));
+  int form;
+  { LaunchTimer lt(ctx, "group_accumulate_multi"); form = launch_group_accumulate_multi(s, A); }
+  if (form < 0) fail(DFDB_ERR_DEVICE, "groupreduce: the accumulate pass could not be launched");
+  if (read_flag(ctx, flag.buf)) fail(DFDB_ERR_DEVICE, "groupreduce: a selected row has no group among %lld", (long long)ng);
+  prof_note(ctx, form ? "group_accumulate_multi.lds" : "group_accumulate_multi.global");
+  for (int m = 0; m < nvals; m++) launch_group_finish(s, q->gr_val.as<uint64_t>() + (size_t)m * ng, ng, kinds[(size_t)m], stats[m]);
+  stream_wait(ctx);
+  q->gr_n = ng; q->gr_state = 2;
+  if (ngroups) *ngroups = ng;
+  if (key_bytes) for (int k = 0; k < nkeys; k++) if (dt_base(kcs[(size_t)k]->dtype) == DFDB_STRING) key_bytes[k] = query_string_bytes(q, key_cols[k]);
+}
+
+// the groups' keys (one dfdb_outcol per key column, gathered over the first rows), counts and values (reducer-major; a count reducer's values are the counts)
+// -> caller buffers (host); restores the query's full selection afterwards
+void query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  if (q->gr_state == 0 || q->gr_multi == 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce_n has not been called (or the query was executed, reset or changed since)");
+  const int nvals = (int)q->gr_ops_n.size();
+  if (q->gr_multi == 1) {                                      // handed to dfdb_query_groupreduce: its fetch, and a count reducer's values from the counts
+    const int64_t ng = q->gr_n;
+    std::vector<int64_t> c((size_t)std::max<int64_t>(ng, 1));
+    const bool cnt_red = nvals == 1 && q->gr_ops_n[0] == DFDB_AGG_COUNT;
+    query_groupreduce_fetch(q, keys, c.data(), nvals && !cnt_red ? vals_i : nullptr, nvals && !cnt_red ? vals_f : nullptr);
+    for (int64_t g = 0; g < ng; g++) {
+      if (counts) counts[g] = c[(size_t)g];
+      if (cnt_red) { if (vals_i) vals_i[g] = c[(size_t)g]; if (vals_f) vals_f[g] = (double)c[(size_t)g]; }
+    }
+    q->gr_multi = 0;
+    return;
+  }
+  if (q->bitmap_rows != t->nrows) { q->gr_state = 0; fail(DFDB_ERR_ARGUMENT, "ArgumentError: the table changed between dfdb_query_groupreduce_n and its fetch"); }
+  const int64_t ng = q->gr_n;
+  const int nkeys = (int)q->gr_keys_n.size();
+  if (ng > 0) {
+    if (keys) for (int k = 0; k < nkeys; k++) { keys[k].memkind = keys[k].memkind == DFDB_MEM_DEVICE ? DFDB_MEM_DEVICE : DFDB_MEM_HOST; materialize_col(q, q->gr_keys_n[(size_t)k], keys[k], ng); }
+    std::vector<uint64_t> c((size_t)ng), v((size_t)ng * (size_t)nvals);
+    HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
+    if (nvals) HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, v.size() * 8, hipMemcpyDeviceToHost, s));
+    stream_wait(ctx);
+    if (counts) for (int64_t g = 0; g < ng; g++) counts[g] = (int64_t)c[(size_t)g];
+    for (int m = 0; m < nvals; m++) {
+      const int kind = q->gr_kinds_n[(size_t)m];
+      const bool cnt_red = q->gr_ops_n[(size_t)m] == DFDB_AGG_COUNT;
+      for (int64_t g = 0; g < ng; g++) {
+        const size_t i = (size_t)m * (size_t)ng + (size_t)g;
+        const uint64_t b = cnt_red ? c[(size_t)g] : v[i];
+        double d; memcpy(&d, &b, 8);
+        if (!cnt_red && kind == 2) { if (vals_f) vals_f[i] = d; if (vals_i) vals_i[i] = (int64_t)d; }
+        else { if (vals_i) vals_i[i] = (int64_t)b; if (vals_f) vals_f[i] = !cnt_red && kind == 1 ? (double)b : (double)(int64_t)b; }
+      }
+    }
+  } else if (keys) for (int k = 0; k < nkeys; k++) { keys[k].count = 0; keys[k].nbytes = 0; }
+  if (q->gr_state == 2) restore_group_selection(q);      // back to the full selection: bitmap + tile counts + prefix
+  q->gr_state = 0; q->gr_multi = 0;
 }
 
 }  // namespace dfdb

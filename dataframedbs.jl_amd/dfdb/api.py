@@ -1258,9 +1258,108 @@ def _groupreduce_frame(by: str, stat: str, keys, counts, vi, vf, vdt):
     return pd.DataFrame(res)
 
 
-def groupreduce(v: Union[DFView, DFTable], by: str, col: Optional[str] = None, stat: str = "count"):
+def _key_out(kdt: int, n: int, kb: int):
+    """a host dfdb_outcol for n keys of dtype kdt (kb string bytes) -> (outcol, a function that returns the keys as _groupreduce_raw does)"""
+    out = N.OutCol()
+    out.memkind = N.MEM_HOST
+    if (kdt & ir.DTYPE_MASK) == ir.STRING:
+        ksz = np.empty(max(n, 1), np.int32); kby = np.empty(max(kb, 1), np.uint8)
+        out.data, out.bytes, out.bytes_cap = ksz.ctypes.data, kby.ctypes.data, kb
+        return out, lambda: _to_user((ksz[:n].copy(), kby[:out.nbytes].copy()))
+    karr = np.empty(max(n, 1), ir.numpy_of_dtype(kdt))
+    kmiss = np.zeros(max(n, 1), np.uint8) if kdt & ir.NULLABLE else None
+    out.data = karr.ctypes.data
+    if kmiss is not None:
+        out.missing = kmiss.ctypes.data
+        return out, lambda: np.ma.masked_array(karr[:n].copy(), mask=kmiss[:n].astype(bool))
+    return out, lambda: karr[:n].copy()
+
+
+def _groupreduce_n_raw(q: "_Query", nkeys: int, vidx, stats):
+    """dfdb_query_groupreduce_n + _fetch: keys are projection columns [0, nkeys), reducer i is stats[i] over projection column vidx[i] ->
+    (list of key arrays, counts, values as Int64 bits [nvals, ng], values as Float64 [nvals, ng])"""
+    L = N.load()
+    nv = len(stats)
+    kc = (C.c_int32 * nkeys)(*range(nkeys))
+    vc = (C.c_int32 * max(nv, 1))(*vidx)
+    st = (C.c_int32 * max(nv, 1))(*[_STATS[s] for s in stats])
+    ng, kb = C.c_int64(), (C.c_int64 * nkeys)()
+    N.check(L.dfdb_query_groupreduce_n(q._h, kc, nkeys, vc, st, nv, C.byref(ng), kb))
+    n = ng.value
+    outs = (N.OutCol * nkeys)()
+    getters = []
+    for k in range(nkeys):
+        o, get = _key_out(q.coltype(k), n, kb[k])
+        outs[k] = o
+        getters.append((o, get))
+    counts = np.zeros(max(n, 1), np.int64); vi = np.zeros(max(n * nv, 1), np.int64); vf = np.zeros(max(n * nv, 1), np.float64)
+    N.check(L.dfdb_query_groupreduce_n_fetch(q._h, outs, counts.ctypes.data, vi.ctypes.data, vf.ctypes.data))
+    for k in range(nkeys):
+        getters[k][0].nbytes = outs[k].nbytes
+    keys = [get() for _, get in getters]
+    return keys, counts[:n].copy(), vi[:n * nv].reshape(nv, n).copy(), vf[:n * nv].reshape(nv, n).copy()
+
+
+def _groupreduce_n(v: Union[DFView, DFTable], by, reducers: dict):
+    import pandas as pd
+    v = v if isinstance(v, DFView) else DFView(v)
+    by = list(by)
+    if not 1 <= len(by) <= 8:
+        raise ValueError(f"ArgumentError: groupreduce takes 1 to 8 key columns, not {len(by)}")
+    if len(set(by)) != len(by):
+        raise ValueError("ArgumentError: a key column appears twice in `by`")
+    names = list(by)
+    specs = []
+    for name, spec in reducers.items():
+        if name in by or name == "count":
+            raise ValueError(f"ArgumentError: the result column {name!r} would be named twice")
+        if not (isinstance(spec, (tuple, list)) and len(spec) == 2):
+            raise ValueError(f"ArgumentError: reducer {name!r} must be (column, stat)")
+        c, stat = spec
+        if stat not in _STATS:
+            raise ValueError(f"ArgumentError: unknown statistic {stat}")
+        if stat != "count" and c not in names:
+            names.append(c)
+        specs.append((name, c, stat))
+    if len(specs) > 16:
+        raise ValueError(f"ArgumentError: groupreduce takes 0 to 16 reducers, not {len(specs)}")
+    sub = DFView(v.table, Projection({nm: v.projection.cols[nm] for nm in names}), v.selection)
+    q = _Query(sub)
+    vidx = [names.index(c) if stat != "count" else -1 for _, c, stat in specs]
+    keys, counts, vi, vf = _groupreduce_n_raw(q, len(by), vidx, [stat for _, _, stat in specs])
+    res = {b: k for b, k in zip(by, keys)}
+    res["count"] = counts
+    for i, (name, c, stat) in enumerate(specs):
+        if stat == "count":
+            res[name] = counts
+            continue
+        vdt = q.coltype(vidx[i]) & ir.DTYPE_MASK
+        isf = vdt in (ir.F32, ir.F64)
+        uns = vdt in (ir.U8, ir.U16, ir.U32, ir.U64)
+        vals = vf[i] if isf else (vi[i].astype(np.uint64) if uns and stat != "mean" else vi[i])
+        if stat == "mean":
+            vals = (vf[i] if isf else (vi[i].astype(np.uint64).astype(np.float64) if uns else vi[i].astype(np.float64))) / np.maximum(counts, 1)
+        res[name] = vals
+    return pd.DataFrame(res)
+
+
+def groupreduce(v: Union[DFView, DFTable], by, col: Optional[str] = None, stat: str = "count", **reducers):
     """groupreduce(view, (:by,); out = :col => Stat()): one row per distinct value of `by` over the view's selected rows, in order of first
     appearance (the reference's group_map numbering), with the group's row count and stat(col) — stat in count / sum / min / max / mean.
-    Returns a pandas.DataFrame with columns [by, "count", stat]."""
-    sub, with_value = _groupreduce_view(v, by, col, stat)
-    return _groupreduce_frame(by, stat, *_groupreduce_raw(_Query(sub), with_value, stat))
+    Returns a pandas.DataFrame with columns [by, "count", stat].
+
+    groupreduce(view, ("a", "b"), name=("col", "stat"), ...) (aggregate.jl:1-14: a tuple of keys, any number of `name = col => Stat()`): one row per
+    distinct tuple, in order of the first selected row that holds it, with the count and every reducer — one device pass for all of them
+    (dfdb_query_groupreduce_n).  Columns [*by, "count", *names] in keyword order.  A tuple `by` with col / stat alone is one reducer named stat."""
+    if isinstance(by, str) and not reducers:
+        sub, with_value = _groupreduce_view(v, by, col, stat)
+        return _groupreduce_frame(by, stat, *_groupreduce_raw(_Query(sub), with_value, stat))
+    if reducers and (col is not None or stat != "count"):
+        raise ValueError("ArgumentError: give either col / stat or name=(col, stat) reducers, not both")
+    if isinstance(by, str):
+        by = (by,)
+    elif not isinstance(by, (tuple, list)):
+        raise ValueError(f"ArgumentError: `by` must be a column name or a tuple of them, not {type(by).__name__}")
+    if not reducers and (col is not None or stat != "count"):
+        reducers = {stat: (col, stat)}
+    return _groupreduce_n(v, by, reducers)

@@ -636,6 +636,63 @@ function gpu_groupreduce(v::DFView, by::Symbol, col::Union{Symbol,Nothing} = not
     end
 end
 
+"""
+groupreduce(view, (:a, :b); name = :col => Stat(), ...) on the device — the reference's own signature (src/tables/aggregate.jl:1-14: a tuple of key columns,
+one `name = col => Stat()` per reducer; lines 19-30 number the groups by first appearance of the key tuple and stop).  Returns a DataFrame with one row per
+distinct tuple in order of the first selected row that holds it: the key columns, `:count`, then one column per reducer in keyword order.  A stat is a
+Symbol (:count, :sum, :minimum, :maximum, :mean) or an instance such as `Sum()` / `Mean()` (mapped by `nameof(typeof(stat))`).  One device call for every
+reducer (dfdb_query_groupreduce_n).  Not yet on a sharded table.
+"""
+function gpu_groupreduce(v::DFView, by::Tuple{Vararg{Symbol}}; cols...)
+    sharded() && throw(ArgumentError("groupreduce by a tuple of keys is not yet on a sharded table"))
+    1 <= length(by) <= 8 || throw(ArgumentError("groupreduce takes 1 to 8 key columns, not $(length(by))"))
+    codes = Dict(:count => 0, :sum => 1, :minimum => 2, :min => 2, :maximum => 3, :max => 3, :mean => 1)
+    names = collect(by)
+    reds = Tuple{Symbol,Symbol,Symbol}[]                         # (result name, column, stat)
+    for (name, spec) in pairs(cols)
+        c, st = spec.first, spec.second
+        stat = st isa Symbol ? st : Symbol(lowercase(String(nameof(typeof(st)))))
+        haskey(codes, stat) || throw(ArgumentError("unknown statistic $(st)"))
+        stat != :count && !(c in names) && push!(names, c)
+        push!(reds, (name, c, stat))
+    end
+    sub = v[:, names]
+    keyview = sub[:, collect(by)]
+    nk = length(by); nv = length(reds)
+    kidx = Int32.(0:nk-1)
+    vidx = Int32[r[3] == :count ? -1 : findfirst(==(r[2]), names) - 1 for r in reds]
+    stats = Int32[codes[r[3]] for r in reds]
+    with_query(sub) do q
+        ng = Ref{Int64}(0); kb = zeros(Int64, nk)
+        check(ccall((:dfdb_query_groupreduce_n, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int64}, Ptr{Int64}),
+                    q, kidx, nk, vidx, stats, nv, ng, kb))
+        n = ng[]
+        outs, bufs = alloc_outputs(keyview, n, i -> begin
+            dt = Ref{Int32}(0)
+            check(ccall((:dfdb_query_coltype, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), q, i, dt)); dt[]
+        end, i -> kb[i + 1])
+        counts = Vector{Int64}(undef, n); vi = Vector{Int64}(undef, n * nv); vf = Vector{Float64}(undef, n * nv)
+        GC.@preserve bufs outs counts vi vf check(ccall((:dfdb_query_groupreduce_n_fetch, LIB), Int32, (Ptr{Cvoid}, Ptr{OutCol}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                                                         q, outs, counts, vi, vf))
+        res = DataFrames.DataFrame()
+        for (b, k) in zip(by, finish_columns(keyview, bufs))
+            res[!, b] = k
+        end
+        res[!, :count] = counts
+        for (j, (name, c, stat)) in enumerate(reds)
+            r = (j - 1) * n + 1 : j * n
+            if stat == :count
+                res[!, name] = counts
+                continue
+            end
+            T = Base.nonmissingtype(DataFrameDBs.coltype(sub.projection, vidx[j] + 1))
+            res[!, name] = stat == :mean ? (T <: AbstractFloat ? vf[r] : (T <: Unsigned ? Float64.(reinterpret(UInt64, vi[r])) : Float64.(vi[r]))) ./ max.(counts, 1) :
+                           T <: AbstractFloat ? vf[r] : (T <: Unsigned ? reinterpret(UInt64, vi[r]) : vi[r])
+        end
+        res
+    end
+end
+
 # ---------------------------------------------------------------- write side (create_table / add_column!)
 struct SizeStatsC; rows::Int64; compressed::Int64; uncompressed::Int64; end
 

@@ -343,6 +343,21 @@ int32_t dfdb_query_unique(dfdb_query* q, int32_t proj_col);
 int32_t dfdb_query_groupreduce(dfdb_query* q, int32_t key_col, int32_t val_col, int32_t stat, int64_t* ngroups, int64_t* key_string_bytes);
 int32_t dfdb_query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* values_i, double* values_f);
 
+/* groupreduce(view, by::Tuple{Vararg{Symbol}}; cols...) with every `name = col => Stat()` of cols (src/tables/aggregate.jl:1-14: a tuple of key columns,
+ * `group_view = view[:, (__by = by => (a...) -> tuple(a...),)]`, one reducer per keyword; lines 19-30 number the groups by first appearance of the key TUPLE,
+ * group_map[elem] = length(group_map) + 1, and the reference stops there).  Completed to that intent: one group per distinct tuple of the projection columns
+ * key_cols[0 .. nkeys) (1 to 8 plain columns, any key dfdb_query_groupreduce takes; tuples compare element by element with isequal), groups in order of the
+ * first selected row that holds the tuple, per group the row count and, for each of the nvals (0 to 16) reducers, stats[i] over projection column val_cols[i]
+ * (DFDB_AGG_COUNT / _SUM / _MIN / _MAX over a plain numeric column, the rules of dfdb_query_groupreduce; a count's values are the counts and its column is not
+ * read; one column may serve several reducers).  Call 1 evaluates on the device and returns the number of groups and, per key column, its string bytes
+ * (key_string_bytes: nkeys values).  Call 2 copies the keys (keys: nkeys dfdb_outcols sized for ngroups rows), the counts and the values — reducer-major,
+ * value j of reducer i at [i * ngroups + j]; values_i for integer columns (unsigned ones as their bits), values_f for floats, either may be NULL — and puts
+ * the query's full selection back (between the calls it is narrowed to the groups' first rows, as after dfdb_query_groupreduce).  nkeys = 1 with at most
+ * one reducer is answered by dfdb_query_groupreduce itself. */
+int32_t dfdb_query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals,
+                                 int64_t* ngroups, int64_t* key_string_bytes);
+int32_t dfdb_query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* values_i, double* values_f);
+
 /* forget the cached execution so the next count/indices/materialize re-evaluates the selection (a new
  * BlocksIterator in the reference: blocksiterator.jl:20-44). */
 int32_t dfdb_query_reset(dfdb_query* q);
