@@ -453,7 +453,7 @@ int32_t dfdb_query_groupreduce(dfdb_query* q, int32_t key_col, int32_t val_col, 
   return guard([&] { NEEDQT(q); if (query_out_of_core(q)) { ooc_groupreduce(q, key_col, val_col, stat, ngroups, key_string_bytes); return; } query_groupreduce(q, key_col, val_col, stat, ngroups, key_string_bytes); });
 }
 int32_t dfdb_query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* values_i, double* values_f) {
-  return guard([&] { NEEDQT(q); if (q->ooc && q->ooc->gr_pending) { ooc_groupreduce_fetch(q, keys, counts, values_i, values_f); return; } query_groupreduce_fetch(q, keys, counts, values_i, values_f); });
+  return guard([&] { NEEDQT(q); if (q->ooc && q->ooc->pending == OocState::GROUPREDUCE) { ooc_groupreduce_fetch(q, OocState::GROUPREDUCE, keys, counts, values_i, values_f); return; } query_groupreduce_fetch(q, keys, counts, values_i, values_f); });
 }
 int32_t dfdb_query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals,
                                  int64_t* ngroups, int64_t* key_string_bytes) {
@@ -464,7 +464,7 @@ int32_t dfdb_query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t
   });
 }
 int32_t dfdb_query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* values_i, double* values_f) {
-  return guard([&] { NEEDQT(q); if (q->ooc && q->ooc->grn_pending) { ooc_groupreduce_n_fetch(q, keys, counts, values_i, values_f); return; } query_groupreduce_n_fetch(q, keys, counts, values_i, values_f); });
+  return guard([&] { NEEDQT(q); if (q->ooc && q->ooc->pending == OocState::GROUPREDUCE_N) { ooc_groupreduce_fetch(q, OocState::GROUPREDUCE_N, keys, counts, values_i, values_f); return; } query_groupreduce_n_fetch(q, keys, counts, values_i, values_f); });
 }
 int32_t dfdb_query_hint_aggregate(dfdb_query* q, int32_t op, int32_t proj_col) {
   return guard([&] { NEEDQ(q); q->hint_agg_op = op; q->hint_agg_proj = proj_col; });   // (affects the NEXT execution only: an executed query keeps its results)

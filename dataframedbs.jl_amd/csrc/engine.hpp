@@ -147,9 +147,10 @@ struct dfdb_query {
   // dfdb_query_groupreduce: the full selection set aside, per-group counts / values, what the fetch needs
   dfdb::DevBuf gr_sel, gr_cnt, gr_val, gr_keys;     // (gr_keys: the key column's values at the groups' first rows, group order — k_group_acc_hash_lds)
   dfdb::DevBuf du_first, du_rows, du_rank;   // dict_unique's scratch (first row per code, the group rows, rank of every code)
-  int64_t gr_n = 0; int gr_key = -1, gr_op = 0, gr_kind = 0, gr_state = 0;   // state 0: none, 1: empty result, 2: results + narrowed selection pending
-  // dfdb_query_groupreduce_n (the same gr_state; gr_multi 0: a dfdb_query_groupreduce, 1: an _n call it was handed to, 2: an _n call of its own — gr_cnt [ng],
-  // gr_val [nvals][ng]); its key columns and its reducers' operators and value kinds
+  int64_t gr_n = 0; int gr_state = 0;   // state 0: none, 1: empty result, 2: results + narrowed selection pending
+  // whose result is pending — gr_multi 0: a dfdb_query_groupreduce, 1: a dfdb_query_groupreduce_n call that was handed to it, 2: an _n call of its own (gr_cnt
+  // [ng], gr_val [nvals][ng]) — and that call's key columns and its reducers' operators and value kinds (0 signed, 1 unsigned, 2 float); dfdb_query_groupreduce
+  // records its one key, operator and kind here too
   int gr_multi = 0;
   std::vector<int32_t> gr_keys_n; std::vector<int> gr_ops_n, gr_kinds_n;
   int mask_from = -1;          // table ordinal of the column whose calibrated bitmap this query has borrowed (-1: its own)
@@ -204,6 +205,12 @@ void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, 
 void query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, int64_t* ngroups,
                          int64_t* key_bytes);
 void query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f);
+// THE check of groupreduce's arguments, resident or streamed, one key or a tuple: raises what dfdb_query_groupreduce / _n document, returns the reducers' value
+// kinds (0 signed, 1 unsigned, 2 float; a count: 0).  by_prefix stands before "groupreduce by a computed column" (the streamed unique names itself there)
+std::vector<int> groupreduce_check(const dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals,
+                                   const char* by_prefix = "");
+// n 64-bit results of one reducer -> the caller's values_i / values_f (either may be null) by the value column's kind
+void group_values_out(const uint64_t* bits, int64_t n, int kind, int64_t* vals_i, double* vals_f);
 void query_return_mask(dfdb_query* q);            // give a borrowed calibrated bitmap back to its column
 // query.cpp helpers that unique.cpp builds on
 size_t padded_words(int64_t nrows);               // bitmap words for n rows, padded so that K2's 64-word (4096-row) reads stay in bounds

@@ -1093,22 +1093,32 @@ namespace dfdb {
 namespace {
 void put_i64(std::vector<uint8_t>& b, int64_t v) { const size_t o = b.size(); b.resize(o + 8); memcpy(b.data() + o, &v, 8); }
 void put_vec(std::vector<uint8_t>& b, const void* p, size_t n) { put_i64(b, (int64_t)n); const size_t o = b.size(); b.resize(o + n); if (n) memcpy(b.data() + o, p, n); }
+// one record per part: ng, the key blocks (their number first), the counts, the value arrays (their number first); first_rows stay at home
 std::vector<uint8_t> pack_part(const GroupPart& p) {
   std::vector<uint8_t> b;
   put_i64(b, p.ng);
-  put_vec(b, p.key_data.data(), p.key_data.size()); put_vec(b, p.key_missing.data(), p.key_missing.size()); put_vec(b, p.key_bytes.data(), p.key_bytes.size());
-  put_vec(b, p.counts.data(), p.counts.size() * 8); put_vec(b, p.vals.data(), p.vals.size() * 8);
+  put_i64(b, (int64_t)p.keys.size());
+  for (const GroupKeys& k : p.keys) { put_vec(b, k.key_data.data(), k.key_data.size()); put_vec(b, k.key_missing.data(), k.key_missing.size()); put_vec(b, k.key_bytes.data(), k.key_bytes.size()); }
+  put_vec(b, p.counts.data(), p.counts.size() * 8);
+  put_i64(b, (int64_t)p.vals.size());
+  for (const std::vector<uint64_t>& v : p.vals) put_vec(b, v.data(), v.size() * 8);
   return b;
 }
 GroupPart unpack_part(const uint8_t* b, size_t n) {
   GroupPart p; size_t o = 0;
   auto i64 = [&]() { if (o + 8 > n) fail(DFDB_ERR_DEVICE, "group exchange: truncated record"); int64_t v; memcpy(&v, b + o, 8); o += 8; return v; };
-  auto vec = [&](std::vector<uint8_t>& v) { const int64_t m = i64(); if (m < 0 || o + (size_t)m > n) fail(DFDB_ERR_DEVICE, "group exchange: truncated record"); v.assign(b + o, b + o + m); o += (size_t)m; };
+  auto vec = [&](auto& v) {
+    const int64_t m = i64();
+    if (m < 0 || o + (size_t)m > n) fail(DFDB_ERR_DEVICE, "group exchange: truncated record");
+    v.resize((size_t)m / sizeof(v[0])); if (m) memcpy(v.data(), b + o, v.size() * sizeof(v[0])); o += (size_t)m;
+  };
+  auto count = [&](int64_t most) { const int64_t m = i64(); if (m < 0 || m > most) fail(DFDB_ERR_DEVICE, "group exchange: truncated record"); return (size_t)m; };
   p.ng = i64();
-  vec(p.key_data); vec(p.key_missing); vec(p.key_bytes);
-  std::vector<uint8_t> c, v; vec(c); vec(v);
-  p.counts.resize(c.size() / 8); if (!c.empty()) memcpy(p.counts.data(), c.data(), c.size());
-  p.vals.resize(v.size() / 8); if (!v.empty()) memcpy(p.vals.data(), v.data(), v.size());
+  p.keys.resize(count(8));
+  for (GroupKeys& k : p.keys) { vec(k.key_data); vec(k.key_missing); vec(k.key_bytes); }
+  vec(p.counts);
+  p.vals.resize(count(kMaxReducers));
+  for (std::vector<uint64_t>& v : p.vals) vec(v);
   return p;
 }
 }  // namespace
@@ -1162,7 +1172,7 @@ static std::vector<GroupPart> all_parts(dfdb_group* g, std::vector<GroupPart>& l
   return parts;
 }
 
-static void group_reduce_all(dfdb_gquery* gq, int32_t key_p, int32_t val_p, int32_t op, bool with_stats) {
+static void group_reduce_all(dfdb_gquery* gq, int32_t key_p, int32_t val_p, int32_t op) {
   dfdb_group* g = gq->gt->g;
   fresh(g);
   gq->merged = GroupMerged{};
@@ -1170,20 +1180,20 @@ static void group_reduce_all(dfdb_gquery* gq, int32_t key_p, int32_t val_p, int3
   const int nl = g->nlocal();
   std::vector<GroupPart> local((size_t)nl);
   std::vector<int> kinds((size_t)nl, 0);
+  const int32_t nvals = op == DFDB_AGG_COUNT ? 0 : 1;      // (a count has no value array)
   for_shards_deferred(g, [&](int l) {
     dfdb_query* q = gq->shard[(size_t)l];
     GroupPart& part = local[(size_t)l];
     if (query_out_of_core(q)) { kinds[(size_t)l] = ooc_group_part(q, key_p, val_p, op, part); return; }   // (its chunks merged in chunk order: one part)
-    int64_t ng = 0, kb = 0;
-    query_groupreduce(q, key_p, val_p, op, &ng, &kb);     // the shard's own device reduction (k_unique.hip / k_dict.hip); the selection is the group's
-    kinds[(size_t)l] = q->gr_kind;
-    fetch_group_part(q, key_p, ng, kb, false, part);      // (puts the shard's full selection back)
+    // the shard's own device reduction (k_unique.hip / k_dict.hip; the selection is the group's) and its fetch, which puts the shard's full selection back
+    fetch_group_part(q, &key_p, 1, &val_p, &op, nvals, false, part);
+    if (nvals) kinds[(size_t)l] = q->gr_kinds_n[0];
   });
   const std::vector<GroupPart> parts = all_parts(g, local);
-  const int32_t kdt = gq->shard[0]->proj[(size_t)key_p].expr->dtype;
-  const int kind = kinds[0];
   GroupMerged& m = gq->merged;
-  m.key_dtype = kdt; m.kind = kind; m.op = op; m.with_stats = with_stats;
+  m.key_dtypes.assign(1, gq->shard[0]->proj[(size_t)key_p].expr->dtype);
+  m.kinds.assign((size_t)nvals, kinds[0]); m.ops.assign((size_t)nvals, op);
+  m.keys.resize(1); m.vals.resize((size_t)nvals);
   GroupMerger mg;
   for (const GroupPart& p : parts) mg.add(m, p);           // rank order = table order: a key keeps the place of its first appearance
   m.valid = true;
@@ -1192,7 +1202,7 @@ static void group_reduce_all(dfdb_gquery* gq, int32_t key_p, int32_t val_p, int3
 static void group_reduce_fetch(dfdb_gquery* gq, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
   GroupMerged& m = gq->merged;
   if (!m.valid) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_group_query_unique / _groupreduce has not been called");
-  merged_fetch(m, keys, counts, vals_i, vals_f);
+  merged_fetch(m, keys, counts, vals_i, vals_f, true);
 }
 }  // namespace dfdb
 
@@ -1204,9 +1214,9 @@ extern "C" {
 int32_t dfdb_group_query_unique(dfdb_gquery* gq, int32_t proj_col, int64_t* ndistinct, int64_t* string_bytes) {
   return gguard([&] {
     GNEEDQ(gq);
-    group_reduce_all(gq, proj_col, -1, DFDB_AGG_COUNT, false);
+    group_reduce_all(gq, proj_col, -1, DFDB_AGG_COUNT);
     if (ndistinct) *ndistinct = gq->merged.ng;
-    if (string_bytes) *string_bytes = (int64_t)gq->merged.key_bytes.size();
+    if (string_bytes) *string_bytes = (int64_t)gq->merged.keys[0].key_bytes.size();
   });
 }
 int32_t dfdb_group_query_unique_fetch(dfdb_gquery* gq, dfdb_outcol* keys) {
@@ -1218,9 +1228,9 @@ int32_t dfdb_group_query_unique_fetch(dfdb_gquery* gq, dfdb_outcol* keys) {
 int32_t dfdb_group_query_groupreduce(dfdb_gquery* gq, int32_t key_col, int32_t val_col, int32_t stat, int64_t* ngroups, int64_t* key_string_bytes) {
   return gguard([&] {
     GNEEDQ(gq);
-    group_reduce_all(gq, key_col, val_col, stat, true);
+    group_reduce_all(gq, key_col, val_col, stat);
     if (ngroups) *ngroups = gq->merged.ng;
-    if (key_string_bytes) *key_string_bytes = (int64_t)gq->merged.key_bytes.size();
+    if (key_string_bytes) *key_string_bytes = (int64_t)gq->merged.keys[0].key_bytes.size();
   });
 }
 int32_t dfdb_group_query_groupreduce_fetch(dfdb_gquery* gq, dfdb_outcol* keys, int64_t* counts, int64_t* values_i, double* values_f) {

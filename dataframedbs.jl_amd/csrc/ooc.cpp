@@ -31,145 +31,119 @@ uint64_t fold_bits(uint64_t a, uint64_t b, int dt, int op) {
   return op == DFDB_AGG_SUM ? a + b : (uint64_t)fold_t<int64_t>((int64_t)a, (int64_t)b, op);
 }
 
-// isequal as a byte string: the missing flag, then the value's bytes with every NaN folded onto one (isequal(NaN, -NaN); -0.0 and 0.0 stay apart)
-static std::string merge_key(int32_t kdt, const GroupPart& p, int64_t j, int64_t& byte_off) {
+// isequal as a byte string, appended to k: the missing flag, then the value's bytes with every NaN folded onto one (isequal(NaN, -NaN); -0.0 and 0.0 stay apart)
+static void merge_key(std::string& k, int32_t kdt, const GroupKeys& p, int64_t j, int64_t& byte_off) {
   const bool miss = !p.key_missing.empty() && p.key_missing[(size_t)j];
-  std::string k(1, miss ? '\1' : '\0');
+  const size_t flag = k.size();
+  k.push_back(miss ? '\1' : '\0');
   if (dt_base(kdt) == DFDB_STRING) {
     int32_t sz; memcpy(&sz, p.key_data.data() + (size_t)j * 4, 4);
-    if (sz < 0) { k[0] = '\1'; return k; }
+    if (sz < 0) { k[flag] = '\1'; return; }
     k.append((const char*)p.key_bytes.data() + byte_off, (size_t)sz); byte_off += sz;
-    return k;
+    return;
   }
-  if (miss) return k;                                    // (the bytes under a missing flag are garbage: quirk Q11)
+  if (miss) return;                                      // (the bytes under a missing flag are garbage: quirk Q11)
   const int w = dt_width(kdt);
   const uint8_t* v = p.key_data.data() + (size_t)j * w;
-  if (dt_base(kdt) == DFDB_F64) { double d; memcpy(&d, v, 8); if (std::isnan(d)) { k.append("NaN"); return k; } }
-  if (dt_base(kdt) == DFDB_F32) { float f; memcpy(&f, v, 4); if (std::isnan(f)) { k.append("NaN"); return k; } }
+  if (dt_base(kdt) == DFDB_F64) { double d; memcpy(&d, v, 8); if (std::isnan(d)) { k.append("NaN"); return; } }
+  if (dt_base(kdt) == DFDB_F32) { float f; memcpy(&f, v, 4); if (std::isnan(f)) { k.append("NaN"); return; } }
   k.append((const char*)v, (size_t)w);
-  return k;
 }
 
 void GroupMerger::add(GroupMerged& m, const GroupPart& p) {
-  const int32_t kdt = m.key_dtype;
-  const bool is_str = dt_base(kdt) == DFDB_STRING;
-  const int w = is_str ? 4 : dt_width(kdt);
+  const size_t nk = m.key_dtypes.size(), nv = m.ops.size();
+  if (p.keys.size() != nk || p.vals.size() != nv) fail(DFDB_ERR_DEVICE, "group merge: a part of %zu key columns and %zu reducers among parts of %zu and %zu", p.keys.size(), p.vals.size(), nk, nv);
   const bool rows = !p.first_rows.empty();
-  int64_t boff = 0;
-  for (int64_t j = 0; j < p.ng; j++) {                     // part order = table order: a key keeps the place of its first appearance
-    const int64_t b0 = boff;
-    const std::string k = merge_key(kdt, p, j, boff);
-    auto it = slot.find(k);
-    if (it == slot.end()) {
-      slot.emplace(k, m.ng++);
-      m.key_data.insert(m.key_data.end(), p.key_data.begin() + j * w, p.key_data.begin() + (j + 1) * w);
-      m.key_missing.push_back(k[0] == '\1' ? 1 : 0);
-      if (is_str) m.key_bytes.insert(m.key_bytes.end(), p.key_bytes.begin() + b0, p.key_bytes.begin() + boff);
-      m.counts.push_back(p.counts[(size_t)j]); m.vals.push_back(p.vals[(size_t)j]);
-      if (rows) m.first_rows.push_back(p.first_rows[(size_t)j]);
-      continue;
-    }
-    const size_t s = (size_t)it->second;
-    m.counts[s] += p.counts[(size_t)j];
-    const uint64_t a = m.vals[s], b = p.vals[(size_t)j];
-    if (m.op == DFDB_AGG_COUNT) m.vals[s] = a + b;
-    else m.vals[s] = fold_bits(a, b, m.kind == 2 ? DFDB_F64 : (m.kind == 1 ? DFDB_U64 : DFDB_I64), m.op);   // wrapping Int sums, Float64 sums of the parts' sums, NaN-propagating min / max
-  }
-}
-
-void GroupMergerN::add(GroupMergedN& m, const GroupPartN& p) {
-  const size_t nk = m.keys.size(), nv = m.ops.size();
   std::vector<int64_t> boff(nk, 0), b0(nk);
-  std::vector<std::string> ki(nk);
+  std::vector<size_t> at(nk);                              // where key i's image starts in k
+  std::string k;
   for (int64_t j = 0; j < p.ng; j++) {                     // part order = table order: a tuple keeps the place of its first appearance
-    std::string k;
+    k.clear();
     for (size_t i = 0; i < nk; i++) {
       b0[i] = boff[i];
-      ki[i] = merge_key(m.keys[i].key_dtype, p.keys[i], j, boff[i]);
-      const uint32_t len = (uint32_t)ki[i].size();
-      k.append((const char*)&len, 4); k.append(ki[i]);
+      k.append(4, '\0'); at[i] = k.size();
+      merge_key(k, m.key_dtypes[i], p.keys[i], j, boff[i]);
+      const uint32_t len = (uint32_t)(k.size() - at[i]);
+      memcpy(&k[at[i] - 4], &len, 4);
     }
-    auto it = slot.find(k);
-    if (it == slot.end()) {
-      slot.emplace(std::move(k), m.ng++);
+    const auto ins = slot.try_emplace(k, m.ng);
+    if (ins.second) {
+      m.ng++;
       for (size_t i = 0; i < nk; i++) {
-        GroupMerged& km = m.keys[i]; const GroupPart& kp = p.keys[i];
-        const bool is_str = dt_base(km.key_dtype) == DFDB_STRING;
-        const int w = is_str ? 4 : dt_width(km.key_dtype);
+        GroupKeys& km = m.keys[i]; const GroupKeys& kp = p.keys[i];
+        const bool is_str = dt_base(m.key_dtypes[i]) == DFDB_STRING;
+        const int w = is_str ? 4 : dt_width(m.key_dtypes[i]);
         km.key_data.insert(km.key_data.end(), kp.key_data.begin() + j * w, kp.key_data.begin() + (j + 1) * w);
-        km.key_missing.push_back(ki[i][0] == '\1' ? 1 : 0);
+        km.key_missing.push_back(k[at[i]] == '\1' ? 1 : 0);
         if (is_str) km.key_bytes.insert(km.key_bytes.end(), kp.key_bytes.begin() + b0[i], kp.key_bytes.begin() + boff[i]);
-        km.ng++;
       }
       m.counts.push_back(p.counts[(size_t)j]);
       for (size_t r = 0; r < nv; r++) m.vals[r].push_back(p.vals[r][(size_t)j]);
+      if (rows) m.first_rows.push_back(p.first_rows[(size_t)j]);
       continue;
     }
-    const size_t s = (size_t)it->second;
+    const size_t s = (size_t)ins.first->second;
     m.counts[s] += p.counts[(size_t)j];
     for (size_t r = 0; r < nv; r++) {
       const uint64_t a = m.vals[r][s], b = p.vals[r][(size_t)j];
       if (m.ops[r] == DFDB_AGG_COUNT) m.vals[r][s] = a + b;
-      else m.vals[r][s] = fold_bits(a, b, m.kinds[r] == 2 ? DFDB_F64 : (m.kinds[r] == 1 ? DFDB_U64 : DFDB_I64), m.ops[r]);
+      else m.vals[r][s] = fold_bits(a, b, m.kinds[r] == 2 ? DFDB_F64 : (m.kinds[r] == 1 ? DFDB_U64 : DFDB_I64), m.ops[r]);   // wrapping Int sums, Float64 sums of the parts' sums, NaN-propagating min / max
     }
   }
 }
 
-void fetch_group_part(dfdb_query* q, int32_t key_p, int64_t ng, int64_t kb, bool with_rows, GroupPart& part) {
-  const int32_t kdt = q->proj[(size_t)key_p].expr->dtype;
-  const bool is_str = dt_base(kdt) == DFDB_STRING;
-  part.ng = ng;
-  part.key_data.resize((size_t)ng * (size_t)(is_str ? 4 : dt_width(kdt)));
-  if (dt_nullable(kdt) && !is_str) part.key_missing.assign((size_t)ng, 0);
-  part.key_bytes.resize((size_t)kb);
-  part.counts.assign((size_t)ng, 0); part.vals.assign((size_t)ng, 0);
+void fetch_group_part(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, bool with_rows, GroupPart& part) {
+  int64_t ng = 0;
+  std::vector<int64_t> kb((size_t)nkeys, 0);
+  query_groupreduce_n(q, key_cols, nkeys, val_cols, stats, nvals, &ng, kb.data());   // (one key with at most one reducer: query_groupreduce itself)
+  part.ng = ng; part.keys.resize((size_t)nkeys);
+  std::vector<dfdb_outcol> outs((size_t)nkeys);
+  for (int k = 0; k < nkeys; k++) {
+    const int32_t kdt = q->proj[(size_t)key_cols[k]].expr->dtype;
+    const bool is_str = dt_base(kdt) == DFDB_STRING;
+    GroupKeys& kp = part.keys[(size_t)k];
+    kp.key_data.resize((size_t)ng * (size_t)(is_str ? 4 : dt_width(kdt)));
+    if (dt_nullable(kdt) && !is_str) kp.key_missing.assign((size_t)ng, 0);
+    kp.key_bytes.resize((size_t)kb[(size_t)k]);
+    dfdb_outcol& oc = outs[(size_t)k];
+    oc = dfdb_outcol{}; oc.memkind = DFDB_MEM_HOST; oc.data = kp.key_data.data(); oc.bytes = kp.key_bytes.data(); oc.bytes_cap = kb[(size_t)k];
+    oc.missing = kp.key_missing.empty() ? nullptr : kp.key_missing.data();
+  }
+  part.counts.assign((size_t)ng, 0);
   if (with_rows) {                                         // between groupreduce and its fetch q's selection IS the first occurrences (dfdb.h)
     part.first_rows.assign((size_t)ng, 0);
     if (ng > 0) { int64_t got = 0; query_select_indices(q, part.first_rows.data(), ng, DFDB_MEM_HOST, &got); if (got != ng) fail(DFDB_ERR_DEVICE, "groupreduce: %lld first rows for %lld groups", (long long)got, (long long)ng); }
   }
-  dfdb_outcol o{}; o.memkind = DFDB_MEM_HOST; o.data = part.key_data.data(); o.bytes = part.key_bytes.data(); o.bytes_cap = kb;
-  o.missing = part.key_missing.empty() ? nullptr : part.key_missing.data();
-  std::vector<int64_t> vi((size_t)ng); std::vector<double> vf((size_t)ng);
-  query_groupreduce_fetch(q, &o, part.counts.data(), vi.data(), vf.data());   // (puts the full selection back)
-  for (int64_t j = 0; j < ng; j++) { if (q->gr_kind == 2) memcpy(&part.vals[(size_t)j], &vf[(size_t)j], 8); else part.vals[(size_t)j] = (uint64_t)vi[(size_t)j]; }
+  std::vector<int64_t> vi((size_t)ng * (size_t)nvals); std::vector<double> vf((size_t)ng * (size_t)nvals);
+  query_groupreduce_n_fetch(q, outs.data(), part.counts.data(), vi.data(), vf.data());   // (puts the full selection back)
+  part.vals.assign((size_t)nvals, std::vector<uint64_t>((size_t)ng));
+  for (int r = 0; r < nvals; r++) {
+    const size_t r0 = (size_t)r * (size_t)ng;
+    if (stats[r] != DFDB_AGG_COUNT && q->gr_kinds_n[(size_t)r] == 2) { if (ng > 0) memcpy(part.vals[(size_t)r].data(), vf.data() + r0, (size_t)ng * 8); }
+    else for (int64_t j = 0; j < ng; j++) part.vals[(size_t)r][(size_t)j] = (uint64_t)vi[r0 + (size_t)j];
+  }
 }
 
-void merged_fetch(const GroupMerged& m, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
-  if (keys) {
-    if (keys->memkind != DFDB_MEM_HOST) fail(DFDB_ERR_ARGUMENT, "merged keys are written to host buffers");
-    const bool is_str = dt_base(m.key_dtype) == DFDB_STRING;
-    keys->dtype = m.key_dtype; keys->count = m.ng; keys->nbytes = (int64_t)m.key_bytes.size();
-    if (m.ng > 0) {
-      if (!keys->data) fail(DFDB_ERR_ARGUMENT, "the key column has no data buffer");
-      memcpy(keys->data, m.key_data.data(), m.key_data.size());
-      if (keys->missing) memcpy(keys->missing, m.key_missing.data(), (size_t)m.ng);
-      if (is_str && !m.key_bytes.empty()) {
-        if ((int64_t)m.key_bytes.size() > keys->bytes_cap || !keys->bytes) fail(DFDB_ERR_ARGUMENT, "the key column needs %zu string bytes, capacity is %lld", m.key_bytes.size(), (long long)keys->bytes_cap);
-        memcpy(keys->bytes, m.key_bytes.data(), m.key_bytes.size());
-      }
+void merged_fetch(const GroupMerged& m, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f, bool single_key) {
+  const size_t ng = (size_t)m.ng;
+  if (keys) for (size_t i = 0; i < m.key_dtypes.size(); i++) {
+    dfdb_outcol* o = &keys[i];
+    const GroupKeys& km = m.keys[i];
+    if (o->memkind != DFDB_MEM_HOST) fail(DFDB_ERR_ARGUMENT, "merged keys are written to host buffers");
+    o->dtype = m.key_dtypes[i]; o->count = m.ng; o->nbytes = (int64_t)km.key_bytes.size();
+    if (ng == 0) continue;
+    if (!o->data) fail(DFDB_ERR_ARGUMENT, "the key column has no data buffer");
+    memcpy(o->data, km.key_data.data(), km.key_data.size());
+    if (o->missing) memcpy(o->missing, km.key_missing.data(), ng);
+    if (dt_base(m.key_dtypes[i]) == DFDB_STRING && !km.key_bytes.empty()) {
+      if ((int64_t)km.key_bytes.size() > o->bytes_cap || !o->bytes) fail(DFDB_ERR_ARGUMENT, "the key column needs %zu string bytes, capacity is %lld", km.key_bytes.size(), (long long)o->bytes_cap);
+      memcpy(o->bytes, km.key_bytes.data(), km.key_bytes.size());
     }
   }
-  for (int64_t j = 0; j < m.ng; j++) {
-    if (counts) counts[j] = m.counts[(size_t)j];
-    const uint64_t b = m.vals[(size_t)j];
-    double d; memcpy(&d, &b, 8);
-    if (m.kind == 2) { if (vals_f) vals_f[j] = d; if (vals_i) vals_i[j] = (int64_t)d; }
-    else { if (vals_i) vals_i[j] = (int64_t)b; if (vals_f) vals_f[j] = m.kind == 1 ? (double)b : (double)(int64_t)b; }
-  }
-}
-
-// one key column of a merged result -> a caller buffer (HOST)
-static void merged_keys_fetch(const GroupMerged& km, int64_t ng, dfdb_outcol* o) {
-  if (o->memkind != DFDB_MEM_HOST) fail(DFDB_ERR_ARGUMENT, "merged keys are written to host buffers");
-  o->dtype = km.key_dtype; o->count = ng; o->nbytes = (int64_t)km.key_bytes.size();
-  if (ng == 0) return;
-  if (!o->data) fail(DFDB_ERR_ARGUMENT, "the key column has no data buffer");
-  memcpy(o->data, km.key_data.data(), km.key_data.size());
-  if (o->missing) memcpy(o->missing, km.key_missing.data(), (size_t)ng);
-  if (dt_base(km.key_dtype) == DFDB_STRING && !km.key_bytes.empty()) {
-    if ((int64_t)km.key_bytes.size() > o->bytes_cap || !o->bytes) fail(DFDB_ERR_ARGUMENT, "the key column needs %zu string bytes, capacity is %lld", km.key_bytes.size(), (long long)o->bytes_cap);
-    memcpy(o->bytes, km.key_bytes.data(), km.key_bytes.size());
-  }
+  if (counts && ng > 0) memcpy(counts, m.counts.data(), ng * 8);
+  for (size_t r = 0; r < m.vals.size(); r++)
+    group_values_out(m.vals[r].data(), m.ng, m.ops[r] == DFDB_AGG_COUNT ? 0 : m.kinds[r], vals_i ? vals_i + r * ng : nullptr, vals_f ? vals_f + r * ng : nullptr);
+  if (single_key && m.vals.empty()) { if (vals_i) std::fill_n(vals_i, ng, 0); if (vals_f) std::fill_n(vals_f, ng, 0.0); }
 }
 
 // ------------------------------------------------------------------ which queries stream
@@ -368,7 +342,7 @@ int64_t ooc_string_bytes(dfdb_query* q, int32_t i) {
   if (dt_base(e.dtype) != DFDB_STRING) return 0;
   if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
   OocState& o = state(q);
-  if (o.narrowed && o.merged_col == e.col) return (int64_t)o.merged.key_bytes.size();
+  if (o.narrowed && o.merged_col == e.col) return (int64_t)o.merged.keys[0].key_bytes.size();
   if (!o.narrowed && o.str_bytes[(size_t)i] >= 0) return o.str_bytes[(size_t)i];
   // a sizing pass of its own: the selection with this one column as its projection
   TempQuery tq(q, !o.narrowed);
@@ -395,7 +369,7 @@ void ooc_materialize(dfdb_query* q, dfdb_outcol* outs, int32_t ncols) {
         if (outs[p].memkind != DFDB_MEM_HOST) { only_key = false; break; }
       }
     }
-    if (only_key) { for (int32_t p = 0; p < ncols; p++) merged_fetch(o.merged, &outs[p], nullptr, nullptr, nullptr); return; }
+    if (only_key) { for (int32_t p = 0; p < ncols; p++) merged_fetch(o.merged, &outs[p], nullptr, nullptr, nullptr, true); return; }
     TempQuery tq(q, false);
     narrowed_view(q, tq);
     for (const ProjCol& p : q->proj) tq.project(p);
@@ -452,29 +426,26 @@ void ooc_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double*
     if (op != DFDB_AGG_SUM) fail(DFDB_ERR_ARGUMENT, "ArgumentError: reducing over an empty collection is not allowed");
     acc = 0;                                             // (0 and 0.0 share a bit pattern)
   }
-  if (adt == DFDB_F64) { double d; memcpy(&d, &acc, 8); if (out_f) *out_f = d; if (out_i) *out_i = (int64_t)d; }
-  else { if (out_i) *out_i = (int64_t)acc; if (out_f) *out_f = adt == DFDB_U64 ? (double)acc : (double)(int64_t)acc; }
+  group_values_out(&acc, 1, adt == DFDB_F64 ? 2 : (adt == DFDB_U64 ? 1 : 0), out_i, out_f);
 }
 
 // ------------------------------------------------------------------ unique / groupreduce
-static void stream_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, bool with_rows) {
-  if (key_p < 0 || (size_t)key_p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", key_p);
-  const Node& ke = *q->proj[(size_t)key_p].expr;
-  if (ke.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "unique / groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
-  int kind = 0;
-  if (op != DFDB_AGG_COUNT) {
-    if (val_p < 0 || (size_t)val_p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", val_p);
-    const Node& ve = *q->proj[(size_t)val_p].expr;
-    if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
-    const int b = dt_base(ve.dtype); kind = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
-  }
+// the resident dfdb_query_groupreduce_n per chunk, the chunks merged by key tuple in chunk order (= first appearance) -> state(q).merged.
+// by_prefix: groupreduce_check's — the streamed dfdb_query_unique and dfdb_query_groupreduce name both in the refusal of a computed key column
+static void stream_groupreduce(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, bool with_rows,
+                               const char* by_prefix) {
+  GroupMerged m;
+  m.kinds = groupreduce_check(q, key_cols, nkeys, val_cols, stats, nvals, by_prefix);
+  m.ops.assign(stats, stats + nvals);
+  for (int k = 0; k < nkeys; k++) m.key_dtypes.push_back(q->proj[(size_t)key_cols[k]].expr->dtype);
+  m.keys.resize((size_t)nkeys); m.vals.resize((size_t)nvals);
   OocState& o = state(q);
   if (o.narrowed) fail(DFDB_ERR_ARGUMENT, "ArgumentError: the query's selection is narrowed by dfdb_query_unique: dfdb_query_reset it first");
+  // the chunk query projects the keys, then the reducers' columns (a count reads none)
   TempQuery tq(q, true);
-  tq.project(q->proj[(size_t)key_p]);
-  if (op != DFDB_AGG_COUNT) tq.project(q->proj[(size_t)val_p]);
-  GroupMerged m; m.key_dtype = ke.dtype; m.kind = kind; m.op = op; m.with_stats = !with_rows;
+  std::vector<int32_t> kidx((size_t)nkeys), vidx((size_t)nvals, -1);
+  for (int k = 0; k < nkeys; k++) { kidx[(size_t)k] = (int32_t)tq.q.proj.size(); tq.project(q->proj[(size_t)key_cols[k]]); }
+  for (int r = 0; r < nvals; r++) if (stats[r] != DFDB_AGG_COUNT) { vidx[(size_t)r] = (int32_t)tq.q.proj.size(); tq.project(q->proj[(size_t)val_cols[r]]); }
   GroupMerger mg;
   int64_t rows = 0;
   {
@@ -483,137 +454,47 @@ static void stream_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int3
       const int64_t n = query_count(c, -1);
       if (n == 0) continue;
       rows += n;
-      int64_t ng = 0, kb = 0;
-      query_groupreduce(c, 0, op == DFDB_AGG_COUNT ? -1 : 1, op, &ng, &kb);
       GroupPart part;
-      fetch_group_part(c, 0, ng, kb, with_rows, part);
+      fetch_group_part(c, kidx.data(), nkeys, vidx.data(), stats, nvals, with_rows, part);
       mg.add(m, part);
     }
   }
   m.valid = true;
   o.count = rows;
   o.merged = std::move(m);
-  o.merged_col = ke.col;
+  o.merged_col = q->proj[(size_t)key_cols[0]].expr->col;
+  o.pending = OocState::NONE;
 }
 
 void ooc_unique(dfdb_query* q, int32_t p) {
-  stream_groupreduce(q, p, -1, DFDB_AGG_COUNT, true);
-  OocState& o = state(q);
-  o.narrowed = true; o.gr_pending = false;
+  stream_groupreduce(q, &p, 1, nullptr, nullptr, 0, true, "unique / ");
+  state(q).narrowed = true;
 }
 
 void ooc_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes) {
-  stream_groupreduce(q, key_p, val_p, op, false);
+  stream_groupreduce(q, &key_p, 1, &val_p, &op, op == DFDB_AGG_COUNT ? 0 : 1, false, "unique / ");   // (a count has no value array)
   OocState& o = state(q);
-  o.gr_pending = true;
+  o.pending = OocState::GROUPREDUCE;
   if (ngroups) *ngroups = o.merged.ng;
-  if (key_bytes) *key_bytes = (int64_t)o.merged.key_bytes.size();
+  if (key_bytes) *key_bytes = (int64_t)o.merged.keys[0].key_bytes.size();
 }
 
-void ooc_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
-  OocState& o = state(q);
-  if (!o.gr_pending || !o.merged.valid) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce has not been called (or the query was executed, reset or changed since)");
-  merged_fetch(o.merged, keys, counts, vals_i, vals_f);
-  o.merged = GroupMerged{}; o.gr_pending = false; o.merged_col = -1;
-}
-
-// groupreduce by a tuple of keys: the resident dfdb_query_groupreduce_n per chunk, the chunks merged by tuple in chunk order (= first appearance)
 void ooc_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals, int64_t* ngroups,
                        int64_t* key_bytes) {
-  if (nkeys < 1 || nkeys > 8 || !key_cols) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 1 to 8 key columns, not %d", nkeys);
-  if (nvals < 0 || nvals > kMaxReducers || (nvals > 0 && (!val_cols || !stats))) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 0 to %d reducers, not %d", kMaxReducers, nvals);
-  GroupMergedN m;
-  for (int k = 0; k < nkeys; k++) {
-    const int32_t p = key_cols[k];
-    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
-    const Node& ke = *q->proj[(size_t)p].expr;
-    if (ke.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-    m.keys.emplace_back(); m.keys.back().key_dtype = ke.dtype;
-  }
-  for (int r = 0; r < nvals; r++) {
-    const int32_t op = stats[r];
-    if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
-    int kind = 0;
-    if (op != DFDB_AGG_COUNT) {
-      const int32_t p = val_cols[r];
-      if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
-      const Node& ve = *q->proj[(size_t)p].expr;
-      if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
-      const int b = dt_base(ve.dtype); kind = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
-    }
-    m.kinds.push_back(kind); m.ops.push_back(op);
-  }
-  m.vals.resize((size_t)nvals);
+  stream_groupreduce(q, key_cols, nkeys, val_cols, stats, nvals, false, "");
   OocState& o = state(q);
-  if (o.narrowed) fail(DFDB_ERR_ARGUMENT, "ArgumentError: the query's selection is narrowed by dfdb_query_unique: dfdb_query_reset it first");
-  // the chunk query projects the keys, then the reducers' columns (a count reads none)
-  TempQuery tq(q, true);
-  std::vector<int32_t> kidx((size_t)nkeys), vidx((size_t)nvals, -1);
-  for (int k = 0; k < nkeys; k++) { kidx[(size_t)k] = (int32_t)tq.q.proj.size(); tq.project(q->proj[(size_t)key_cols[k]]); }
-  for (int r = 0; r < nvals; r++) if (stats[r] != DFDB_AGG_COUNT) { vidx[(size_t)r] = (int32_t)tq.q.proj.size(); tq.project(q->proj[(size_t)val_cols[r]]); }
-  GroupMergerN mg;
-  int64_t rows = 0;
-  {
-    StreamPass pass(q, &tq.q);
-    while (dfdb_query* c = pass.next()) {
-      const int64_t n = query_count(c, -1);
-      if (n == 0) continue;
-      rows += n;
-      int64_t ng = 0;
-      std::vector<int64_t> kb((size_t)nkeys, 0);
-      query_groupreduce_n(c, kidx.data(), nkeys, vidx.data(), stats, nvals, &ng, kb.data());
-      GroupPartN part;
-      part.ng = ng; part.keys.resize((size_t)nkeys);
-      std::vector<dfdb_outcol> outs((size_t)nkeys);
-      for (int k = 0; k < nkeys; k++) {
-        const int32_t kdt = m.keys[(size_t)k].key_dtype;
-        const bool is_str = dt_base(kdt) == DFDB_STRING;
-        GroupPart& kp = part.keys[(size_t)k];
-        kp.ng = ng;
-        kp.key_data.resize((size_t)ng * (size_t)(is_str ? 4 : dt_width(kdt)));
-        if (dt_nullable(kdt) && !is_str) kp.key_missing.assign((size_t)ng, 0);
-        kp.key_bytes.resize((size_t)kb[(size_t)k]);
-        dfdb_outcol& oc = outs[(size_t)k];
-        oc = dfdb_outcol{}; oc.memkind = DFDB_MEM_HOST; oc.data = kp.key_data.data(); oc.bytes = kp.key_bytes.data(); oc.bytes_cap = kb[(size_t)k];
-        oc.missing = kp.key_missing.empty() ? nullptr : kp.key_missing.data();
-      }
-      part.counts.assign((size_t)ng, 0);
-      std::vector<int64_t> vi((size_t)ng * (size_t)nvals); std::vector<double> vf((size_t)ng * (size_t)nvals);
-      query_groupreduce_n_fetch(c, outs.data(), part.counts.data(), vi.data(), vf.data());   // (puts the chunk's full selection back)
-      part.vals.assign((size_t)nvals, std::vector<uint64_t>((size_t)ng));
-      for (int r = 0; r < nvals; r++)
-        for (int64_t j = 0; j < ng; j++) {
-          const size_t i = (size_t)r * (size_t)ng + (size_t)j;
-          if (stats[r] != DFDB_AGG_COUNT && m.kinds[(size_t)r] == 2) memcpy(&part.vals[(size_t)r][(size_t)j], &vf[i], 8); else part.vals[(size_t)r][(size_t)j] = (uint64_t)vi[i];
-        }
-      mg.add(m, part);
-    }
-  }
-  m.valid = true;
-  o.count = rows;
-  o.merged_n = std::move(m);
-  o.grn_pending = true;
-  if (ngroups) *ngroups = o.merged_n.ng;
-  if (key_bytes) for (int k = 0; k < nkeys; k++) key_bytes[k] = (int64_t)o.merged_n.keys[(size_t)k].key_bytes.size();
+  o.pending = OocState::GROUPREDUCE_N;
+  if (ngroups) *ngroups = o.merged.ng;
+  if (key_bytes) for (int k = 0; k < nkeys; k++) key_bytes[k] = (int64_t)o.merged.keys[(size_t)k].key_bytes.size();
 }
 
-void ooc_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
+void ooc_groupreduce_fetch(dfdb_query* q, OocState::Pending which, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
   OocState& o = state(q);
-  if (!o.grn_pending || !o.merged_n.valid) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce_n has not been called (or the query was executed, reset or changed since)");
-  const GroupMergedN& m = o.merged_n;
-  const int64_t ng = m.ng;
-  if (keys) for (size_t k = 0; k < m.keys.size(); k++) merged_keys_fetch(m.keys[k], ng, &keys[k]);
-  for (int64_t j = 0; j < ng; j++) if (counts) counts[j] = m.counts[(size_t)j];
-  for (size_t r = 0; r < m.ops.size(); r++)
-    for (int64_t j = 0; j < ng; j++) {
-      const size_t i = r * (size_t)ng + (size_t)j;
-      const uint64_t b = m.vals[r][(size_t)j];
-      const int kind = m.ops[r] == DFDB_AGG_COUNT ? 0 : m.kinds[r];
-      double d; memcpy(&d, &b, 8);
-      if (kind == 2) { if (vals_f) vals_f[i] = d; if (vals_i) vals_i[i] = (int64_t)d; }
-      else { if (vals_i) vals_i[i] = (int64_t)b; if (vals_f) vals_f[i] = kind == 1 ? (double)b : (double)(int64_t)b; }
-    }
-  o.merged_n = GroupMergedN{}; o.grn_pending = false;
+  const bool single = which == OocState::GROUPREDUCE;
+  if (o.pending != which || !o.merged.valid)
+    fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce%s has not been called (or the query was executed, reset or changed since)", single ? "" : "_n");
+  merged_fetch(o.merged, keys, counts, vals_i, vals_f, single);
+  o.merged = GroupMerged{}; o.pending = OocState::NONE; o.merged_col = -1;
 }
 
 // ------------------------------------------------------------------ what a multi-GPU group asks of a shard that is not resident (group.cpp)
@@ -654,13 +535,10 @@ int ooc_aggregate_bits(dfdb_query* q, int32_t op, int32_t i, uint64_t out[2]) {
 }
 // the shard's groups as ONE part (its chunks merged in chunk order), for the merge across the ranks
 int ooc_group_part(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, GroupPart& part) {
-  stream_groupreduce(q, key_p, val_p, op, false);
+  stream_groupreduce(q, &key_p, 1, &val_p, &op, op == DFDB_AGG_COUNT ? 0 : 1, false, "unique / ");
   OocState& o = state(q);
-  GroupMerged& m = o.merged;
-  part.ng = m.ng; part.key_data = std::move(m.key_data); part.key_bytes = std::move(m.key_bytes); part.counts = std::move(m.counts); part.vals = std::move(m.vals);
-  const int32_t kdt = m.key_dtype;
-  if (dt_nullable(kdt) && dt_base(kdt) != DFDB_STRING) part.key_missing = std::move(m.key_missing);
-  const int kind = m.kind;
+  const int kind = o.merged.kinds.empty() ? 0 : o.merged.kinds[0];
+  part = std::move(static_cast<GroupPart&>(o.merged));
   o.merged = GroupMerged{}; o.merged_col = -1;
   return kind;
 }

@@ -497,9 +497,10 @@ static bool group_radix(dfdb_query* q, const void* keys, int dt, const uint64_t*
   uint64_t* aux = (uint64_t*)run.extra();                                // [0] the unstorable key's first row, [1] the missing key's, [3] abort; [4..7] gspec; [8] nres
   RadixGroup g{};
   g.valcol = vc ? vc->data.p : nullptr; g.valdt = vc ? dt_base(vc->dtype) : 0;
-  g.gop = op == DFDB_AGG_SUM ? (q->gr_kind == 2 ? 2 : 1) : (op == DFDB_AGG_MIN ? 3 : (op == DFDB_AGG_MAX ? 4 : 0));
+  const int kind = q->gr_kinds_n[0];
+  g.gop = op == DFDB_AGG_SUM ? (kind == 2 ? 2 : 1) : (op == DFDB_AGG_MIN ? 3 : (op == DFDB_AGG_MAX ? 4 : 0));
   if (!vc) g.gop = 0;
-  g.vkind = q->gr_kind; g.results = res.buf.p; g.gspec = aux + 4; g.nres = (uint32_t*)(aux + 8);
+  g.vkind = kind; g.results = res.buf.p; g.gspec = aux + 4; g.nres = (uint32_t*)(aux + 8);
   HIP_CHECK(hipMemsetAsync(aux, 0xFF, 16, s));                           // aux[0], aux[1] = none
   if (g.gop == 3) { HIP_CHECK(hipMemsetAsync(aux + 5, 0xFF, 8, s)); HIP_CHECK(hipMemsetAsync(aux + 7, 0xFF, 8, s)); }      // gspec[1], [3]: a minimum starts at all ones
   // a key that a large part of the rows hold is reduced by the partition pass itself (k_radix.hip, hot keys: the form this replaces sent every one of its rows
@@ -636,26 +637,48 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
   return ng;
 }
 
+std::vector<int> groupreduce_check(const dfdb_query* q, const int32_t* key_cols, int32_t nkeys, const int32_t* val_cols, const int32_t* stats, int32_t nvals,
+                                   const char* by_prefix) {
+  if (nkeys < 1 || nkeys > 8 || !key_cols) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 1 to 8 key columns, not %d", nkeys);
+  if (nvals < 0 || nvals > kMaxReducers || (nvals > 0 && (!val_cols || !stats))) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 0 to %d reducers, not %d", kMaxReducers, nvals);
+  for (int k = 0; k < nkeys; k++) {
+    const int32_t p = key_cols[k];
+    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+    if (q->proj[(size_t)p].expr->op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "%sgroupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)", by_prefix);
+  }
+  std::vector<int> kinds((size_t)nvals, 0);
+  for (int m = 0; m < nvals; m++) {
+    const int32_t op = stats[m];
+    if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
+    if (op == DFDB_AGG_COUNT) continue;                      // (a count reads no column)
+    const int32_t p = val_cols[m];
+    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
+    const Node& ve = *q->proj[(size_t)p].expr;
+    if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
+    const int b = dt_base(ve.dtype);
+    kinds[(size_t)m] = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
+  }
+  return kinds;
+}
+void group_values_out(const uint64_t* bits, int64_t n, int kind, int64_t* vals_i, double* vals_f) {
+  for (int64_t j = 0; j < n; j++) {
+    const uint64_t b = bits[j];
+    double d; memcpy(&d, &b, 8);
+    if (kind == 2) { if (vals_f) vals_f[j] = d; if (vals_i) vals_i[j] = (int64_t)d; }
+    else { if (vals_i) vals_i[j] = (int64_t)b; if (vals_f) vals_f[j] = kind == 1 ? (double)b : (double)(int64_t)b; }
+  }
+}
+
 // groupreduce(view, (:key,); out = :val => Stat()) (src/tables/aggregate.jl:1-36; unfinished in the reference: it numbers the groups in order of
 // first appearance of the key and prints the map).  Completed to that intent: one group per distinct key (isequal), groups in order of first
 // appearance, count and one reduced value per group.  Device side: unique's table + k_group_ids + k_group_accumulate (k_unique.hip).
 void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes) {
   ensure_executed_checked(q);
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  if (key_p < 0 || (size_t)key_p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", key_p);
-  const Node& ke = *q->proj[(size_t)key_p].expr;
-  if (ke.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
-  const Column* vc = nullptr;
-  if (op != DFDB_AGG_COUNT) {
-    if (val_p < 0 || (size_t)val_p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", val_p);
-    const Node& ve = *q->proj[(size_t)val_p].expr;
-    if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
-    vc = &need_resident(t, ve.col);
-  }
-  const Column& kc = need_resident(t, ke.col);
-  q->gr_n = 0; q->gr_key = key_p; q->gr_op = op; q->gr_kind = 0; q->gr_multi = 0;
-  if (vc) { const int b = dt_base(vc->dtype); q->gr_kind = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1); }
+  const std::vector<int> kinds = groupreduce_check(q, &key_p, 1, &val_p, &op, 1);
+  const Column* vc = op != DFDB_AGG_COUNT ? &need_resident(t, q->proj[(size_t)val_p].expr->col) : nullptr;
+  const Column& kc = need_resident(t, q->proj[(size_t)key_p].expr->col);
+  q->gr_n = 0; q->gr_multi = 0; q->gr_keys_n.assign(1, key_p); q->gr_ops_n.assign(1, op); q->gr_kinds_n = kinds;
   if (ngroups) *ngroups = 0;
   if (key_bytes) *key_bytes = 0;
   const int64_t nsel = query_count(q, -1);
@@ -678,7 +701,7 @@ void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, 
                                     t->nrows, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init);
     }
   } else ng = groupreduce_hashed(q, key_p, kc, vc, op, nsel, init, T);
-  launch_group_finish(s, q->gr_val.as<uint64_t>(), ng, q->gr_kind, op);
+  launch_group_finish(s, q->gr_val.as<uint64_t>(), ng, kinds[0], op);
   stream_wait(ctx);                                        // the tables die here
   { RecycleScope rs; T = UniqueTables(); }
   q->gr_n = ng; q->gr_state = 2;
@@ -694,18 +717,13 @@ void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, 
   if (q->bitmap_rows != t->nrows) { q->gr_state = 0; fail(DFDB_ERR_ARGUMENT, "ArgumentError: the table changed between dfdb_query_groupreduce and its fetch"); }
   const int64_t ng = q->gr_n;
   if (ng > 0) {
-    if (keys) { keys->memkind = keys->memkind == DFDB_MEM_DEVICE ? DFDB_MEM_DEVICE : DFDB_MEM_HOST; materialize_col(q, q->gr_key, *keys, ng); }
+    if (keys) { keys->memkind = keys->memkind == DFDB_MEM_DEVICE ? DFDB_MEM_DEVICE : DFDB_MEM_HOST; materialize_col(q, q->gr_keys_n[0], *keys, ng); }
     std::vector<uint64_t> c((size_t)ng), v((size_t)ng);
     HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
     stream_wait(ctx);
-    for (int64_t g = 0; g < ng; g++) {
-      if (counts) counts[g] = (int64_t)c[(size_t)g];
-      const uint64_t b = v[(size_t)g];
-      double d; memcpy(&d, &b, 8);
-      if (q->gr_kind == 2) { if (vals_f) vals_f[g] = d; if (vals_i) vals_i[g] = (int64_t)d; }
-      else { if (vals_i) vals_i[g] = (int64_t)b; if (vals_f) vals_f[g] = q->gr_kind == 1 ? (double)b : (double)(int64_t)b; }
-    }
+    if (counts) memcpy(counts, c.data(), (size_t)ng * 8);
+    group_values_out(v.data(), ng, q->gr_kinds_n.empty() ? 0 : q->gr_kinds_n[0], vals_i, vals_f);   // (no kind: an _n call without a reducer that was handed over)
   } else if (keys) { keys->count = 0; keys->nbytes = 0; }
   if (q->gr_state == 2) restore_group_selection(q);      // back to the full selection: bitmap + tile counts + prefix
   q->gr_state = 0;
@@ -778,26 +796,7 @@ void query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, 
                          int64_t* key_bytes) {
   ensure_executed_checked(q);
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  if (nkeys < 1 || nkeys > 8 || !key_cols) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 1 to 8 key columns, not %d", nkeys);
-  if (nvals < 0 || nvals > kMaxReducers || (nvals > 0 && (!val_cols || !stats))) fail(DFDB_ERR_ARGUMENT, "ArgumentError: groupreduce takes 0 to %d reducers, not %d", kMaxReducers, nvals);
-  std::vector<const Column*> kcs((size_t)nkeys), vcs((size_t)nvals, nullptr);
-  for (int k = 0; k < nkeys; k++) {
-    const int32_t p = key_cols[k];
-    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
-    if (q->proj[(size_t)p].expr->op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "groupreduce by a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  }
-  std::vector<int> kinds((size_t)nvals, 0);
-  for (int m = 0; m < nvals; m++) {
-    const int32_t op = stats[m];
-    if (op != DFDB_AGG_COUNT && op != DFDB_AGG_SUM && op != DFDB_AGG_MIN && op != DFDB_AGG_MAX) fail(DFDB_ERR_ARGUMENT, "unknown statistic %d", op);
-    if (op == DFDB_AGG_COUNT) continue;
-    const int32_t p = val_cols[m];
-    if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
-    const Node& ve = *q->proj[(size_t)p].expr;
-    if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
-    const int b = dt_base(ve.dtype);
-    kinds[(size_t)m] = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
-  }
+  const std::vector<int> kinds = groupreduce_check(q, key_cols, nkeys, val_cols, stats, nvals);
   // the shape that dfdb_query_groupreduce answers: handed to it (the same answers, bit for bit, at the same speed)
   if (nkeys == 1 && nvals <= 1) {
     query_groupreduce(q, key_cols[0], nvals ? val_cols[0] : -1, nvals ? stats[0] : DFDB_AGG_COUNT, ngroups, key_bytes);
@@ -805,6 +804,7 @@ void query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, 
     q->gr_keys_n.assign(key_cols, key_cols + 1); q->gr_ops_n.assign(stats, stats + nvals); q->gr_kinds_n = kinds;
     return;
   }
+  std::vector<const Column*> kcs((size_t)nkeys), vcs((size_t)nvals, nullptr);
   for (int k = 0; k < nkeys; k++) kcs[(size_t)k] = &need_resident(t, q->proj[(size_t)key_cols[k]].expr->col);
   for (int m = 0; m < nvals; m++) if (stats[m] != DFDB_AGG_COUNT) vcs[(size_t)m] = &need_resident(t, q->proj[(size_t)val_cols[m]].expr->col);
   q->gr_state = 0; q->gr_n = 0; q->gr_multi = 2;
@@ -862,10 +862,8 @@ void query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts
     std::vector<int64_t> c((size_t)std::max<int64_t>(ng, 1));
     const bool cnt_red = nvals == 1 && q->gr_ops_n[0] == DFDB_AGG_COUNT;
     query_groupreduce_fetch(q, keys, c.data(), nvals && !cnt_red ? vals_i : nullptr, nvals && !cnt_red ? vals_f : nullptr);
-    for (int64_t g = 0; g < ng; g++) {
-      if (counts) counts[g] = c[(size_t)g];
-      if (cnt_red) { if (vals_i) vals_i[g] = c[(size_t)g]; if (vals_f) vals_f[g] = (double)c[(size_t)g]; }
-    }
+    if (counts && ng > 0) memcpy(counts, c.data(), (size_t)ng * 8);
+    if (cnt_red) group_values_out((const uint64_t*)c.data(), ng, 0, vals_i, vals_f);
     q->gr_multi = 0;
     return;
   }
@@ -878,17 +876,11 @@ void query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts
     HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
     if (nvals) HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, v.size() * 8, hipMemcpyDeviceToHost, s));
     stream_wait(ctx);
-    if (counts) for (int64_t g = 0; g < ng; g++) counts[g] = (int64_t)c[(size_t)g];
+    if (counts) memcpy(counts, c.data(), (size_t)ng * 8);
     for (int m = 0; m < nvals; m++) {
-      const int kind = q->gr_kinds_n[(size_t)m];
       const bool cnt_red = q->gr_ops_n[(size_t)m] == DFDB_AGG_COUNT;
-      for (int64_t g = 0; g < ng; g++) {
-        const size_t i = (size_t)m * (size_t)ng + (size_t)g;
-        const uint64_t b = cnt_red ? c[(size_t)g] : v[i];
-        double d; memcpy(&d, &b, 8);
-        if (!cnt_red && kind == 2) { if (vals_f) vals_f[i] = d; if (vals_i) vals_i[i] = (int64_t)d; }
-        else { if (vals_i) vals_i[i] = (int64_t)b; if (vals_f) vals_f[i] = !cnt_red && kind == 1 ? (double)b : (double)(int64_t)b; }
-      }
+      const size_t m0 = (size_t)m * (size_t)ng;
+      group_values_out(cnt_red ? c.data() : v.data() + m0, ng, cnt_red ? 0 : q->gr_kinds_n[(size_t)m], vals_i ? vals_i + m0 : nullptr, vals_f ? vals_f + m0 : nullptr);
     }
   } else if (keys) for (int k = 0; k < nkeys; k++) { keys[k].count = 0; keys[k].nbytes = 0; }
   if (q->gr_state == 2) restore_group_selection(q);      // back to the full selection: bitmap + tile counts + prefix

@@ -345,6 +345,33 @@ def test_selection_restored_and_errors(dfdb_mod, ctx):
             dfdb_mod.groupreduce(v, "k1", "x", "sum", s=("x", "sum"))
         with pytest.raises(ValueError):
             dfdb_mod.groupreduce(v, ("k1", "k2"), s=("x", "median"))
+        # out of core each fetch takes only its own call's groups, also where the _n call has one key and one reducer; a refused fetch leaves them pending
+        d = tempfile.mkdtemp(prefix="dfdb_grn_")
+        try:
+            t.save(os.path.join(d, "tb"))
+            lazy = dfdb_mod.open_table(os.path.join(d, "tb"), load=False, ctx=ctx)
+            try:
+                ql = api._Query(lazy[("a", lambda c: c < 0.3), ["k1", "k2", "x", "xn"]])
+                want = len(np.unique(k1[a < 0.3]))
+                out1 = (N.OutCol * 1)()
+                out1[0].data = bufs[0].ctypes.data; out1[0].memkind = N.MEM_HOST
+                plain = lambda: L.dfdb_query_groupreduce_fetch(ql._h, out1, cnt.ctypes.data, vi.ctypes.data, vf.ctypes.data)   # noqa: E731
+                multi = lambda: L.dfdb_query_groupreduce_n_fetch(ql._h, out1, cnt.ctypes.data, vi.ctypes.data, vf.ctypes.data)  # noqa: E731
+                rc, ng1 = raw_call(dfdb_mod, ql, [0], [2], [N.AGG_SUM])
+                assert rc == N.OK and ng1 == want and not lazy.resident(0)
+                assert plain() == N.ERR_ARGUMENT
+                assert multi() == N.OK and cnt[:ng1].sum() == before_n
+                assert multi() == N.ERR_ARGUMENT                                           # the fetch cleared them
+                ng2, kb2 = C.c_int64(), C.c_int64()
+                assert L.dfdb_query_groupreduce(ql._h, 0, 2, N.AGG_SUM, C.byref(ng2), C.byref(kb2)) == N.OK and ng2.value == want
+                assert multi() == N.ERR_ARGUMENT
+                assert plain() == N.OK and cnt[:ng1].sum() == before_n
+                assert plain() == N.ERR_ARGUMENT
+                assert not lazy.resident(0)
+            finally:
+                lazy.close()
+        finally:
+            shutil.rmtree(d, ignore_errors=True)
     finally:
         t.close()
 
