@@ -133,8 +133,9 @@ struct dfdb_query {
   // the final mask, the scan adds up the selected values while it holds them (one partial per 1024-row tile) and dfdb_aggregate only
   // reduces the partials
   int hint_agg_op = 0, hint_agg_proj = -1;
-  // the smallest rows on which a predicate of the current execution hit DivideError [0] / InexactError [1] (~0: none); decided at the end of query_execute
-  uint64_t err_row[2] = {~0ull, ~0ull};
+  // the smallest rows on which a predicate of the current execution hit DivideError [0] / InexactError [1] / a parse(T, s) without a value [2] (~0: none);
+  // decided at the end of query_execute.  [2] is the device's word `row << 3 | reason` (dfdb::err_word_row, dfdb::throw_parse_error)
+  uint64_t err_row[3] = {~0ull, ~0ull, ~0ull};
   bool err_checking = false;   // inside error_is_reached's partial executions: errors are not raised
   uint64_t* proj_err = nullptr; // query_materialize: the first erroring row per kind of the projection column being computed lands here instead of raising
   int agg_col = -1;            // table ordinal whose per-tile sums agg_partials holds (-1: none)
@@ -163,6 +164,17 @@ struct dfdb_query {
 };
 
 namespace dfdb {
+// the three error words of an interpreter launch (k_interp_device.inc flag_error / flag_parse_error): the table row of word `kind`
+inline uint64_t err_word_row(int kind, uint64_t w) { return (kind == 2 && w != ~0ull) ? w >> 3 : w; }
+// which of the three words holds the smallest row (-1: none).  On the same row the parse word wins: the parsed leaf is evaluated before anything computed from
+// it, and a row without a value continues as 0 (`x ÷ parse(T, s)` adds a DivideError of its own there, which Julia never reaches)
+inline int first_error_kind(const uint64_t w[3]) {
+  int best = -1;
+  for (int k : {2, 0, 1}) if (w[k] != ~0ull && (best < 0 || err_word_row(k, w[k]) < err_word_row(best, w[best]))) best = k;
+  return best;
+}
+// raises what the parse word says about its row: ArgumentError / OverflowError / MethodError (DFDB_ERR_ARGUMENT) or DFDB_ERR_UNSUPPORTED, with the global row
+[[noreturn]] void throw_parse_error(uint64_t word, int64_t row_base);
 // engine entry points used by c_api.cpp
 void table_open(dfdb_ctx* ctx, const char* path, dfdb_table** out);
 void table_add_column(dfdb_table* t, const char* name, int32_t dtype, int64_t nrows, const void* data, const uint8_t* bytes,

@@ -13,6 +13,21 @@ void fail(int code, const char* fmt, ...) {
   throw Error(code, buf);
 }
 
+// a parse(T, s) row that gave no value (k_interp_device.inc PR_*): the three outcomes of include/dfdb_ir.h's DFIR_CAST contract that are not a value
+void throw_parse_error(uint64_t word, int64_t row_base) {
+  const uint64_t row = (uint64_t)row_base + (word >> 3);
+  char buf[256];
+  switch ((int)(word & 7)) {
+    case 1 /* PR_ARGUMENT */: snprintf(buf, sizeof buf, "ArgumentError: parse: the string is not a valid number of the target type (row %llu)", (unsigned long long)row); break;
+    case 2 /* PR_OVERFLOW */: snprintf(buf, sizeof buf, "OverflowError: parse: the value does not fit the target type (row %llu)", (unsigned long long)row); break;
+    case 3 /* PR_METHOD */: snprintf(buf, sizeof buf, "MethodError: no method matching parse(::Type{T}, ::Missing) (row %llu)", (unsigned long long)row); break;
+    default /* PR_UNSUPPORTED */:
+      snprintf(buf, sizeof buf, "parse: the string is outside what the device parser decides, the caller falls back to the Julia path (row %llu)", (unsigned long long)row);
+      throw Error(DFDB_ERR_UNSUPPORTED, buf, row);
+  }
+  throw Error(DFDB_ERR_ARGUMENT, buf, row);
+}
+
 static const char* kNames[] = {nullptr, "Int8", "Int16", "Int32", "Int64", "UInt8", "UInt16", "UInt32", "UInt64",
                                "Float32", "Float64", "Bool", "String"};
 static const int kWidth[] = {0, 1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 1, 0};
@@ -169,7 +184,13 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
         if (op == DFIR_CAST) { need(1); n->cast_to = ir[pos++]; }
         n->a = pop();
         if (n->a->op == DFIR_CONST_SET) fail(DFDB_ERR_ARGUMENT, "a set is only valid as the second argument of in");
-        if (op == DFIR_CAST) {
+        if (op == DFIR_CAST && dt_base(n->a->dtype) == DFDB_STRING) {
+          // parse(T, s) over a String column (include/dfdb_ir.h): an integer type or Float64, never Union{T,Missing} — parse(T, ::Missing) is a MethodError
+          const int ct = n->cast_to;
+          if (n->a->op != DFIR_COL || !(dt_isint(ct) || ct == DFDB_F64) || dt_nullable(ct))
+            fail(DFDB_ERR_UNSUPPORTED, "unsupported conversion %s -> %s", dt_name(n->a->dtype).c_str(), dt_name(n->cast_to).c_str());
+          n->dtype = ct;
+        } else if (op == DFIR_CAST) {
           if (!dt_isnum(n->a->dtype) || !dt_isnum(n->cast_to) || dt_nullable(n->cast_to))
             fail(DFDB_ERR_UNSUPPORTED, "unsupported conversion %s -> %s", dt_name(n->a->dtype).c_str(), dt_name(n->cast_to).c_str());
           n->dtype = n->cast_to | (dt_nullable(n->a->dtype) ? DFDB_NULLABLE : 0);

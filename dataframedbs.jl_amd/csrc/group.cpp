@@ -205,8 +205,16 @@ static void for_shards(dfdb_group* g, const std::function<void(int)>& fn) {
 // every collective entry point starts with a clean slate: a note left behind by an operation that died on its way to the exchange (a failed RCCL
 // call, a caller's collective that returned an error) must not be taken for this operation's
 static void fresh(dfdb_group* g) { g->fault_key = ~0ull; g->fault_code = 0; g->fault_msg.clear(); }
+// (bits 4-7 of the code byte: which of parse's outcomes the row raised, k_interp_device.inc PR_*, 0 for everything else — the ranks that do not own the
+// failing shard rebuild the message from it)
+static uint64_t parse_reason_of(const Error& e) {
+  if (e.row == ~0ull) return 0;
+  const std::string m = e.what();
+  if (e.code == DFDB_ERR_ARGUMENT) return m.rfind("ArgumentError: parse", 0) == 0 ? 1 : (m.rfind("OverflowError: parse", 0) == 0 ? 2 : (m.rfind("MethodError: no method matching parse", 0) == 0 ? 3 : 0));
+  return e.code == DFDB_ERR_UNSUPPORTED && m.rfind("parse:", 0) == 0 ? 4 : 0;
+}
 static uint64_t fault_key_of(const Error& e) {
-  const uint64_t code = (uint64_t)(e.code > 0 && e.code < 256 ? e.code : DFDB_ERR_DEVICE);
+  const uint64_t code = (uint64_t)(e.code > 0 && e.code < 16 ? e.code : DFDB_ERR_DEVICE) | parse_reason_of(e) << 4;
   return e.row != ~0ull ? (((e.row + 1) << 8) | code) : code;
 }
 static void note_fault(dfdb_group* g, const Error& e) {
@@ -242,9 +250,10 @@ static void settle_fault(dfdb_group* g, uint64_t agreed) {
     if (mine != ~0ull) throw Error(code, msg);            // (no exchange carried it: a group of one process)
     return;
   }
-  const int acode = (int)(agreed & 0xffu);
+  const int acode = (int)(agreed & 0xfu), areason = (int)((agreed >> 4) & 0xfu);
   const uint64_t arow = (agreed >> 8) ? (agreed >> 8) - 1 : ~0ull;
   if (agreed == mine) throw Error(code, msg, arow);
+  if (arow != ~0ull && areason) throw_parse_error(arow << 3 | (uint64_t)areason, 0);
   if (arow != ~0ull && acode == DFDB_ERR_DIVIDE) throw Error(acode, "DivideError: integer division error", arow);
   if (arow != ~0ull && acode == DFDB_ERR_ARGUMENT) throw Error(acode, "InexactError: conversion is not exact", arow);
   throw Error(acode, "another shard of the group failed with status " + std::to_string(acode) + " (its own rank holds the message)");

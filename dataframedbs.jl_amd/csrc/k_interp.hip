@@ -187,6 +187,13 @@ struct Compiler {
     const int rt = dt_base(n.dtype);
     const bool a_str = n.a && dt_base(n.a->dtype) == DFDB_STRING, b_str = n.b && dt_base(n.b->dtype) == DFDB_STRING;
     if (a_str || b_str) {   // string forms: column vs constant only
+      if (n.op == DFIR_CAST) {                           // parse(T, s): expr.cpp has checked that n.a is a column and T an integer type or Float64
+        const int slot = slot_for(n.a->col);
+        const int so = offsets_for(slot);
+        IInstr& in = fresh(H_PARSE);
+        in.slot = slot; in.so = (uint8_t)so; in.rt = (uint8_t)dt_base(n.cast_to);
+        return;
+      }
       if (n.op == DFIR_SIZEOF || n.op == DFIR_ISMISSING) {
         if (n.a->op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "sizeof/ismissing need a String column");
         eval(*n.a);                                    // the Int32 size; -1 = missing (the load also raises the missing flag)
@@ -306,6 +313,28 @@ struct Compiler {
   }
 };
 
+// what a launch left in its error block {flags, pad, three smallest-row words} (k_interp_device.inc flag_error / flag_parse_error); k_parse.hip uses it too
+void settle_launch_errors(dfdb_query* q, int mode, const int* derr) {
+  hipStream_t s = q->t->ctx->stream;
+  struct { int flags, pad; uint64_t row[3]; } herr{0, 0, {~0ull, ~0ull, ~0ull}};
+  HIP_CHECK(hipMemcpyAsync(&herr, derr, 32, hipMemcpyDeviceToHost, s));
+  stream_wait(q->t->ctx);
+  if (!herr.flags) return;
+  for (int k = 0; k < 3; k++) if (!(herr.flags & (1 << k))) herr.row[k] = ~0ull;
+  // a predicate: WHETHER the reference raises depends on whether its block-by-block iteration reaches the row (query_execute decides once every
+  // stage has run: error_is_reached); the erroring rows count as not selected until then.
+  // One of several projection columns: query_materialize picks the error the reference's block-by-block, column-by-column order meets first.
+  uint64_t* sink = mode == 0 ? q->err_row : q->proj_err;
+  if (sink) {
+    for (int k = 0; k < 3; k++) sink[k] = std::min(sink[k], herr.row[k]);
+    return;
+  }
+  const int first = first_error_kind(herr.row);
+  if (first == 0) fail(DFDB_ERR_DIVIDE, "DivideError: integer division error");
+  if (first == 2) throw_parse_error(herr.row[2], q->t->row_base);
+  fail(DFDB_ERR_ARGUMENT, "InexactError: conversion is not exact");
+}
+
 static void run_interp(dfdb_query* q, const Node& root, int mode, bool and_existing, void* out, int64_t cap, uint8_t* out_missing) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   Compiler c; c.t = t; c.compile(root);
@@ -316,7 +345,7 @@ static void run_interp(dfdb_query* q, const Node& root, int mode, bool and_exist
   std::vector<uint8_t> img(err_off + 64, 0);
   memcpy(img.data(), &c.prog, sizeof(IProgram));
   if (!c.pool.empty()) memcpy(img.data() + pool_off, c.pool.data(), c.pool.size());
-  memset(img.data() + err_off + 8, 0xFF, 16);            // the smallest erroring rows: none yet
+  memset(img.data() + err_off + 8, 0xFF, 24);            // the smallest erroring rows: none yet
   HIP_CHECK(hipMemcpyAsync(db.p, img.data(), img.size(), hipMemcpyHostToDevice, s));
   stream_wait(q->t->ctx);
   const int64_t ntiles = ceil_div(t->nrows, kTile);
@@ -364,24 +393,7 @@ static void run_interp(dfdb_query* q, const Node& root, int mode, bool and_exist
 #undef DFDB_INTERP_LAUNCH
     HIP_CHECK(hipGetLastError());
   }
-  struct { int flags, pad; uint64_t row[2]; } herr{0, 0, {~0ull, ~0ull}};
-  HIP_CHECK(hipMemcpyAsync(&herr, derr, 24, hipMemcpyDeviceToHost, s));
-  stream_wait(q->t->ctx);
-  if (!herr.flags) return;
-  if (mode == 0) {
-    // a predicate: WHETHER the reference raises depends on whether its block-by-block iteration reaches the row (query_execute decides once every
-    // stage has run: error_is_reached); the erroring rows count as not selected until then
-    if (herr.flags & 1) q->err_row[0] = std::min(q->err_row[0], herr.row[0]);
-    if (herr.flags & 2) q->err_row[1] = std::min(q->err_row[1], herr.row[1]);
-    return;
-  }
-  if (q->proj_err) {          // one of several projection columns: query_materialize picks the error the reference's block-by-block, column-by-column order meets first
-    if (herr.flags & 1) q->proj_err[0] = std::min(q->proj_err[0], herr.row[0]);
-    if (herr.flags & 2) q->proj_err[1] = std::min(q->proj_err[1], herr.row[1]);
-    return;
-  }
-  if ((herr.flags & 1) && (!(herr.flags & 2) || herr.row[0] <= herr.row[1])) fail(DFDB_ERR_DIVIDE, "DivideError: integer division error");
-  fail(DFDB_ERR_ARGUMENT, "InexactError: conversion is not exact");
+  settle_launch_errors(q, mode, derr);
 }
 
 void run_interp_predicate(dfdb_query* q, const Node& pred, bool and_existing) { run_interp(q, pred, 0, and_existing, nullptr, 0, nullptr); }

@@ -34,7 +34,8 @@ enum Handler : uint8_t {
   H_CMP_FF, H_CMP_SS, H_CMP_UU, H_CMP_US, H_CMP_IF,
   H_INSET, H_CAST,
   // handlers that set the missing flag of their result themselves (everything above: flag = union of the operands' flags)
-  H_STRCMP, H_STRPRE, H_STRSUF, H_ISMISS, H_AND3, H_OR3, H_COALESCE, H_ISMISSA
+  H_STRCMP, H_STRPRE, H_STRSUF, H_ISMISS, H_AND3, H_OR3, H_COALESCE, H_ISMISSA,
+  H_PARSE   // DFIR_CAST over a String column: parse(T, s), never missing
 };
 constexpr int kFirstOwnFlag = H_STRCMP;
 enum BSrc : uint8_t { B_NONE = 0, B_IMM = 1, B_COL = 2, B_POP = 3 };
@@ -156,11 +157,17 @@ DFDB_SLOW double slow_fmod(double a, double b) {
   if (v == 0.0) v = __builtin_copysign(v, b); else if ((v > 0.0) != (b > 0.0)) v += b;
   return v;
 }
-// err[0]: flags (1 DivideError, 2 InexactError); the two 64-bit words at err + 2: the SMALLEST row each kind happened on (the host decides from it
-// whether the reference's block-by-block iteration would have reached that row at all: query.cpp error_is_reached)
+// err[0]: flags (1 DivideError, 2 InexactError, 4 a parse(T, s) that gives no value); the three 64-bit words at err + 2: the SMALLEST row each kind
+// happened on (the host decides from it whether the reference's block-by-block iteration would have reached that row at all: query.cpp error_is_reached).
+// The third word is `row << 3 | reason` (PR_*): the smallest row wins, and the host reads from the reason which error that row raises.
 __device__ __forceinline__ void flag_error(int* err, int code, uint64_t row) {
   atomicOr(err, code);
   atomicMin((unsigned long long*)(err + 2) + (code == 1 ? 0 : 1), (unsigned long long)row);
+}
+enum : int { PR_OK = 0, PR_ARGUMENT = 1, PR_OVERFLOW = 2, PR_METHOD = 3, PR_UNSUPPORTED = 4 };   // expr.cpp throw_parse_error reads these numbers
+__device__ __forceinline__ void flag_parse_error(int* err, int reason, uint64_t row) {
+  atomicOr(err, 4);
+  atomicMin((unsigned long long*)(err + 2) + 2, (unsigned long long)(row << 3 | (uint64_t)reason));
 }
 DFDB_SLOW double slow_fidiv(double a, double b) { return __builtin_rint((a - fmod(a, b)) / b); }
 DFDB_SLOW uint64_t slow_idivop(int64_t a, int64_t b, int op, bool uns, int64_t tmin, bool alive, int* err, uint64_t row) {
@@ -183,6 +190,74 @@ DFDB_SLOW uint64_t slow_inset(uint64_t x, int ta, const uint64_t* set, int n, in
   bool hit = false;
   for (int i = 0; i < n && !hit; i++) hit = cmp3(x, ta, set[i], tb) == 0;
   return hit;
+}
+// DFIR_CAST over a String column = parse(T, s), the ASCII subset of Base.tryparse_internal (include/dfdb_ir.h states the contract).  Every string ends as a
+// value, as an error Julia certainly raises too (PR_ARGUMENT / PR_OVERFLOW, in the order Julia meets them: left to right), or as PR_UNSUPPORTED for what
+// Julia may accept and this parser does not try.  Float64 is Clinger's fast path only: significand < 2^53, |power of ten| <= 22, ONE correctly rounded
+// multiply or divide of two exact doubles; everything else is PR_UNSUPPORTED, never an approximation.
+__device__ __forceinline__ bool parse_ws(uint8_t c) { return c == 0x20 || (c >= 0x09 && c <= 0x0d); }
+__device__ __forceinline__ uint64_t parse_bytes(const uint8_t* p, int len, int rt, int& reason) {
+  int b = 0, e = len;
+  for (int i = 0; i < len; i++) if (p[i] >= 0x80) { reason = PR_UNSUPPORTED; return 0; }      // (Unicode spaces: Julia's to decide)
+  while (b < e && parse_ws(p[b])) b++;
+  while (e > b && parse_ws(p[e - 1])) e--;
+  if (b == e) { reason = PR_ARGUMENT; return 0; }                                                // empty or all whitespace
+  const bool flt = rt == DFDB_F64, sgn = flt || issigned(rt);
+  bool neg = false;
+  if (p[b] == '+' || (sgn && p[b] == '-')) {
+    neg = p[b] == '-'; b++;
+    if (b == e) { reason = flt ? PR_UNSUPPORTED : PR_ARGUMENT; return 0; }                       // a sign with nothing after it
+    if (parse_ws(p[b])) { reason = PR_UNSUPPORTED; return 0; }                                   // Julia skips whitespace after the sign
+  }
+  if (!flt) {
+    if (p[b] == '0' && b + 1 < e && (p[b + 1] == 'x' || p[b + 1] == 'o' || p[b + 1] == 'b')) { reason = PR_UNSUPPORTED; return 0; }
+    uint64_t lim;                                                                                // the largest magnitude of this sign
+    switch (rt) {
+      case DFDB_I8: lim = 127; break; case DFDB_I16: lim = 32767; break; case DFDB_I32: lim = 2147483647ull; break; case DFDB_I64: lim = 9223372036854775807ull; break;
+      case DFDB_U8: lim = 255; break; case DFDB_U16: lim = 65535; break; case DFDB_U32: lim = 4294967295ull; break; default: lim = ~0ull; break;
+    }
+    if (neg) lim += 1;
+    uint64_t v = 0;
+    for (; b < e; b++) {
+      const uint32_t d = (uint32_t)p[b] - '0';
+      if (d > 9) { reason = PR_ARGUMENT; return 0; }
+      if (v > (lim - d) / 10) { reason = PR_OVERFLOW; return 0; }
+      v = v * 10 + d;
+    }
+    return neg ? 0 - v : v;
+  }
+  // Float64: (digits[.digits*] | .digits)[(e|E)[+-]digits]
+  uint64_t m = 0; int nd = 0, frac = 0; bool big = false;
+  for (; b < e && (uint32_t)p[b] - '0' <= 9; b++, nd++) { if (m >= (1ull << 53)) big = true; else m = m * 10 + (p[b] - '0'); }
+  if (b < e && p[b] == '.') {
+    b++;
+    for (; b < e && (uint32_t)p[b] - '0' <= 9; b++, nd++, frac++) { if (m >= (1ull << 53)) big = true; else m = m * 10 + (p[b] - '0'); }
+  }
+  int ex = 0;
+  bool bad = nd == 0;
+  if (!bad && b < e && (p[b] == 'e' || p[b] == 'E')) {
+    b++;
+    bool eneg = false;
+    if (b < e && (p[b] == '+' || p[b] == '-')) { eneg = p[b] == '-'; b++; }
+    int ned = 0;
+    for (; b < e && (uint32_t)p[b] - '0' <= 9; b++, ned++) if (ex < 10000) ex = ex * 10 + (p[b] - '0');
+    bad = ned == 0;
+    if (eneg) ex = -ex;
+  }
+  const int e10 = ex - frac;
+  if (bad || b != e || big || m >= (1ull << 53) || e10 > 22 || e10 < -22) { reason = PR_UNSUPPORTED; return 0; }
+  double p10 = 1.0;                                                                              // 10^|e10|: exact up to 10^22 (every partial product is)
+  for (int i = e10 < 0 ? -e10 : e10; i > 0; i--) p10 *= 10.0;
+  const double d = e10 < 0 ? (double)m / p10 : (double)m * p10;
+  return d_bits(neg ? -d : d);
+}
+// alive: the row is inside the table and selected; only such a row is parsed, and only it can raise
+DFDB_SLOW uint64_t slow_parse(const uint8_t* p, int len, bool missing, int rt, bool alive, int* err, uint64_t row) {
+  if (!alive) return 0;
+  int reason = missing ? PR_METHOD : PR_OK;
+  const uint64_t v = missing ? 0 : parse_bytes(p, len, rt, reason);
+  if (reason) { flag_parse_error(err, reason, row); return 0; }
+  return v;
 }
 // DFIR_CAST = Julia's T(x) / convert(T, x): exact or InexactError (Int8(300), Int8(300.0), UInt64(-1), UInt64(-1.0), Int64(typemax(UInt64)),
 // Bool(2) all throw; Float32(x) rounds).  The implicit promotions of arithmetic wrap instead (`a % T`, Base int.jl) and do not come here.

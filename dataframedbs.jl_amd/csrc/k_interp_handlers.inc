@@ -88,6 +88,18 @@
               Am[k] = (NUL && (COL_DTYPE(in_slot) & DFDB_NULLABLE)) ? (uint32_t)(sz < 0) : 0u;
             }
           } break;
+          case H_PARSE: {   // parse(T, s): the value, or one of the outcomes of slow_parse reported with its row
+            const IColDesc& c = prog->cols[in_slot];
+            const int rt = (w2 >> 16) & 0xff, so = w2 >> 24;
+#pragma unroll
+            EACH {
+              const int32_t sz = ((const int32_t*)c.data + base)[idx[k]];   // idx is clamped: always a valid row
+              const bool alive = inb[k] && ((maskword[k] >> lane) & 1ull);
+              const uint8_t* p = c.bytes + (int64_t)lds[((stack_levels + so) * kW + k) * kBlock + tid];
+              A[k] = slow_parse(p, sz > 0 ? sz : 0, sz < 0, rt, alive, err, (uint64_t)(base + idx[k]));
+              Am[k] = 0;                                                    // parse(T, ::Missing) is a MethodError, not missing
+            }
+          } break;
           case H_ISMISS: {
             const uint64_t* m = prog->cols[in_slot].missing;
 #pragma unroll

@@ -1,0 +1,164 @@
+// k_parse.hip — the conversion kernel: a projected column that is exactly `CAST T (COL s)` over a String column, i.e. parse.(T, s) — the tutorial's
+// add_column!(t, :id, parse.(Int64, t.s)) and materialize (include/dfdb_ir.h has the contract).
+//
+// The interpreter's H_PARSE (k_interp_device.inc: slow_parse / parse_bytes) is the definition, and this file compiles that very text: every row the fast
+// path below does not settle goes through the same function, so the two paths cannot disagree on a value, an error kind or an error row.
+//
+// One wave per 1024-row tile, the shape of k_str_match_short's staged form (k_strings.hip): the sixteen size loads and the tile's byte range
+// [tile_off[t], tile_off[t+1]), as aligned 16-byte loads, are in flight together; the bytes are parked in LDS and row offsets are wave prefix sums of the
+// sizes.  A lane reads its row as four aligned 8-byte LDS words, shifts them into place and converts [sign] + 1..19 digits eight at a time in registers
+// (SWAR); anything else — whitespace, other characters, 20 digits, a value outside the target, a missing row, Float64 — is slow_parse's, over the same LDS
+// bytes.  A tile whose bytes do not fit the stage is parsed straight from the arena.  Row j * 64 + lane belongs to lane `lane`, so the results of 64
+// neighbouring rows leave in one coalesced store.  SELECTED: only the rows of the bitmap, written compacted at prefix[tile] + rank (as k_gather does).
+#include "device_utils.hpp"
+#include "engine.hpp"
+
+namespace dfdb {
+
+#include "k_interp_device.inc"
+
+void settle_launch_errors(dfdb_query* q, int mode, const int* derr);   // k_interp.hip
+
+constexpr uint32_t kParseStage = 19968;      // 1024 rows x 19 bytes + the lead of the 16-byte boundary below
+constexpr int kParseWaves = 2;               // waves per workgroup: 39 KB of LDS each, four workgroups per CU
+
+__device__ __forceinline__ uint64_t parse_get8(uint64_t x0, uint64_t x1, uint64_t x2, uint32_t o) {   // 8 bytes at byte offset o (0..15) of the 24 bytes x0 x1 x2
+  const uint64_t lo = (o & 8u) ? x1 : x0, hi = (o & 8u) ? x2 : x1;
+  const uint32_t sh = (o & 7u) * 8u;
+  return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+}
+__device__ __forceinline__ bool swar_digits8(uint64_t x) {       // all eight bytes are '0'..'9'
+  return ((x & 0xF0F0F0F0F0F0F0F0ull) | (((x + 0x0606060606060606ull) & 0xF0F0F0F0F0F0F0F0ull) >> 4)) == 0x3333333333333333ull;
+}
+__device__ __forceinline__ uint64_t swar_value8(uint64_t x) {    // eight ASCII digits, the first in the lowest byte
+  x -= 0x3030303030303030ull;
+  x = x * 10 + (x >> 8);
+  return (((x & 0x000000FF000000FFull) * 0x000F424000000064ull) + (((x >> 16) & 0x000000FF000000FFull) * 0x0000271000000001ull)) >> 32;
+}
+// [sign] + 1..19 digits that fit the target: true and the register image; anything else is the slow path's to decide
+__device__ __forceinline__ bool parse_fast(uint64_t x0, uint64_t x1, uint64_t x2, int len, int rt, uint64_t& out) {
+  const uint32_t c0 = (uint32_t)x0 & 0xffu;
+  const uint32_t s = (c0 == '+' || (issigned(rt) && c0 == '-')) ? 1u : 0u;
+  const bool neg = s && c0 == '-';
+  const int nd = len - (int)s;
+  if (nd < 1 || nd > 19) return false;
+  const uint32_t k = (uint32_t)nd & 7u, full = (uint32_t)nd >> 3;
+  uint32_t o = s; uint64_t v = 0; bool ok = true;
+  if (k) {
+    const uint64_t x = (parse_get8(x0, x1, x2, o) << ((8u - k) * 8u)) | (0x3030303030303030ull >> (k * 8u));      // left-padded with '0'
+    ok = swar_digits8(x); v = swar_value8(x); o += k;
+  }
+  if (full >= 1) { const uint64_t x = parse_get8(x0, x1, x2, o); ok = ok && swar_digits8(x); v = v * 100000000ull + swar_value8(x); o += 8; }
+  if (full >= 2) { const uint64_t x = parse_get8(x0, x1, x2, o); ok = ok && swar_digits8(x); v = v * 100000000ull + swar_value8(x); }
+  uint64_t lim;                                                  // the largest magnitude of this sign (19 digits never overflow 64 bits)
+  switch (rt) {
+    case DFDB_I8: lim = 127; break; case DFDB_I16: lim = 32767; break; case DFDB_I32: lim = 2147483647ull; break; case DFDB_I64: lim = 9223372036854775807ull; break;
+    case DFDB_U8: lim = 255; break; case DFDB_U16: lim = 65535; break; case DFDB_U32: lim = 4294967295ull; break; default: lim = ~0ull; break;
+  }
+  if (neg) lim += 1;
+  out = neg ? 0 - v : v;
+  return ok && v <= lim;
+}
+
+template <int W, bool SELECTED>
+__global__ __launch_bounds__(kParseWaves * 64) void k_str_parse(const int32_t* __restrict__ sizes, const int64_t* __restrict__ tile_off, const uint8_t* __restrict__ bytes,
+                                                                const uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ prefix, void* __restrict__ out,
+                                                                int64_t out_cap, int64_t nrows, int64_t ntiles, int rt, int* __restrict__ err) {
+  __shared__ __attribute__((aligned(16))) uint64_t stage_sh[kParseWaves][kParseStage / 8 + 8];
+  const int lane = lane_id();
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  uint64_t* const stage = stage_sh[wid];
+  const int64_t wave = (int64_t)blockIdx.x * kParseWaves + wid, nwaves = (int64_t)gridDim.x * kParseWaves;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const bool isint = rt != DFDB_F64;
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    uint32_t m_lo = ~0u, m_hi = ~0u;
+    if (SELECTED) {
+      const uint64_t w = lane < 16 ? bitmap[tile * 16 + lane] : 0ull;
+      if (__ballot(w != 0) == 0) continue;                               // nothing selected in this tile
+      m_lo = (uint32_t)w; m_hi = (uint32_t)(w >> 32);
+    }
+    const int64_t base = tile * kTile;
+    int32_t sz[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? __builtin_nontemporal_load(sizes + i) : 0; }
+    const int64_t o0 = tile_off[tile], a0 = o0 & ~15ll;
+    const uint32_t lead = (uint32_t)(o0 - a0);
+    const int64_t span = tile_off[tile + 1] - a0 + 16;                   // (up to 31 bytes past the tile's end: every arena is allocated with 64 bytes of slack)
+    const bool staged = span <= (int64_t)kParseStage;                   // wave-uniform
+    if (staged) {
+      const uint32_t need = (uint32_t)span, lastc = (need - 1u) & ~15u;
+      // (a piece past the range's end is the range's last piece once more, loaded and stored by several lanes alike: no predication, no divergence)
+      for (uint32_t c0 = 0; c0 < need; c0 += 5 * 1024u) {
+        u32x4 piece[5];
+#pragma unroll
+        for (int i = 0; i < 5; i++) { uint32_t c = c0 + (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; piece[i] = __builtin_nontemporal_load((const u32x4*)(bytes + a0 + c)); }
+#pragma unroll
+        for (int i = 0; i < 5; i++) { uint32_t c = c0 + (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; *(u32x4*)((uint8_t*)stage + c) = piece[i]; }
+      }
+      wave_lds_fence();
+    }
+    uint32_t run = 0, run_sel = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int32_t s0 = sz[j];
+      const uint32_t len = s0 > 0 ? (uint32_t)s0 : 0u;
+      const uint32_t incl = wave_incl_scan(len);
+      const uint32_t rel = run + incl - len;
+      run += __shfl(incl, 63, 64);
+      const uint64_t mw = SELECTED ? ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)m_hi, j) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)m_lo, j)) : ~0ull;
+      const int64_t row = base + j * 64 + lane;
+      const bool alive = row < nrows && ((mw >> lane) & 1ull);
+      uint64_t v = 0;
+      bool done = false;
+      if (staged && isint && alive && s0 > 0) {
+        // (the four words stay inside the stage: a row starts at least its own length before `need - 16`, and the array has 64 bytes to spare)
+        const uint32_t p = lead + rel, a = p >> 3, sh = (p & 7u) * 8u;
+        const uint64_t w0 = stage[a], w1 = stage[a + 1], w2 = stage[a + 2], w3 = stage[a + 3];
+        const uint64_t x0 = sh ? (w0 >> sh) | (w1 << (64u - sh)) : w0, x1 = sh ? (w1 >> sh) | (w2 << (64u - sh)) : w1, x2 = sh ? (w2 >> sh) | (w3 << (64u - sh)) : w2;
+        done = parse_fast(x0, x1, x2, (int)len, rt, v);
+      }
+      if (!done) {
+        const uint8_t* p = staged ? (const uint8_t*)stage + lead + rel : bytes + o0 + rel;
+        v = slow_parse(p, (int)len, s0 < 0, rt, alive, err, (uint64_t)row);
+      }
+      const int64_t o = SELECTED ? (int64_t)prefix[tile] + run_sel + (int64_t)__popcll(mw & ((1ull << lane) - 1ull)) : row;
+      if (alive && o < out_cap) {
+        if (W == 1) ((uint8_t*)out)[o] = (uint8_t)v; else if (W == 2) ((uint16_t*)out)[o] = (uint16_t)v;
+        else if (W == 4) ((uint32_t*)out)[o] = (uint32_t)v; else ((uint64_t*)out)[o] = v;
+      }
+      run_sel += (uint32_t)__popcll(mw);
+    }
+  }
+}
+
+// `e` is CAST T (COL s) over a resident String column: the selected rows' values, compacted, into dst (cap elements)
+void run_str_parse(dfdb_query* q, const Node& e, void* dst, int64_t cap) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const Column& c = t->cols[(size_t)e.a->col];
+  if (!c.resident) fail(DFDB_ERR_ARGUMENT, "column %s is not resident on the device (dfdb_table_load it first)", c.name.c_str());
+  const int64_t ntiles = ceil_div(t->nrows, kTile);
+  if (ntiles == 0) return;
+  DevBuf& db = q->tmp_a; db.ensure(64);
+  struct { int flags, pad; uint64_t row[3]; } init{0, 0, {~0ull, ~0ull, ~0ull}};      // the interpreter's error block
+  HIP_CHECK(hipMemcpyAsync(db.p, &init, sizeof init, hipMemcpyHostToDevice, s));
+  stream_wait(ctx);
+  int* derr = (int*)db.p;
+  const int rt = dt_base(e.cast_to), w = dt_width(rt);
+  const bool all = cap == t->nrows;                                     // every row is selected: no bitmap, no compaction
+  int64_t grid = ceil_div(ntiles, kParseWaves); if (grid > 32768) grid = 32768;
+  {
+    LaunchTimer lt(ctx, "str_parse");
+#define DFDB_PARSE_LAUNCH(W, SEL)                                                                                                                                             \
+    hipLaunchKernelGGL((k_str_parse<W, SEL>), dim3((unsigned)grid), dim3(kParseWaves * 64), 0, s, c.data.as<int32_t>(), (const int64_t*)c.tile_off.p, c.bytes.as<uint8_t>(), \
+                       q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), dst, cap, t->nrows, ntiles, rt, derr)
+#define DFDB_PARSE_PICK(W) do { if (all) DFDB_PARSE_LAUNCH(W, false); else DFDB_PARSE_LAUNCH(W, true); } while (0)
+    switch (w) { case 1: DFDB_PARSE_PICK(1); break; case 2: DFDB_PARSE_PICK(2); break; case 4: DFDB_PARSE_PICK(4); break; default: DFDB_PARSE_PICK(8); break; }
+#undef DFDB_PARSE_PICK
+#undef DFDB_PARSE_LAUNCH
+    HIP_CHECK(hipGetLastError());
+  }
+  settle_launch_errors(q, 1, derr);
+}
+
+}  // namespace dfdb

@@ -22,6 +22,7 @@ namespace dfdb {
 // launchers living in k_interp.hip / k_strings.hip that take engine-level descriptions
 void run_interp_predicate(dfdb_query* q, const Node& pred, bool and_existing);
 void run_interp_project(dfdb_query* q, const Node& expr, void* dst, int64_t cap, uint8_t* missing_dst);
+void run_str_parse(dfdb_query* q, const Node& expr, void* dst, int64_t cap);   // k_parse.hip
 
 // ---------------------------------------------------------------- ranges
 static int64_t range_len(int64_t a, int64_t s, int64_t b) {
@@ -692,25 +693,29 @@ static bool error_is_reached(dfdb_query* q, uint64_t erow) {
   return true;
 }
 static void raise_reached_errors(dfdb_query* q, int nstages) {
-  const uint64_t er[2] = {q->err_row[0], q->err_row[1]};
+  const uint64_t ew[3] = {q->err_row[0], q->err_row[1], q->err_row[2]};
+  uint64_t er[3];
+  for (int k = 0; k < 3; k++) er[k] = err_word_row(k, ew[k]);
   bool any_range = false;
   for (const Stage& st : q->stages) any_range = any_range || st.kind != ST_PRED;
+  // in row order: the first error the iteration reaches is the one Julia throws; the parse word first, it wins a tie on the same row (first_error_kind)
+  int order[3] = {2, 0, 1};
+  std::stable_sort(order, order + 3, [&](int a, int b) { return er[a] < er[b]; });
   int raise = -1;
-  if (!any_range) raise = er[0] <= er[1] ? 0 : 1;                             // every block is evaluated: the error of the smaller row
+  if (!any_range) raise = order[0];                                           // every block is evaluated: the error of the smallest row
   else {
     q->err_checking = true;
     try {
-      // in row order: the first error the iteration reaches is the one Julia throws
-      const int first = er[0] <= er[1] ? 0 : 1;
-      for (int i = 0; i < 2 && raise < 0; i++) { const int kind = i == 0 ? first : 1 - first; if (er[kind] != ~0ull && error_is_reached(q, er[kind])) raise = kind; }
+      for (int i = 0; i < 3 && raise < 0; i++) { const int kind = order[i]; if (er[kind] != ~0ull && error_is_reached(q, er[kind])) raise = kind; }
       if (raise < 0) query_execute(q, nstages);                                // not reached: the result stands (the erroring rows are beyond the finish)
     } catch (...) { q->err_checking = false; throw; }
     q->err_checking = false;
   }
-  q->err_row[0] = q->err_row[1] = ~0ull;
+  q->err_row[0] = q->err_row[1] = q->err_row[2] = ~0ull;
   // (the row travels with the error: the shards of a multi-GPU group raise the error of the lowest GLOBAL row, group.cpp)
   if (raise == 0) { q->executed_stages = -1; throw Error(DFDB_ERR_DIVIDE, "DivideError: integer division error", (uint64_t)q->t->row_base + er[0]); }
   if (raise == 1) { q->executed_stages = -1; throw Error(DFDB_ERR_ARGUMENT, "InexactError: conversion is not exact", (uint64_t)q->t->row_base + er[1]); }
+  if (raise == 2) { q->executed_stages = -1; throw_parse_error(ew[2], q->t->row_base); }
 }
 
 void query_execute(dfdb_query* q, int nstages) {
@@ -722,7 +727,7 @@ void query_execute(dfdb_query* q, int nstages) {
   q->comp_scanned.clear();
   for (auto& a : q->arenas) a.second.valid = false;      // the survivors' blocks of the previous selection
   q->gr_state = 0;             // a pending groupreduce belongs to the selection that is being replaced: its fetch must not restore the old one over this
-  q->err_row[0] = q->err_row[1] = ~0ull;
+  q->err_row[0] = q->err_row[1] = q->err_row[2] = ~0ull;
   // A range-like stage that is EMPTY (an empty range, an empty index vector) finishes the reference's iteration before the first block is read:
   // is_finished (selection.jl:192-196: `last <= offset` for ANY range stage of the queue) is tested ahead of every block (blocksiterator.jl:69-78).
   // Nothing is evaluated — a predicate of another stage that would raise DivideError on some row never runs (found by the fuzz soak: the engine raised).
@@ -757,7 +762,7 @@ void query_execute(dfdb_query* q, int nstages) {
   }
   scan_prefix(q);
   q->executed_stages = nstages;
-  if (!q->err_checking && (q->err_row[0] != ~0ull || q->err_row[1] != ~0ull)) raise_reached_errors(q, nstages);
+  if (!q->err_checking && (q->err_row[0] != ~0ull || q->err_row[1] != ~0ull || q->err_row[2] != ~0ull)) raise_reached_errors(q, nstages);
 }
 
 static void ensure_executed(dfdb_query* q) {
@@ -1061,7 +1066,9 @@ void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
         LaunchTimer lt(ctx, "gather");
         launch_gather_transform(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), gather_source(q, tcol->col), dt_base(sc.dtype), tf, dst, t->nrows, cnt);
       }
-    } else
+    } else if (e.op == DFIR_CAST && e.a->op == DFIR_COL && dt_base(e.a->dtype) == DFDB_STRING && ctx_option(ctx, "parse_kernel", 1) != 0)
+      run_str_parse(q, e, dst, cnt);                        // exactly parse.(T, s): the conversion kernel (k_parse.hip); "parse_kernel" = 0: the interpreter
+    else
     run_interp_project(q, e, dst, cnt, mdst);
     if (!dev) {
       HIP_CHECK(hipMemcpyAsync(o.data, dst, (size_t)cnt * w, hipMemcpyDeviceToHost, s));
@@ -1079,20 +1086,22 @@ void query_materialize(dfdb_query* q, dfdb_outcol* outs, int32_t ncols) {
   // columns in order (projection.jl:149-154 under blocksiterator.jl:98-121) — the error it throws is the one of the first BLOCK that holds an erroring row, the
   // first such COLUMN in that block, the first such row of that column.  The columns are computed whole here, so their first erroring rows are collected and
   // the choice is made at the end.
-  uint64_t pe[2], best_block = ~0ull; int best_kind = -1;
+  uint64_t pe[3], best_block = ~0ull, best_word = ~0ull; int best_kind = -1;
   const uint64_t bs = (uint64_t)std::max<int64_t>(q->t->block_size, 1);
   q->proj_err = pe;
   try {
     for (int32_t p = 0; p < ncols; p++) {
-      pe[0] = pe[1] = ~0ull;
+      pe[0] = pe[1] = pe[2] = ~0ull;
       materialize_col(q, p, outs[p], cnt);
-      const uint64_t r = std::min(pe[0], pe[1]);
-      if (r != ~0ull && r / bs < best_block) { best_block = r / bs; best_kind = pe[0] <= pe[1] ? 0 : 1; }
+      const int k = first_error_kind(pe);
+      const uint64_t r = k < 0 ? ~0ull : err_word_row(k, pe[k]);
+      if (r != ~0ull && r / bs < best_block) { best_block = r / bs; best_kind = k; best_word = pe[k]; }
     }
   } catch (...) { q->proj_err = nullptr; throw; }
   q->proj_err = nullptr;
   if (best_kind == 0) fail(DFDB_ERR_DIVIDE, "DivideError: integer division error");
   if (best_kind == 1) fail(DFDB_ERR_ARGUMENT, "InexactError: conversion is not exact");
+  if (best_kind == 2) throw_parse_error(best_word, q->t->row_base);
 }
 
 // add_column!(table, name, lazy_col) (src/tables/table.jl:96-124): the p-th column of the view materialised into a new

@@ -353,8 +353,8 @@ void load_chunk(dfdb_stream* s, Slot* sl) {
         std::vector<int64_t> counts;
         query_block_counts(q, s->block_size, counts);
         for (int64_t b = 0; b < nb && b < (int64_t)counts.size(); b++) keep[(size_t)b] = counts[(size_t)b] > 0;
-        sl->pre_executed = s->kprefix == (int)q->stages.size() && q->err_row[0] == ~0ull && q->err_row[1] == ~0ull;
-        if (!sl->pre_executed) { q->executed_stages = -1; q->count = -1; q->prefix_valid = false; q->err_row[0] = q->err_row[1] = ~0ull; }
+        sl->pre_executed = s->kprefix == (int)q->stages.size() && q->err_row[0] == ~0ull && q->err_row[1] == ~0ull && q->err_row[2] == ~0ull;
+        if (!sl->pre_executed) { q->executed_stages = -1; q->count = -1; q->prefix_valid = false; q->err_row[0] = q->err_row[1] = q->err_row[2] = ~0ull; }
       }
       bool all = true;
       for (char kp : keep) all = all && kp;

@@ -1144,6 +1144,11 @@ sizeof = _fn_bc(ir.sizeof)
 float64 = _fn_bc(ir.float64)
 
 
+def parse(dtype: int, c):
+    """parse.(T, col): a String column (or Expr) as an integer type or Float64; the result type is the engine's (dfdb_expr_result_type): T, never missing."""
+    return _fn_bc(lambda e: ir.parse(dtype, e))(c)
+
+
 def coalesce(c, default):
     """coalesce.(col, default): DFColumn or Expr; `default` may itself be a column of the same view."""
     if isinstance(c, DFColumn):

@@ -310,6 +310,11 @@ def cast(a, dtype: int) -> Expr: return Expr(CAST, (wrap(a),), dtype)
 def float64(a) -> Expr: return cast(a, F64)
 
 
+def parse(dtype: int, a) -> Expr:
+    """`parse.(T, s)` over a String column: the same bytes as `cast(s, T)` — DFIR_CAST applied to a String operand means parse (include/dfdb_ir.h)."""
+    return cast(a, dtype)
+
+
 def trace(fn, leaves: Sequence[Expr]) -> Expr:
     """Call a user function on symbolic leaves: `(:a,:b) => (a,b) -> …` (view.jl:64-68)."""
     r = fn(*leaves)

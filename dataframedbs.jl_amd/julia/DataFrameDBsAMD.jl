@@ -53,6 +53,9 @@ function check(rc::Int32)
     msg = last_error()
     # InexactError (Int8(300), UInt64(-1) inside a predicate) travels as DFDB_ERR_ARGUMENT with its name in the text (include/dfdb.h)
     rc == 1 && startswith(msg, "InexactError") && throw(InexactError(:convert, Integer, msg))
+    # parse.(T, s): the engine names the error Base raises (include/dfdb_ir.h, DFIR_CAST over a String column)
+    rc == 1 && startswith(msg, "OverflowError") && throw(OverflowError(msg))
+    rc == 1 && startswith(msg, "MethodError") && throw(MethodError(parse, (Number, missing)))
     rc == 1 && throw(ArgumentError(msg))
     rc == 4 && throw(KeyError(msg))
     rc == 5 && throw(BoundsError(msg))
@@ -126,13 +129,19 @@ Base.in(a::Tr, s::AbstractVector) = Tr(vcat(a.code, tr(s).code, 0x40))
 Base.in(a::Tr, s::AbstractVector{<:AbstractString}) = isempty(s) ? throw(Unsupported("in.() over an empty set of strings")) : reduce((x, y) -> x | y, [a == v for v in s])
 Base.Float64(a::Tr) = Tr(vcat(a.code, 0x50, DT[Float64]))
 Base.convert(::Type{Float64}, a::Tr) = Float64(a)
+# parse.(T, s) over a String column: DFIR_CAST applied to a String operand (include/dfdb_ir.h), written after the column — outside OPS / UNARY.  What the
+# device parser does not decide (Unicode spaces, "0x10", a Float64 outside the exact domain) comes back as status 7 and the view takes the Julia path.
+const PARSE_TARGETS = (Int8, Int16, Int32, Int64, UInt8, UInt16, UInt32, UInt64, Float64)
+emit_parse(::Type{T}, a::Tr) where {T} = T in PARSE_TARGETS ? Tr(vcat(a.code, 0x50, DT[T])) : throw(Unsupported("parse($(T), s) is outside the IR"))
+Base.parse(::Type{T}, a::Tr) where {T} = emit_parse(T, a)
 
 # BlockBroadcasting / ColRef -> Tr.  `ord` maps a column Symbol to its 0-based table ordinal.
 lower(c::ColRef, ord) = leaf(io -> emit_col(io, ord[c.name]))
 lower(x, ord) = tr(x)
 function lower(b::BlockBroadcasting, ord)
-    args = map(a -> lower(a, ord), b.args)
     f = b.f
+    f === parse && length(b.args) == 2 && b.args[1] isa Type && return emit_parse(b.args[1], lower(b.args[2], ord))   # (a Type is no IR constant)
+    args = map(a -> lower(a, ord), b.args)
     if f === in && length(args) == 2
         return Tr(vcat(args[1].code, args[2].code, 0x40))
     elseif haskey(OPS, f) && length(args) == 2

@@ -69,5 +69,24 @@ enum {
 
 /* ---- conversion ---- */
 #define DFIR_CAST  0x50 /* payload: u8 dtype ; Julia T(x) / convert */
+/* DFIR_CAST applied to a String operand means parse(T, s) (Julia has no T("12"), so `COL s; CAST T` is free: "convert this column to T").
+ *   operand  a String or Union{String,Missing} COLUMN leaf, as for sizeof; any other String-typed operand is DFDB_ERR_UNSUPPORTED
+ *   targets  Int8 .. Int64, UInt8 .. UInt64, Float64 (Bool, Float32, String: DFDB_ERR_UNSUPPORTED)
+ *   type     the target, never Union{T,Missing}, also over a nullable column: parse(T, ::Missing) is a MethodError
+ * Integers are the ASCII subset of Base.tryparse_internal: [ws][+-]digits[ws], ws = 0x20 and 0x09-0x0d, `-` for signed targets only; leading zeros are
+ * fine, "-9223372036854775808" parses, "-0" is 0.  Every evaluated row ends in exactly one of three ways:
+ *   1. the value;
+ *   2. an error Julia certainly raises too, status DFDB_ERR_ARGUMENT with the smallest raising row, the message starts with the Julia name:
+ *        "ArgumentError:"  empty or all whitespace, a sign with nothing after it, a non-digit where a digit must be, characters after trailing
+ *                          whitespace, `-` with an unsigned target
+ *        "OverflowError:"  the value does not fit the target (read left to right: whichever of the two comes first in the string)
+ *        "MethodError: no method matching parse(::Type{T}, ::Missing)"  a missing row
+ *   3. DFDB_ERR_UNSUPPORTED with the row, "the caller falls back to the Julia path": strings Julia may accept and the device does not try — any byte
+ *      >= 0x80 (Unicode spaces), whitespace directly after the sign, digits that start 0x / 0o / 0b.  Never reported as ArgumentError, never given a value.
+ * Float64 is the correctly rounded value or DFDB_ERR_UNSUPPORTED, never an approximation: [ws][+-](digits[.digits*] | .digits)[(e|E)[+-]digits][ws] whose
+ * significand with the point removed is < 2^53 and whose power of ten then has |e10| <= 22 — one IEEE multiply or divide of two exact doubles (Clinger's
+ * fast path; "35.79" is 3579 / 1e2, "-0.0" keeps its sign).  Longer significands, larger exponents, Inf, NaN, hex floats, "1f3", underscores: UNSUPPORTED
+ * with the smallest such row; empty, all-whitespace and missing rows raise as for integers.
+ * Which rows count as evaluated, and which of several errors is reported (the smallest row among all kinds), follows the rule of DivideError / InexactError. */
 
 #endif
