@@ -4,6 +4,7 @@ Checked against a numpy restatement written here: each key's isequal image (one 
 groups in order of the first selected row that holds the tuple, exact counts and integer results, Float64 sums within n * eps * sum|x|, signbit on
 minimum / maximum.  Every case runs over a filtered view."""
 import ctypes as C
+import math
 import os
 import shutil
 import tempfile
@@ -61,8 +62,23 @@ def from_image(im, v_dtype):
     return (im ^ np.uint64(1 << 63)).view(np.int64)
 
 
-def expect(keys, sel, reducers):
-    """keys: list of key columns; sel: bool mask; reducers: {name: (values or None, stat)} -> (first rows, counts, {name: values})"""
+def fsum_groups(v, gid, ng):
+    """per group, the exact sum of the Float64 values rounded once (math.fsum); NaN where the group holds a NaN or infinities of both signs"""
+    order = np.argsort(gid, kind="stable")
+    ends = np.cumsum(np.bincount(gid, minlength=ng))
+    vs, out, lo = v[order].tolist(), np.empty(ng, np.float64), 0
+    for g, hi in enumerate(ends.tolist()):
+        try:
+            out[g] = math.fsum(vs[lo:hi])
+        except (ValueError, OverflowError):
+            out[g] = float(np.sum(v[order][lo:hi]))
+        lo = hi
+    return out
+
+
+def expect(keys, sel, reducers, exact_float_sums=False):
+    """keys: list of key columns; sel: bool mask; reducers: {name: (values or None, stat)} -> (first rows, counts, {name: values});
+    exact_float_sums: Float sums and means from math.fsum per group instead of a float64 running sum"""
     rows = np.flatnonzero(sel)
     if len(rows) == 0:
         return rows, np.zeros(0, np.int64), {nm: None for nm in reducers}
@@ -84,7 +100,10 @@ def expect(keys, sel, reducers):
         v = vals[rows]
         if stat in ("sum", "mean"):
             acc = np.zeros(ng, np.float64 if v.dtype.kind == "f" else (np.uint64 if v.dtype.kind == "u" else np.int64))
-            np.add.at(acc, gid, v.astype(acc.dtype))
+            if exact_float_sums and v.dtype.kind == "f":
+                acc = fsum_groups(v.astype(np.float64), gid, ng)
+            else:
+                np.add.at(acc, gid, v.astype(acc.dtype))
             out[nm] = acc if stat == "sum" else acc.astype(np.float64) / cnt
         else:
             im = np.full(ng, ~np.uint64(0) if stat == "min" else np.uint64(0), np.uint64)
@@ -93,8 +112,8 @@ def expect(keys, sel, reducers):
     return rows[first[order]], cnt, out
 
 
-def check_frame(df, by, keys, sel, reducers, tag=""):
-    first_rows, cnt, want = expect(keys, sel, reducers)
+def check_frame(df, by, keys, sel, reducers, tag="", exact_float_sums=False):
+    first_rows, cnt, want = expect(keys, sel, reducers, exact_float_sums)
     assert list(df.columns) == [*by, "count", *reducers], (tag, list(df.columns))
     assert len(df) == len(cnt), (tag, len(df), len(cnt))
     assert np.array_equal(df["count"].to_numpy(), cnt), tag
@@ -123,7 +142,9 @@ def check_frame(df, by, keys, sel, reducers, tag=""):
             absum = expect(keys, sel, {"a": (np.abs(vals), "sum")})[2]["a"]
             tol = cnt * np.finfo(np.float64).eps * absum / (cnt if stat == "mean" else 1) + 1e-300
             nan = np.isnan(w)                                         # (a group with a NaN sums to NaN)
-            assert np.array_equal(np.isnan(got), nan) and np.all(np.abs(got - w)[~nan] <= tol[~nan]), (tag, nm)
+            with np.errstate(invalid="ignore"):                       # (an infinite sum is met exactly: inf - inf has no distance)
+                near = (np.abs(got - w) <= tol) | (got == w)
+            assert np.array_equal(np.isnan(got), nan) and np.all(near[~nan]), (tag, nm)
         elif stat == "mean":
             assert np.allclose(got, w, rtol=1e-12, atol=0), (tag, nm)
         elif vals.dtype.kind == "f":
