@@ -438,4 +438,15 @@ bool match_string_term(const Node& n, const dfdb_table& t, int& ordinal, int& mo
   ordinal = coln->col; pat = cn->str; return true;
 }
 
+// `s1 OP s2` over two String columns (the same column twice included).  allow_nullable: the caller evaluates `coalesce(term, false)`, which k_str_pair
+// gives over Union{String,Missing} operands (a row with a missing side selects nothing)
+bool match_string_pair_term(const Node& n, int& ord_a, int& ord_b, int& op, bool allow_nullable) {
+  if (!n.a || !n.b || n.a->op != DFIR_COL || n.b->op != DFIR_COL) return false;
+  if (dt_base(n.a->dtype) != DFDB_STRING || dt_base(n.b->dtype) != DFDB_STRING) return false;
+  if ((dt_nullable(n.a->dtype) || dt_nullable(n.b->dtype)) && !allow_nullable) return false;
+  op = cmp_from_ir(n.op);
+  if (op < 0) return false;
+  ord_a = n.a->col; ord_b = n.b->col; return true;
+}
+
 }  // namespace dfdb

@@ -156,6 +156,71 @@ void launch_dict_scan(hipStream_t s, const uint16_t* codes, const uint32_t* lut,
   else hipLaunchKernelGGL(k_dict_scan<false>, dim3(grid_for(nt, 2048)), dim3(kBlock), 0, s, codes, lut, lut_words, bitmap, tile_counts, nrows, nt);
 }
 
+// Two dictionary columns compared (s1 OP s2): the host has ranked the union of the two dictionaries bytewise, so the rows compare their ranks — two 16-bit
+// codes read per row, no string byte touched.  Row layout of k_dict_scan: lane l takes 8 consecutive rows of each code stream (one 16-byte load each) and
+// writes one BYTE of the bitmap.  The rank tables (4 B per entry) sit in LDS when both fit kDictPairLds entries, otherwise they are read where they are.
+constexpr int kDictPairLds = 12288;
+template <bool AND_EXISTING>
+__global__ __launch_bounds__(kBlock) void k_dict_pair(const uint16_t* __restrict__ codes_a, const uint16_t* __restrict__ codes_b, const uint32_t* __restrict__ rank_a, int32_t n_a,
+                                                      const uint32_t* __restrict__ rank_b, int32_t n_b, int op, int use_lds, uint64_t* __restrict__ bitmap,
+                                                      uint32_t* __restrict__ tile_counts, int64_t nrows, int64_t ntiles) {
+  extern __shared__ uint32_t rank_sh[];                                          // [n_a + n_b] when use_lds
+  const uint32_t* ta = rank_a; const uint32_t* tb = rank_b;
+  if (use_lds) {
+    for (int k = threadIdx.x; k < n_a; k += kBlock) rank_sh[k] = rank_a[k];
+    for (int k = threadIdx.x; k < n_b; k += kBlock) rank_sh[n_a + k] = rank_b[k];
+    __syncthreads();
+    ta = rank_sh; tb = rank_sh + n_a;
+  }
+  const int lane = lane_id();
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  uint8_t* bm8 = (uint8_t*)bitmap;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    const int64_t base = tile * kTile;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int64_t r0 = base + h * 512 + (int64_t)lane * 8;
+      uint32_t wa[4] = {0, 0, 0, 0}, wb[4] = {0, 0, 0, 0};
+      // (the code arrays are allocated in whole 4096-row tiles: the 16-byte loads of a ragged last group stay inside them, its rows past the end are masked below)
+      if (r0 < nrows) {
+        const u32x4 qa = __builtin_nontemporal_load((const u32x4*)(codes_a + r0)), qb = __builtin_nontemporal_load((const u32x4*)(codes_b + r0));
+        wa[0] = qa.x; wa[1] = qa.y; wa[2] = qa.z; wa[3] = qa.w; wb[0] = qb.x; wb[1] = qb.y; wb[2] = qb.z; wb[3] = qb.w;
+      }
+      uint32_t byte = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const uint32_t ca = (wa[k >> 1] >> (16 * (k & 1))) & 0xffffu, cb = (wb[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+        const bool ok = r0 + k < nrows && ca < (uint32_t)n_a && cb < (uint32_t)n_b;
+        const uint32_t x = ok ? ta[ca] : 0u, y = ok ? tb[cb] : 0u;
+        bool r;
+        switch (op) {
+          case CMP_EQ: r = x == y; break; case CMP_NE: r = x != y; break; case CMP_LT: r = x < y; break;
+          case CMP_LE: r = x <= y; break; case CMP_GT: r = x > y; break; default: r = x >= y; break;
+        }
+        byte |= (uint32_t)(ok && r) << k;
+      }
+      const int64_t bi = tile * 128 + h * 64 + lane;
+      if (AND_EXISTING) byte &= bm8[bi];
+      bm8[bi] = (uint8_t)byte;
+      cnt += (uint32_t)__popc(byte);
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0) tile_counts[tile] = cnt;
+  }
+}
+void launch_dict_pair(hipStream_t s, const uint16_t* codes_a, const uint16_t* codes_b, const uint32_t* rank_a, int32_t n_a, const uint32_t* rank_b, int32_t n_b, int op,
+                      uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing) {
+  const int64_t nt = (nrows + kTile - 1) / kTile;
+  if (nt == 0) return;
+  const int use_lds = n_a + n_b <= kDictPairLds ? 1 : 0;
+  const size_t lds = use_lds ? (size_t)(n_a + n_b) * 4 : 0;
+  if (and_existing) hipLaunchKernelGGL(k_dict_pair<true>, dim3(grid_for(nt, 2048)), dim3(kBlock), lds, s, codes_a, codes_b, rank_a, n_a, rank_b, n_b, op, use_lds, bitmap, tile_counts, nrows, nt);
+  else hipLaunchKernelGGL(k_dict_pair<false>, dim3(grid_for(nt, 2048)), dim3(kBlock), lds, s, codes_a, codes_b, rank_a, n_a, rank_b, n_b, op, use_lds, bitmap, tile_counts, nrows, nt);
+}
+
 // Projection of a dictionary column.  K3 first compacts the selected rows' CODES (a 2-byte gather); what is left is flat work over the selected rows in
 // table order, 1024 per wave: coalesced code loads, dictionary lookups that hit in L2, coalesced size stores; then, once the tiles' byte totals are
 // scanned, every row copies its dictionary entry to its place (destination offsets by wave prefix sums).  (Gathering sizes and bytes tile by tile

@@ -186,7 +186,7 @@ struct Compiler {
     if (n.op == DFIR_CONST_STR || n.op == DFIR_CONST_SET) fail(DFDB_ERR_UNSUPPORTED, "string/set constant in an unsupported position");
     const int rt = dt_base(n.dtype);
     const bool a_str = n.a && dt_base(n.a->dtype) == DFDB_STRING, b_str = n.b && dt_base(n.b->dtype) == DFDB_STRING;
-    if (a_str || b_str) {   // string forms: column vs constant only
+    if (a_str || b_str) {   // string forms: a column against a constant, or two columns compared
       if (n.op == DFIR_CAST) {                           // parse(T, s): expr.cpp has checked that n.a is a column and T an integer type or Float64
         const int slot = slot_for(n.a->col);
         const int so = offsets_for(slot);
@@ -201,10 +201,17 @@ struct Compiler {
         else { nul = true; ins(H_ISMISSA); }           // the flag becomes the (never missing) Bool value
         return;
       }
+      if (n.a->op == DFIR_COL && n.b->op == DFIR_COL && a_str && b_str && n.op >= DFIR_EQ && n.op <= DFIR_GE) {   // s1 OP s2: Base.cmp on the bytes
+        const int sa = slot_for(n.a->col), sb = slot_for(n.b->col);                                               // (the same column twice is one slot, one offset array)
+        const int oa = offsets_for(sa), ob = offsets_for(sb);
+        IInstr& in = fresh(H_STRCMP2);
+        in.slot = sa; in.so = (uint8_t)oa; in.ta = (uint8_t)sb; in.tb = (uint8_t)ob; in.cmp = (uint8_t)n.op;
+        return;
+      }
       const Node *cn = nullptr, *sn = nullptr; bool flipped = false;
       if (n.a->op == DFIR_COL && n.b->op == DFIR_CONST_STR) { cn = n.a.get(); sn = n.b.get(); }
       else if (n.a->op == DFIR_CONST_STR && n.b->op == DFIR_COL && n.op >= DFIR_EQ && n.op <= DFIR_GE) { cn = n.b.get(); sn = n.a.get(); flipped = true; }
-      else fail(DFDB_ERR_UNSUPPORTED, "String expressions are limited to column-vs-constant comparisons, startswith, endswith, sizeof, ismissing");
+      else fail(DFDB_ERR_UNSUPPORTED, "String expressions are limited to comparisons of a column with a constant or with another column, startswith / endswith with a constant pattern, sizeof, ismissing, parse");
       const int slot = slot_for(cn->col);
       const int so = offsets_for(slot);
       IInstr& in = fresh(n.op == DFIR_STARTSWITH ? H_STRPRE : (n.op == DFIR_ENDSWITH ? H_STRSUF : H_STRCMP));

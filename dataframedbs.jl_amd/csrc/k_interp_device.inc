@@ -35,7 +35,8 @@ enum Handler : uint8_t {
   H_INSET, H_CAST,
   // handlers that set the missing flag of their result themselves (everything above: flag = union of the operands' flags)
   H_STRCMP, H_STRPRE, H_STRSUF, H_ISMISS, H_AND3, H_OR3, H_COALESCE, H_ISMISSA,
-  H_PARSE   // DFIR_CAST over a String column: parse(T, s), never missing
+  H_PARSE,  // DFIR_CAST over a String column: parse(T, s), never missing
+  H_STRCMP2 // String column OP String column: Base.cmp on the bytes; the second column's slot / offset-array index travel in ta / tb
 };
 constexpr int kFirstOwnFlag = H_STRCMP;
 enum BSrc : uint8_t { B_NONE = 0, B_IMM = 1, B_COL = 2, B_POP = 3 };
@@ -50,7 +51,7 @@ struct IInstr {                // host-side form (the Compiler fills these field
   int32_t slot;                // column slot (B_COL, string handlers, H_ISMISS)
   int32_t len;                 // pattern / set length
   uint64_t imm;                // immediate bits / pool offset
-  uint8_t ta, tb, rt, so;      // generic handlers (H_CAST, H_INSET): operand/result dtypes; so: offset-array index of the string column
+  uint8_t ta, tb, rt, so;      // generic handlers (H_CAST, H_INSET): operand/result dtypes; so: offset-array index of the string column (H_STRCMP2: ta / tb = the second column's slot / offset-array index)
   int32_t aslot;               // 1 + column slot loaded into A before the operation (fused leaf load), 0 = A is the running value
   uint64_t imm2;               // type_min of the compute type (typemin ÷ -1 check)
 };
@@ -186,6 +187,7 @@ DFDB_SLOW uint64_t slow_strop(int h_is_cmp, int suffix, const uint8_t* p, int le
   if (ok) { if (suffix) p += len - pl; for (int i = 0; i < pl && ok; i++) ok = p[i] == pat[i]; }
   return ok;
 }
+DFDB_SLOW uint64_t slow_strcmp2(const uint8_t* a, int la, const uint8_t* b, int lb, int op) { return cmp_result(op, str_cmp_dev(a, la, b, lb)); }
 DFDB_SLOW uint64_t slow_inset(uint64_t x, int ta, const uint64_t* set, int n, int tb) {
   bool hit = false;
   for (int i = 0; i < n && !hit; i++) hit = cmp3(x, ta, set[i], tb) == 0;

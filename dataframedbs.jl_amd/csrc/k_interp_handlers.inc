@@ -88,6 +88,19 @@
               Am[k] = (NUL && (COL_DTYPE(in_slot) & DFDB_NULLABLE)) ? (uint32_t)(sz < 0) : 0u;
             }
           } break;
+          case H_STRCMP2: {   // s1 OP s2 over two String columns: a missing size (-1) compares as length 0 and raises the flag
+            const int slot_b = w2 & 0xff, so_a = w2 >> 24, so_b = (w2 >> 8) & 0xff, op = in_cmp;
+            const IColDesc& ca = prog->cols[in_slot];
+            const IColDesc& cb = prog->cols[slot_b];
+#pragma unroll
+            EACH {
+              const int32_t za = ((const int32_t*)ca.data + base)[idx[k]], zb = ((const int32_t*)cb.data + base)[idx[k]];   // idx is clamped: always a valid row
+              const uint8_t* pa = ca.bytes + (int64_t)lds[((stack_levels + so_a) * kW + k) * kBlock + tid];
+              const uint8_t* pb = cb.bytes + (int64_t)lds[((stack_levels + so_b) * kW + k) * kBlock + tid];
+              A[k] = slow_strcmp2(pa, (inb[k] && za > 0) ? za : 0, pb, (inb[k] && zb > 0) ? zb : 0, op);
+              Am[k] = NUL ? (uint32_t)(((COL_DTYPE(in_slot) & DFDB_NULLABLE) && za < 0) || ((COL_DTYPE(slot_b) & DFDB_NULLABLE) && zb < 0)) : 0u;
+            }
+          } break;
           case H_PARSE: {   // parse(T, s): the value, or one of the outcomes of slow_parse reported with its row
             const IColDesc& c = prog->cols[in_slot];
             const int rt = (w2 >> 16) & 0xff, so = w2 >> 24;

@@ -336,6 +336,115 @@ void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_o
   else hipLaunchKernelGGL((k_str_match<false>), dim3(grid), dim3(kBlock), 0, s, sizes, tile_off, bytes, pat, pat_dev, mode, bitmap, tile_counts, nrows, ntiles);
 }
 
+// ---------------------------------------------------------------- K5b: s1 OP s2 over two String columns
+// Base.cmp(::String, ::String): memcmp over the common prefix, then the lengths, bytes unsigned.  One wave per 1024-row tile, K5's three phases per 8 steps:
+//   A  wave prefix sums of BOTH size streams -> the rows' byte offsets in the two arenas
+//   B  one 8-byte probe per side of every row the sizes do not settle (== / != with unequal sizes never read a byte; a missing or dead row neither)
+//   C  the first differing byte decides: both words masked to min(la, lb), compared byte-reversed as unsigned; equal words of longer strings walk on 8 bytes
+//      at a time; an equal common prefix leaves it to the lengths
+// The probes go to the arenas directly: parking both tiles' byte ranges in LDS first (2 x 8 KB per wave) was measured slower at config 4's
+// string lengths (profiles/str_pair.txt) and is not built.  Nothing read past a string's end is trusted: the words are masked.
+// -1 / 0 / 1 of two 8-byte words whose first m (1..8) bytes count: the lowest byte is the string's first, so the byte-reversed words order as memcmp does
+__device__ __forceinline__ int pair_cmp_word(uint64_t x, uint64_t y, int m) {
+  const uint64_t mk = m >= 8 ? ~0ull : ((1ull << (8 * m)) - 1ull);
+  x &= mk; y &= mk;
+  if (x == y) return 0;
+  return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
+}
+__device__ __forceinline__ bool pair_result(int op, int c) {
+  switch (op) {
+    case CMP_EQ: return c == 0; case CMP_NE: return c != 0; case CMP_LT: return c < 0;
+    case CMP_LE: return c <= 0; case CMP_GT: return c > 0; default: return c >= 0;
+  }
+}
+
+template <bool AND_EXISTING>
+__global__ __launch_bounds__(kBlock) void k_str_pair(const int32_t* __restrict__ sizes_a, const int64_t* __restrict__ toff_a, const uint8_t* __restrict__ bytes_a,
+                                                      const int32_t* __restrict__ sizes_b, const int64_t* __restrict__ toff_b, const uint8_t* __restrict__ bytes_b,
+                                                      int op, uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, int64_t nrows, int64_t ntiles) {
+  const int lane = lane_id();
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wid, nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  const bool ordered = op >= CMP_LT;                                    // (== / != are settled by unequal sizes alone)
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    uint32_t ex_lo = ~0u, ex_hi = ~0u;
+    if (AND_EXISTING) {
+      const uint64_t existing = lane < 16 ? bitmap[tile * 16 + lane] : 0ull;
+      if (__ballot(existing != 0) == 0) { if (lane == 0) tile_counts[tile] = 0; continue; }
+      ex_lo = (uint32_t)existing; ex_hi = (uint32_t)(existing >> 32);
+    }
+    const int64_t base = tile * kTile;
+    int32_t sa[16], sb[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int64_t i = base + j * 64 + lane;
+      sa[j] = i < nrows ? __builtin_nontemporal_load(sizes_a + i) : -2;
+      sb[j] = i < nrows ? __builtin_nontemporal_load(sizes_b + i) : -2;
+    }
+    const int64_t oa0 = toff_a[tile], ob0 = toff_b[tile];
+    const uint8_t* const ta = bytes_a + oa0;
+    const uint8_t* const tb = bytes_b + ob0;
+    uint64_t myword = 0;
+    uint32_t run_a = 0, run_b = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      uint32_t ra[8], rb[8]; uint64_t va[8], vb[8]; bool probe[8], alive[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {                                   // A
+        const uint32_t ca = clamp_size(sa[h * 8 + j]), cb = clamp_size(sb[h * 8 + j]);
+        const uint32_t ia = wave_incl_scan(ca), ib = wave_incl_scan(cb);
+        ra[j] = run_a + ia - ca; rb[j] = run_b + ib - cb;
+        run_a += __shfl(ia, 63, 64); run_b += __shfl(ib, 63, 64);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; j++) {                                   // B
+        const int32_t s0 = sa[h * 8 + j], s1 = sb[h * 8 + j];
+        const uint32_t la = clamp_size(s0), lb = clamp_size(s1);
+        // (-2: past the last row; -1: missing — a comparison with a missing side selects nothing: coalesce(term, false))
+        alive[j] = s0 >= 0 && s1 >= 0;
+        if (AND_EXISTING) {
+          const uint64_t ew = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)ex_hi, h * 8 + j) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)ex_lo, h * 8 + j);
+          alive[j] = alive[j] && ((ew >> lane) & 1ull);               // a row the stages before dropped reads nothing (a dead word: nobody probes)
+        }
+        probe[j] = alive[j] && la > 0 && lb > 0 && (ordered || la == lb);
+        va[j] = 0; vb[j] = 0;
+        // (an 8-byte probe reads up to 7 bytes past its string, so past the arena's last byte for the last row: every arena — resident, decoded, a chunk's —
+        // is allocated with 64 bytes of slack behind it (table.cpp), as K5's tail probe needs too)
+        if (probe[j]) { va[j] = load_u64_unaligned(ta + ra[j]); vb[j] = load_u64_unaligned(tb + rb[j]); }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; j++) {                                   // C
+        const int la = (int)clamp_size(sa[h * 8 + j]), lb = (int)clamp_size(sb[h * 8 + j]);
+        const int m = la < lb ? la : lb;
+        int c = la < lb ? -1 : (la > lb ? 1 : 0);                     // what the lengths say: it stands unless a byte of the common prefix differs
+        if (probe[j]) {
+          int d = pair_cmp_word(va[j], vb[j], m);
+          for (int k = 8; d == 0 && k < m; k += 8) {                  // longer than 8 bytes and equal so far
+            d = pair_cmp_word(load_u64_unaligned(ta + ra[j] + k), load_u64_unaligned(tb + rb[j] + k), m - k);
+          }
+          if (d) c = d;
+        }
+        const uint64_t mw = __ballot(alive[j] && pair_result(op, c));
+        if (lane == h * 8 + j) myword = mw;
+      }
+    }
+    uint32_t cnt = lane < 16 ? (uint32_t)__popcll(myword) : 0u;
+#pragma unroll
+    for (int d = 8; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if (lane < 16) __hip_atomic_store(&bitmap[tile * 16 + lane], myword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // write-through: see k_scan_cmp
+    if (lane == 0) tile_counts[tile] = cnt;
+  }
+}
+
+void launch_str_pair(hipStream_t s, const int32_t* sizes_a, const int64_t* toff_a, const uint8_t* bytes_a, const int32_t* sizes_b, const int64_t* toff_b,
+                     const uint8_t* bytes_b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing) {
+  const int64_t ntiles = (nrows + kTile - 1) / kTile;
+  if (ntiles == 0) return;
+  const int g = grid_for(ntiles, 2048);
+  if (and_existing) hipLaunchKernelGGL((k_str_pair<true>), dim3(g), dim3(kBlock), 0, s, sizes_a, toff_a, bytes_a, sizes_b, toff_b, bytes_b, op, bitmap, tile_counts, nrows, ntiles);
+  else hipLaunchKernelGGL((k_str_pair<false>), dim3(g), dim3(kBlock), 0, s, sizes_a, toff_a, bytes_a, sizes_b, toff_b, bytes_b, op, bitmap, tile_counts, nrows, ntiles);
+}
+
 // ---------------------------------------------------------------- K6
 // Both passes work on 1024-row tiles, one wave per tile.  Lane l owns a 16-bit slice of the tile's bitmap
 // (rows 16l..16l+15) and expands it into a 2-KB LDS list of selected in-tile positions (wave prefix-sum of

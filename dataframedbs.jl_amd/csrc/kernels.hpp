@@ -119,6 +119,9 @@ struct StrCapture { int32_t* sizes; uint8_t* bytes; uint32_t* tile_bytes; };   /
 void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const uint8_t* pat_host,
                       const uint8_t* pat_dev, int32_t patlen, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
                       bool and_existing, const StrCapture* cap = nullptr, uint32_t max_tile_bytes = 0);   // max_tile_bytes: Column::max_tile_bytes (0 = not known: probes straight from memory)
+// K5b: s1 OP s2 (CmpOp) over two String columns -> bitmap + counts; a row with a missing side (size -1) selects nothing
+void launch_str_pair(hipStream_t s, const int32_t* sizes_a, const int64_t* toff_a, const uint8_t* bytes_a, const int32_t* sizes_b, const int64_t* toff_b,
+                     const uint8_t* bytes_b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
 void launch_str_compact_captured(hipStream_t s, const StrCapture& cap, const uint64_t* prefix, const int64_t* tile_off, const uint64_t* out_tile_off,
                                  int32_t* out_sizes, uint8_t* out_bytes, int64_t nrows, int64_t out_rows, int64_t out_bytes_cap);
 // K6: selected sizes -> out sizes (+ per-ctile selected byte totals); then bytes
@@ -143,6 +146,9 @@ void launch_dict_encode(hipStream_t s, const int32_t* sizes, const int64_t* tile
 // lut: one bit per code, 1 = the row is selected; lut_words = ceil(entries / 32) <= 2048
 void launch_dict_scan(hipStream_t s, const uint16_t* codes, const uint32_t* lut, int32_t lut_words, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
                       bool and_existing);
+// two dictionary columns compared: rank_a / rank_b give every code its rank in the bytewise sorted union of the two dictionaries (equal strings, equal rank)
+void launch_dict_pair(hipStream_t s, const uint16_t* codes_a, const uint16_t* codes_b, const uint32_t* rank_a, int32_t n_a, const uint32_t* rank_b, int32_t n_b, int op,
+                      uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
 // the projection of a dictionary column over n selected rows whose codes K3 has compacted: sizes + per-1024-output-row byte totals, then the bytes
 void launch_dict_expand_sizes(hipStream_t s, const uint16_t* codes, int64_t n, const int32_t* dict_len, int32_t* out_sizes, uint32_t* out_tile_bytes);
 void launch_dict_expand_bytes(hipStream_t s, const uint16_t* codes, int64_t n, const int32_t* dict_len, const uint32_t* dict_off, const uint8_t* dict_bytes,

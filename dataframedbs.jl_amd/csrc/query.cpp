@@ -276,6 +276,26 @@ static void run_dict_scan(dfdb_query* q, const Column& col, const std::vector<ui
   LaunchTimer lt(ctx, "dict_scan");
   launch_dict_scan(s, col.dict_codes.as<uint16_t>(), lb.as<uint32_t>(), (int32_t)lut.size(), q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), q->t->nrows, have);
 }
+// s1 OP s2 over two dictionary columns: the two dictionaries merged on every run of the conjunct (not cached: at most 65535 entries each) — the union sorted bytewise (std::string orders as memcmp then length, bytes
+// unsigned: Base.cmp), equal strings one rank — and one rank table per column uploaded; the rows compare ranks (k_dict_pair)
+static void run_dict_pair(dfdb_query* q, const Column& ca, const Column& cb, int op, bool have) {
+  dfdb_ctx* ctx = q->t->ctx; hipStream_t s = ctx->stream;
+  const size_t na = (size_t)ca.dict_n, nb = (size_t)cb.dict_n;
+  std::vector<const std::string*> all; all.reserve(na + nb);
+  for (const std::string& e : ca.dict_host) all.push_back(&e);
+  for (const std::string& e : cb.dict_host) all.push_back(&e);
+  std::vector<uint32_t> order(na + nb), rank(na + nb);
+  for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return *all[x] < *all[y]; });
+  uint32_t r = 0;
+  for (size_t k = 0; k < order.size(); k++) { if (k && *all[order[k]] != *all[order[k - 1]]) r++; rank[order[k]] = r; }
+  DevBuf& rb = q->tmp_a; rb.ensure(rank.size() * 4 + 64);
+  HIP_CHECK(hipMemcpyAsync(rb.p, rank.data(), rank.size() * 4, hipMemcpyHostToDevice, s));
+  stream_wait(ctx);                                      // `rank` is pageable host memory
+  LaunchTimer lt(ctx, "dict_pair");
+  launch_dict_pair(s, ca.dict_codes.as<uint16_t>(), cb.dict_codes.as<uint16_t>(), rb.as<uint32_t>(), (int32_t)na, rb.as<uint32_t>() + na, (int32_t)nb, op,
+                   q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), q->t->nrows, have);
+}
 
 // predicate stage = AND of its conjuncts, each routed to the cheapest kernel that is exact for it
 static void run_predicate(dfdb_query* q, const Node& pred, bool first_stage, bool last_stage) {
@@ -337,6 +357,11 @@ static void run_predicate(dfdb_query* q, const Node& pred, bool first_stage, boo
     int o, mode; std::string pat; match_string_term(n, *t, o, mode, pat);
     return dict_entry_matches(e, mode, pat);
   };
+  // `s1 OP s2` over two String columns (and coalesce(s1 OP s2, false) over nullable ones): k_str_pair / k_dict_pair; ctx option "str_pair_kernel" = 0 leaves
+  // it to the interpreter's H_STRCMP2, which is the definition
+  struct PairTerm { int a, b, op; };
+  std::vector<PairTerm> pairs;
+  const bool pair_kernel = ctx_option(ctx, "str_pair_kernel", 1) != 0;
   struct MissTerm { const uint64_t* bits; bool negate; };
   std::vector<MissTerm> miss;
   struct CompTerm { ScanTerm tm; int ord; };
@@ -390,6 +415,10 @@ static void run_predicate(dfdb_query* q, const Node& pred, bool first_stage, boo
     else if (c->op == DFIR_COALESCE && c->a && c->b && c->b->op == DFIR_CONST && dt_base(c->b->dtype) == DFDB_BOOL && !dt_nullable(c->b->dtype) && c->b->cbits == 0 &&
              match_string_term(*c->a, *t, ord, mode, pat, true))
       strs.push_back(c->a.get());     // coalesce(s == "x", false) over a Union{String,Missing} column (the docs' real data set: index.md:264-272): K5's own answer, not the interpreter's
+    else if (PairTerm pt{}; pair_kernel && match_string_pair_term(*c, pt.a, pt.b, pt.op)) pairs.push_back(pt);
+    else if (PairTerm pt{}; pair_kernel && c->op == DFIR_COALESCE && c->a && c->b && c->b->op == DFIR_CONST && dt_base(c->b->dtype) == DFDB_BOOL && !dt_nullable(c->b->dtype) &&
+             c->b->cbits == 0 && match_string_pair_term(*c->a, pt.a, pt.b, pt.op, true))
+      pairs.push_back(pt);
     else generic.push_back(c);
   }
   if (terms.n) term_batches.push_back(terms);
@@ -426,7 +455,7 @@ static void run_predicate(dfdb_query* q, const Node& pred, bool first_stage, boo
     StrCapture capture{nullptr, nullptr, nullptr};
     // (every other kind of conjunct runs AFTER this launch and narrows the mask: the capture would keep rows the query drops — found by tests/test_gpu_fuzz.py)
     bool do_cap = mode != 0 && !str_nullable && q->hint_materialize && q->stages.size() == 1 && !have && generic.empty() && term_batches.empty() && or_batches.empty() && miss.empty() && comp_terms.empty() &&
-                  dict_luts.empty() && strs.size() == 1 && pat.size() <= 64;
+                  dict_luts.empty() && strs.size() == 1 && pairs.empty() && pat.size() <= 64;
     if (do_cap) {
       do_cap = false;
       for (const ProjCol& p : q->proj) if (p.expr->op == DFIR_COL && p.expr->col == ord) { do_cap = true; break; }
@@ -443,6 +472,16 @@ static void run_predicate(dfdb_query* q, const Node& pred, bool first_stage, boo
                      pb.as<uint8_t>(), (int32_t)pat.size(), mode, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), nrows, have,
                      do_cap ? &capture : nullptr, col.max_tile_bytes);
     if (do_cap) q->cap_str_col = ord;
+    have = true;
+  }
+  // (after the generic conjuncts like every other string scan: those see every row that reached the stage; a pair launch pins no constant and captures nothing)
+  for (const PairTerm& pt : pairs) {
+    const Column& ca = need_resident(t, pt.a);
+    const Column& cb = need_resident(t, pt.b);
+    if (ca.dict_n > 0 && cb.dict_n > 0) { run_dict_pair(q, ca, cb, pt.op, have); have = true; continue; }      // (a dictionary column is never nullable)
+    LaunchTimer lt(ctx, "str_pair");
+    launch_str_pair(s, ca.data.as<int32_t>(), (const int64_t*)ca.tile_off.p, ca.bytes.as<uint8_t>(), cb.data.as<int32_t>(), (const int64_t*)cb.tile_off.p,
+                    cb.bytes.as<uint8_t>(), pt.op, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), nrows, have);
     have = true;
   }
   for (const MissTerm& mt : miss) {

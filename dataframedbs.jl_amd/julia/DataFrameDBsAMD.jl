@@ -115,6 +115,8 @@ leaf(f) = (io = IOBuffer(); f(io); Tr(take!(io)))
 tr(x::Tr) = x
 tr(x) = leaf(io -> emit_const(io, x))
 cat2(a, b, op::UInt8) = Tr(vcat(tr(a).code, tr(b).code, op))
+# (two String columns compared — t.a .== t.b, .!=, .<, .<=, .>, .>= — are the Tr x Tr methods below like any other pair of columns: COL a; COL b; EQ..GE,
+#  Base.cmp on the bytes in the engine: include/dfdb_ir.h)
 for (f, op) in OPS
     fn = f
     @eval Base.$(nameof(fn))(a::Tr, b::Tr) = cat2(a, b, $op)

@@ -52,6 +52,10 @@ enum {
 #define DFIR_LE    0x23
 #define DFIR_GT    0x24
 #define DFIR_GE    0x25
+/* String OP String is Base.cmp(::String, ::String) on the bytes: memcmp over the common prefix, then the lengths, bytes unsigned ("\xff" > "\x7f", a proper
+ * prefix is smaller, an embedded NUL is a byte like any other).  Either operand may be a String column or a string constant (at least one is a column); with a
+ * Union{String,Missing} operand the result is Union{Bool,Missing}, missing where either side is — as a predicate it needs coalesce(s1 OP s2, false).
+ * startswith / endswith take a constant pattern only. */
 
 /* ---- logic: Bool (non-short-circuit, like `&` in selection.jl:46) or bitwise on ints ---- */
 #define DFIR_AND   0x30

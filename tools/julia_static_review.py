@@ -292,6 +292,9 @@ def main():
             "* **Untraceable closures.** `65 > a > 34` lowers to `(65 > a) && (a > 34)`; `&&` on a `Tr` raises `TypeError` inside `lower`'s `try`: the lowered-code walk above",
             "  takes over, and what it refuses is `Unsupported` → stock path, logged once.  Lowering happens before any device call (`with_query` lowers all stages first), so a",
             "  fallback leaves no device state behind.",
+            "* **Two String columns compared.** `t.a .== t.b` (`.!=`, `.<`, `.<=`, `.>`, `.>=`) reaches `lower` as a `BlockBroadcasting` of two `ColRef`s and leaves it through the",
+            "  generic `Tr` × `Tr` methods as `COL a; COL b; EQ…GE`, the bytes `include/dfdb_ir.h` defines as `Base.cmp` on the strings; over `Union{String,Missing}` columns the engine",
+            "  types it `Union{Bool,Missing}` and refuses it as a bare selection exactly where the stock path does.  Read, not run: no `julia` exists in either image.",
             "* **GC safety.** Every buffer whose pointer crosses the ABI is rooted: IR byte vectors, index vectors, name / code pointer arrays and the output",
             "  vectors are under `GC.@preserve` for the duration of the call; the engine copies what it keeps (`parse_ir`, `Stage::idx`), so nothing outlives the call.",
             "* **Ownership.** `with_query` frees its query in `finally`; tables and the group live in `DEV[]` until `reset!()`; `dfdb_group_query_shard` returns a borrowed handle.",
