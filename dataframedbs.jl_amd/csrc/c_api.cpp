@@ -484,7 +484,7 @@ int32_t dfdb_count_to(dfdb_query* q, int64_t* out, int32_t memkind) {
       return;
     }
     if (memkind != DFDB_MEM_DEVICE) { *out = query_count(q, -1); return; }
-    if (q->executed_stages != (int)q->stages.size() || q->bitmap_rows != q->t->nrows) query_execute(q, -1);
+    ensure_executed(q);
     const int64_t ntiles = ceil_div(q->t->nrows, kTileRows);
     HIP_CHECK(hipMemcpyAsync(out, q->prefix.as<uint64_t>() + ntiles, 8, hipMemcpyDeviceToDevice, q->t->ctx->stream));
   });

@@ -114,21 +114,28 @@ struct dfdb_query {
   // keeps the selected values of one projected 8-byte predicate column (per-tile compact, cap_buf) and that column's
   // projection becomes a contiguous copy instead of a gather
   bool hint_materialize = false;
-  int cap_col = -1;            // table ordinal captured by the last execution (-1: none)
-  int cap_col2 = -1;           // a second captured column (k_scan_terms EXTRA = 5: the term before the last), in cap_buf2
+  // What the last execution left behind for the projection side and for query_count (query.cpp run_plan writes it, project.cpp and unique.cpp read it):
+  // query_execute starts from `Left{}`.  It holds only while the bitmap reflects every stage: consumers ask reflects_all_stages(q) first.  The device
+  // buffers the entries speak of (cap_buf, cap_buf2, cap_str_*, agg_partials) are members of the query itself, so a reset frees nothing.
+  struct Left {
+    int cap_col = -1;            // table ordinal captured by the scan (k_scan_terms EX_CAPTURE / k_scan_cmp), in cap_buf (-1: none)
+    int cap_col2 = -1;           // a second captured column (EX_CAPTURE2: the term before the last), in cap_buf2
+    // a projected String column filtered by ONE short-pattern string term (K5 CAP): sizes per tile, bytes at the tile's arena offset, selected byte
+    // totals per tile in cap_str_sizes / cap_str_bytes / cap_str_tb
+    int cap_str_col = -1;
+    // a conjunct `strcol == "const"` of some stage holds for every finally selected row: the projection of that column is `const` repeated
+    int const_str_col = -1; std::string const_str;
+    int agg_col = -1;            // table ordinal whose per-tile sums / minima / maxima agg_partials holds (-1: none)
+    int agg_dtype = 0, agg_op = 0;
+    int decoded_col = -1;        // table ordinal whose resident LZ4 blocks the execution decoded on its way (decode_on_scan; -1: none)
+    std::vector<int> comp_scanned;   // compressed-only columns whose blocks it decoded inside its scan (their statuses are read with the count)
+  } left;
   dfdb::DevBuf cap_buf2;
-  int decoded_col = -1;        // table ordinal whose resident LZ4 blocks the last execution decoded on its way (decode_on_scan; -1: none)
-  std::vector<int> comp_scanned;   // compressed-only columns whose blocks the last execution decoded inside its scan (their statuses are read with the count)
   // compressed-only projection columns: the blocks that kept a row, decoded for THIS query's gathers at their natural offsets inside the span
   // [first such block, last such block] — the iterator owns its decode buffers, like the reference's (blocksiterator.jl:98-121)
   struct Arena { dfdb::DevBuf buf, blocks, status; int64_t first_row = 0; int64_t nblocks = 0; bool valid = false; const void* from = nullptr; };   // from: the blocks (Column::comp) it was decoded out of
   std::map<int, Arena> arenas;
   dfdb::DevBuf cap_buf;
-  // the same for a projected String column filtered by ONE short-pattern string term (K5 CAP): sizes per tile, bytes at the tile's arena
-  // offset, selected byte totals per tile
-  int cap_str_col = -1;
-  // a conjunct `strcol == "const"` of some stage holds for every finally selected row: the projection of that column is `const` repeated
-  int const_str_col = -1; std::string const_str;
   // dfdb_query_hint_aggregate: sum(projection column) WILL be asked for: when that column is a simple term of the launch that produces
   // the final mask, the scan adds up the selected values while it holds them (one partial per 1024-row tile) and dfdb_aggregate only
   // reduces the partials
@@ -138,8 +145,6 @@ struct dfdb_query {
   uint64_t err_row[3] = {~0ull, ~0ull, ~0ull};
   bool err_checking = false;   // inside error_is_reached's partial executions: errors are not raised
   uint64_t* proj_err = nullptr; // query_materialize: the first erroring row per kind of the projection column being computed lands here instead of raising
-  int agg_col = -1;            // table ordinal whose per-tile sums agg_partials holds (-1: none)
-  int agg_dtype = 0, agg_op = 0;
   dfdb::DevBuf agg_partials, agg_ones;
   int64_t agg_ones_tiles = -1;
   dfdb::DevBuf cap_str_sizes, cap_str_bytes, cap_str_tb;
@@ -164,6 +169,8 @@ struct dfdb_query {
 };
 
 namespace dfdb {
+// does the query's bitmap — and with it q->left — stand for the whole queue (not a partial execution, not invalidated since)?
+inline bool reflects_all_stages(const dfdb_query* q) { return q->executed_stages == (int)q->stages.size(); }
 // the three error words of an interpreter launch (k_interp_device.inc flag_error / flag_parse_error): the table row of word `kind`
 inline uint64_t err_word_row(int kind, uint64_t w) { return (kind == 2 && w != ~0ull) ? w >> 3 : w; }
 // which of the three words holds the smallest row (-1: none).  On the same row the parse word wins: the parsed leaf is evaluated before anything computed from
@@ -224,13 +231,14 @@ std::vector<int> groupreduce_check(const dfdb_query* q, const int32_t* key_cols,
 // n 64-bit results of one reducer -> the caller's values_i / values_f (either may be null) by the value column's kind
 void group_values_out(const uint64_t* bits, int64_t n, int kind, int64_t* vals_i, double* vals_f);
 void query_return_mask(dfdb_query* q);            // give a borrowed calibrated bitmap back to its column
-// query.cpp helpers that unique.cpp builds on
+// query.cpp / project.cpp helpers that project.cpp and unique.cpp build on
 size_t padded_words(int64_t nrows);               // bitmap words for n rows, padded so that K2's 64-word (4096-row) reads stay in bounds
 uint64_t splitmix64_host(uint64_t x);
 const Column& need_resident(dfdb_table* t, int ordinal);
 void selection_changed(dfdb_query* q);            // the bitmap changed outside query_execute: drop what was derived from it
 void scan_prefix(dfdb_query* q);                  // tile counts -> prefix
-void ensure_executed_checked(dfdb_query* q);
+void ensure_executed(dfdb_query* q);              // execute every stage unless the bitmap already reflects them
+void ensure_executed_checked(dfdb_query* q);      // the same for a consumer that hands results to the host: answers for a decode made on the way
 void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt);
 void set_string_tile_offsets(dfdb_ctx* ctx, Column& c);   // K4 over a resident string column
 bool read_file_range(const std::string& file, uint8_t* dst, int64_t lo, int64_t hi);   // table.cpp: parallel pread

@@ -438,6 +438,11 @@ bool match_string_term(const Node& n, const dfdb_table& t, int& ordinal, int& mo
   ordinal = coln->col; pat = cn->str; return true;
 }
 
+const Node* coalesce_false_arg(const Node& n) {
+  const bool is = n.op == DFIR_COALESCE && n.a && n.b && n.b->op == DFIR_CONST && dt_base(n.b->dtype) == DFDB_BOOL && !dt_nullable(n.b->dtype) && n.b->cbits == 0;
+  return is ? n.a.get() : nullptr;
+}
+
 // `s1 OP s2` over two String columns (the same column twice included).  allow_nullable: the caller evaluates `coalesce(term, false)`, which k_str_pair
 // gives over Union{String,Missing} operands (a row with a missing side selects nothing)
 bool match_string_pair_term(const Node& n, int& ord_a, int& ord_b, int& op, bool allow_nullable) {

@@ -40,6 +40,8 @@ bool match_column_transform(const Node* e, ScanTerm& out, const Node*& coln);   
 
 // `strcol == "x"`, `!=`, startswith, endswith  -> mode 0..3 (launch_str_match)
 bool match_string_term(const Node& n, const dfdb_table& t, int& ordinal, int& mode, std::string& pat, bool allow_nullable = false);
+// `coalesce(X, false)` with a non-nullable Bool constant false — the way a Union{Bool,Missing} term becomes a predicate — gives X; anything else null
+const Node* coalesce_false_arg(const Node& n);
 // `s1 OP s2` over two String columns -> their ordinals and the CmpOp (launch_str_pair / launch_dict_pair)
 bool match_string_pair_term(const Node& n, int& ord_a, int& ord_b, int& op, bool allow_nullable = false);
 

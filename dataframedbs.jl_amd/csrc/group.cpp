@@ -39,7 +39,7 @@
 #include <unordered_map>
 
 namespace dfdb {
-int query_aggregate_device(dfdb_query* q, int32_t op, int32_t i);   // query.cpp
+int query_aggregate_device(dfdb_query* q, int32_t op, int32_t i);   // project.cpp
 
 // ---------------------------------------------------------------- RCCL, resolved at run time
 struct Rccl {

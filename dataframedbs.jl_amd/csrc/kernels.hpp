@@ -54,6 +54,8 @@ void launch_read_probe(hipStream_t s, const void* col, int64_t nrows, uint64_t* 
 // extra = 1 (capture): the LAST term's 8-byte column at the finally selected rows, compacted per tile at extra_out[tile*1024 + rank];
 // extra = 2 (sum): one partial sum of that column per 1024-row tile in extra_out[tile] (double, or wrapping 64-bit integer).  AND only.
 // extra = 5 (capture two): the last term's column like extra = 1, and the 8-byte column of the term before it into extra_out2, same layout.
+// (3 / 4: per-tile minimum / maximum in extra_out[tile], like the sum.)  The host names these values; the kernels take the int.
+enum ScanExtra : int { EX_NONE = 0, EX_CAPTURE = 1, EX_SUM = 2, EX_MIN = 3, EX_MAX = 4, EX_CAPTURE2 = 5 };
 void launch_scan_terms(hipStream_t s, const ScanTerms& terms, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
                        bool and_existing, int extra = 0, void* extra_out = nullptr,
                        int pair = 1 /* ctx option "scan_pair": two plain 8-byte terms go to the pipelined k_scan_pair */, void* extra_out2 = nullptr);

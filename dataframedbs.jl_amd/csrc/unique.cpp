@@ -69,7 +69,7 @@ static int64_t dict_unique(dfdb_query* q, const Column& col, DevBuf* rank_of_cod
   HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
   launch_set_rows(s, drows.as<uint64_t>(), (int)ng, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>());
   scan_prefix(q);
-  selection_changed(q); q->cap_col = -1; q->cap_col2 = -1; q->cap_str_col = -1; q->agg_col = -1; q->const_str_col = -1;
+  selection_changed(q); q->left.cap_col = -1; q->left.cap_col2 = -1; q->left.cap_str_col = -1; q->left.agg_col = -1; q->left.const_str_col = -1;
   stream_wait(ctx);                                        // rows / rank are pageable host memory
   return ng;
 }
@@ -446,7 +446,7 @@ static void unique_impl_col(dfdb_query* q, const Column& col, UniqueTables* keep
     if (!dense) unique_hashed(q, col, cnt, T);
   }
   scan_prefix(q);
-  selection_changed(q); q->cap_col = -1; q->cap_col2 = -1; q->cap_str_col = -1; q->agg_col = -1;
+  selection_changed(q); q->left.cap_col = -1; q->left.cap_col2 = -1; q->left.cap_str_col = -1; q->left.agg_col = -1;
   stream_wait(ctx);                                        // the tables die here (or stay with the caller: groupreduce looks rows up in them)
   if (!keep) { RecycleScope rs; local = UniqueTables(); }
 }
