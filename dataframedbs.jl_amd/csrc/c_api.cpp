@@ -367,7 +367,7 @@ int32_t dfdb_query_new(dfdb_table* t, dfdb_query** out) {
     auto q = std::make_unique<dfdb_query>();
     q->t = t;
     for (size_t i = 0; i < t->cols.size(); i++) {   // full_table_projection: view.jl:43-48
-      auto n = std::make_unique<Node>(); n->op = DFIR_COL; n->col = (int)i; n->dtype = t->cols[i].dtype;
+      auto n = std::make_unique<Node>(); n->op = DFIR_COL; n->col = (int)i; n->dtype = t->cols[i].dtype; n->logical = t->cols[i].logical;
       q->proj.push_back(ProjCol{t->cols[i].name, std::move(n)});
     }
     t->queries.push_back(q.get());
@@ -435,6 +435,14 @@ int32_t dfdb_query_coltype(dfdb_query* q, int32_t i, int32_t* dtype) {
 }
 int32_t dfdb_expr_result_type(dfdb_table* t, const uint8_t* ir, size_t len, int32_t* dtype) {
   return guard([&] { NEED(t); NEED(ir); NEED(dtype); *dtype = parse_ir(*t, ir, len)->dtype; });
+}
+int32_t dfdb_expr_result_logical(dfdb_table* t, const uint8_t* ir, size_t len, char* buf, size_t cap) {
+  return guard([&] {
+    NEED(t); NEED(ir); NEED(buf);
+    const std::string lg = parse_ir(*t, ir, len)->logical;
+    if (lg.size() + 1 > cap) fail(DFDB_ERR_ARGUMENT, "ArgumentError: the buffer holds %zu bytes, the type name needs %zu", cap, lg.size() + 1);
+    memcpy(buf, lg.c_str(), lg.size() + 1);
+  });
 }
 int32_t dfdb_query_set_stage_base(dfdb_query* q, int32_t stage, int64_t survivors_before) {
   return guard([&] {

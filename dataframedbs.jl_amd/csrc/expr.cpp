@@ -13,7 +13,7 @@ void fail(int code, const char* fmt, ...) {
   throw Error(code, buf);
 }
 
-// a parse(T, s) row that gave no value (k_interp_device.inc PR_*): the three outcomes of include/dfdb_ir.h's DFIR_CAST contract that are not a value
+// a parse(T, s) or datetime19(s) row that gave no value (k_interp_device.inc PR_*): the outcomes of include/dfdb_ir.h's DFIR_CAST contracts that are not a value
 void throw_parse_error(uint64_t word, int64_t row_base) {
   const uint64_t row = (uint64_t)row_base + (word >> 3);
   char buf[256];
@@ -21,6 +21,10 @@ void throw_parse_error(uint64_t word, int64_t row_base) {
     case 1 /* PR_ARGUMENT */: snprintf(buf, sizeof buf, "ArgumentError: parse: the string is not a valid number of the target type (row %llu)", (unsigned long long)row); break;
     case 2 /* PR_OVERFLOW */: snprintf(buf, sizeof buf, "OverflowError: parse: the value does not fit the target type (row %llu)", (unsigned long long)row); break;
     case 3 /* PR_METHOD */: snprintf(buf, sizeof buf, "MethodError: no method matching parse(::Type{T}, ::Missing) (row %llu)", (unsigned long long)row); break;
+    case 5 /* PR_BOUNDS */:
+      snprintf(buf, sizeof buf, "BoundsError: datetime19: the string (or string(missing)) is shorter than 19 characters (row %llu)", (unsigned long long)row);
+      throw Error(DFDB_ERR_BOUNDS, buf, row);
+    case 6 /* PR_DATETIME */: snprintf(buf, sizeof buf, "ArgumentError: DateTime: month, day, hour, minute or second out of range (row %llu)", (unsigned long long)row); break;
     default /* PR_UNSUPPORTED */:
       snprintf(buf, sizeof buf, "parse: the string is outside what the device parser decides, the caller falls back to the Julia path (row %llu)", (unsigned long long)row);
       throw Error(DFDB_ERR_UNSUPPORTED, buf, row);
@@ -129,7 +133,7 @@ static int infer_base(int op, int ta, int tb) {
 
 NodePtr Node::clone() const {
   auto n = std::make_unique<Node>();
-  n->op = op; n->dtype = dtype; n->col = col; n->cbits = cbits; n->str = str; n->set = set; n->set_dtype = set_dtype; n->cast_to = cast_to;
+  n->op = op; n->dtype = dtype; n->col = col; n->cbits = cbits; n->str = str; n->set = set; n->set_dtype = set_dtype; n->cast_to = cast_to; n->logical = logical;
   if (a) n->a = a->clone();
   if (b) n->b = b->clone();
   return n;
@@ -164,7 +168,7 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
       case DFIR_COL: {
         need(4); uint32_t c; memcpy(&c, ir + pos, 4); pos += 4;
         if (c >= t.cols.size()) fail(DFDB_ERR_KEY, "KeyError: column ordinal %u out of range", c);
-        n->col = (int)c; n->dtype = t.cols[c].dtype; break;
+        n->col = (int)c; n->dtype = t.cols[c].dtype; n->logical = t.cols[c].logical; break;
       }
       case DFIR_CONST: {
         need(9); n->dtype = ir[pos]; memcpy(&n->cbits, ir + pos + 1, 8); pos += 9;
@@ -184,7 +188,12 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
         if (op == DFIR_CAST) { need(1); n->cast_to = ir[pos++]; }
         n->a = pop();
         if (n->a->op == DFIR_CONST_SET) fail(DFDB_ERR_ARGUMENT, "a set is only valid as the second argument of in");
-        if (op == DFIR_CAST && dt_base(n->a->dtype) == DFDB_STRING) {
+        if (op == DFIR_CAST && (n->cast_to & 0x40)) {
+          // the only target outside the dtypes: datetime19(s) over a String column leaf (include/dfdb_ir.h); Int64 milliseconds, never Union{DateTime,Missing}
+          if (n->cast_to != DFDB_CAST_DATETIME || n->a->op != DFIR_COL || dt_base(n->a->dtype) != DFDB_STRING)
+            fail(DFDB_ERR_UNSUPPORTED, "unsupported conversion %s -> cast target 0x%02x", dt_name(n->a->dtype).c_str(), n->cast_to);
+          n->dtype = DFDB_I64; n->logical = "DateTime";
+        } else if (op == DFIR_CAST && dt_base(n->a->dtype) == DFDB_STRING) {
           // parse(T, s) over a String column (include/dfdb_ir.h): an integer type or Float64, never Union{T,Missing} — parse(T, ::Missing) is a MethodError
           const int ct = n->cast_to;
           if (n->a->op != DFIR_COL || !(dt_isint(ct) || ct == DFDB_F64) || dt_nullable(ct))

@@ -18,6 +18,7 @@ struct Node {
   std::vector<uint64_t> set;     // DFIR_CONST_SET values (bit patterns of set_dtype)
   int32_t set_dtype = 0;
   int cast_to = 0;
+  std::string logical;           // the bits type the Int64 / UInt32 result stands for: "DateTime" for the DFDB_CAST_DATETIME cast, the column's for a DFIR_COL, else empty
   std::unique_ptr<Node> a, b;
   std::unique_ptr<Node> clone() const;
 };

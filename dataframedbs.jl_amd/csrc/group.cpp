@@ -205,11 +205,13 @@ static void for_shards(dfdb_group* g, const std::function<void(int)>& fn) {
 // every collective entry point starts with a clean slate: a note left behind by an operation that died on its way to the exchange (a failed RCCL
 // call, a caller's collective that returned an error) must not be taken for this operation's
 static void fresh(dfdb_group* g) { g->fault_key = ~0ull; g->fault_code = 0; g->fault_msg.clear(); }
-// (bits 4-7 of the code byte: which of parse's outcomes the row raised, k_interp_device.inc PR_*, 0 for everything else — the ranks that do not own the
+// (bits 4-7 of the code byte: which of parse's or datetime19's outcomes the row raised, k_interp_device.inc PR_*, 0 for everything else — the ranks that do not own the
 // failing shard rebuild the message from it)
 static uint64_t parse_reason_of(const Error& e) {
   if (e.row == ~0ull) return 0;
   const std::string m = e.what();
+  if (e.code == DFDB_ERR_ARGUMENT && m.rfind("ArgumentError: DateTime:", 0) == 0) return 6;
+  if (e.code == DFDB_ERR_BOUNDS) return m.rfind("BoundsError: datetime19", 0) == 0 ? 5 : 0;
   if (e.code == DFDB_ERR_ARGUMENT) return m.rfind("ArgumentError: parse", 0) == 0 ? 1 : (m.rfind("OverflowError: parse", 0) == 0 ? 2 : (m.rfind("MethodError: no method matching parse", 0) == 0 ? 3 : 0));
   return e.code == DFDB_ERR_UNSUPPORTED && m.rfind("parse:", 0) == 0 ? 4 : 0;
 }

@@ -187,10 +187,10 @@ struct Compiler {
     const int rt = dt_base(n.dtype);
     const bool a_str = n.a && dt_base(n.a->dtype) == DFDB_STRING, b_str = n.b && dt_base(n.b->dtype) == DFDB_STRING;
     if (a_str || b_str) {   // string forms: a column against a constant, or two columns compared
-      if (n.op == DFIR_CAST) {                           // parse(T, s): expr.cpp has checked that n.a is a column and T an integer type or Float64
+      if (n.op == DFIR_CAST) {                           // parse(T, s) / datetime19(s): expr.cpp has checked that n.a is a column and the target one of theirs
         const int slot = slot_for(n.a->col);
         const int so = offsets_for(slot);
-        IInstr& in = fresh(H_PARSE);
+        IInstr& in = fresh(n.cast_to == DFDB_CAST_DATETIME ? H_DATETIME : H_PARSE);      // (the target outside the dtypes: datetime19(s); rt is Int64 then)
         in.slot = slot; in.so = (uint8_t)so; in.rt = (uint8_t)dt_base(n.cast_to);
         return;
       }

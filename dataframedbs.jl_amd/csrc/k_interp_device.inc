@@ -36,7 +36,8 @@ enum Handler : uint8_t {
   // handlers that set the missing flag of their result themselves (everything above: flag = union of the operands' flags)
   H_STRCMP, H_STRPRE, H_STRSUF, H_ISMISS, H_AND3, H_OR3, H_COALESCE, H_ISMISSA,
   H_PARSE,  // DFIR_CAST over a String column: parse(T, s), never missing
-  H_STRCMP2 // String column OP String column: Base.cmp on the bytes; the second column's slot / offset-array index travel in ta / tb
+  H_STRCMP2,// String column OP String column: Base.cmp on the bytes; the second column's slot / offset-array index travel in ta / tb
+  H_DATETIME// DFIR_CAST with the target DFDB_CAST_DATETIME over a String column: datetime19(s), Int64 milliseconds, never missing
 };
 constexpr int kFirstOwnFlag = H_STRCMP;
 enum BSrc : uint8_t { B_NONE = 0, B_IMM = 1, B_COL = 2, B_POP = 3 };
@@ -158,14 +159,14 @@ DFDB_SLOW double slow_fmod(double a, double b) {
   if (v == 0.0) v = __builtin_copysign(v, b); else if ((v > 0.0) != (b > 0.0)) v += b;
   return v;
 }
-// err[0]: flags (1 DivideError, 2 InexactError, 4 a parse(T, s) that gives no value); the three 64-bit words at err + 2: the SMALLEST row each kind
+// err[0]: flags (1 DivideError, 2 InexactError, 4 a parse(T, s) or datetime19(s) that gives no value); the three 64-bit words at err + 2: the SMALLEST row each kind
 // happened on (the host decides from it whether the reference's block-by-block iteration would have reached that row at all: query.cpp error_is_reached).
 // The third word is `row << 3 | reason` (PR_*): the smallest row wins, and the host reads from the reason which error that row raises.
 __device__ __forceinline__ void flag_error(int* err, int code, uint64_t row) {
   atomicOr(err, code);
   atomicMin((unsigned long long*)(err + 2) + (code == 1 ? 0 : 1), (unsigned long long)row);
 }
-enum : int { PR_OK = 0, PR_ARGUMENT = 1, PR_OVERFLOW = 2, PR_METHOD = 3, PR_UNSUPPORTED = 4 };   // expr.cpp throw_parse_error reads these numbers
+enum : int { PR_OK = 0, PR_ARGUMENT = 1, PR_OVERFLOW = 2, PR_METHOD = 3, PR_UNSUPPORTED = 4, PR_BOUNDS = 5, PR_DATETIME = 6 };   // expr.cpp throw_parse_error reads these numbers
 __device__ __forceinline__ void flag_parse_error(int* err, int reason, uint64_t row) {
   atomicOr(err, 4);
   atomicMin((unsigned long long*)(err + 2) + 2, (unsigned long long)(row << 3 | (uint64_t)reason));
@@ -260,6 +261,47 @@ DFDB_SLOW uint64_t slow_parse(const uint8_t* p, int len, bool missing, int rt, b
   const uint64_t v = missing ? 0 : parse_bytes(p, len, rt, reason);
   if (reason) { flag_parse_error(err, reason, row); return 0; }
   return v;
+}
+// DFIR_CAST with the target DFDB_CAST_DATETIME = datetime19(s), the tutorial's fixed-position timestamp conversion (include/dfdb_ir.h states the contract
+// and numbers the rules).  This is the definition: the conversion kernel (k_datetime.hip) compiles this text, takes rules 4-6 from datetime_fields as they
+// are, and sends every row that is not a plain value through slow_datetime.
+// rules 4-6 over six fields that are all decimal digits (y 0..9999, the others 0..99): the value, or PR_DATETIME / PR_UNSUPPORTED
+__device__ __forceinline__ int64_t datetime_fields(int y, int m, int d, int h, int mi, int s, int& reason) {
+  const bool leap = (y & 3) == 0 && (y % 100 != 0 || y % 400 == 0);                 // proleptic Gregorian; year 0 is a leap year
+  const int dim = m == 2 ? 28 + (int)leap : 30 + ((m + (m >> 3)) & 1);               // 31 30 31 30 31 | 31 30 31 30 31 on either side of July / August
+  if (m < 1 || m > 12 || d < 1 || d > dim || h > 24) { reason = PR_DATETIME; return 0; }
+  if (h == 24) { reason = PR_UNSUPPORTED; return 0; }                                // (before minute and second: Julia versions differ on hour 24)
+  if (mi >= 60 || s >= 60) { reason = PR_DATETIME; return 0; }
+  const int z = m < 3 ? y - 1 : y;                                                   // -1 .. 9999
+  const int shift = (153 * (m < 3 ? m + 9 : m - 3) + 2) / 5;                         // Dates' SHIFT table: 306 337 0 31 61 92 122 153 184 214 245 275
+  const int zc = z + 400;                                                            // never negative, and 4, 100 and 400 divide 400: fld(z, k) = zc / k - 400 / k
+  const int days = d + shift + 365 * z + (zc / 4 - 100) - (zc / 100 - 4) + (zc / 400 - 1) - 306;
+  return 1000ll * ((int64_t)(s + 60 * mi + 3600 * h) + 86400ll * (int64_t)days);
+}
+__device__ __forceinline__ int datetime_digits(const uint8_t* p, int n, bool& ok) {   // n bytes as a decimal number; ok is cleared by a byte outside '0'..'9'
+  int v = 0;
+  for (int i = 0; i < n; i++) { const uint32_t d = (uint32_t)p[i] - '0'; ok = ok && d <= 9; v = v * 10 + (int)(d & 15u); }
+  return v;
+}
+__device__ __forceinline__ int64_t datetime_bytes(const uint8_t* p, int len, int& reason) {
+  const int m = len < 19 ? len : 19;
+  bool high = false;
+  for (int i = 0; i < m; i++) high = high || p[i] >= 0x80;
+  if (len < 19 && !high) { reason = PR_BOUNDS; return 0; }                           // rule 1: SubString raises before anything is parsed
+  if (high) { reason = PR_UNSUPPORTED; return 0; }                                   // rule 2: character indices are not byte indices
+  bool ok = true;
+  const int y = datetime_digits(p, 4, ok), mo = datetime_digits(p + 5, 2, ok), d = datetime_digits(p + 8, 2, ok);
+  const int h = datetime_digits(p + 11, 2, ok), mi = datetime_digits(p + 14, 2, ok), s = datetime_digits(p + 17, 2, ok);
+  if (!ok) { reason = PR_UNSUPPORTED; return 0; }                                    // rule 3: what parse(Int64, ...) makes of the field is Julia's to decide
+  return datetime_fields(y, mo, d, h, mi, s, reason);
+}
+// alive: the row is inside the table and selected; only such a row is converted, and only it can raise.  A missing row is string(missing): 7 ASCII bytes, rule 1
+DFDB_SLOW uint64_t slow_datetime(const uint8_t* p, int len, bool missing, bool alive, int* err, uint64_t row) {
+  if (!alive) return 0;
+  int reason = missing ? PR_BOUNDS : PR_OK;
+  const int64_t v = missing ? 0 : datetime_bytes(p, len, reason);
+  if (reason) { flag_parse_error(err, reason, row); return 0; }
+  return (uint64_t)v;
 }
 // DFIR_CAST = Julia's T(x) / convert(T, x): exact or InexactError (Int8(300), Int8(300.0), UInt64(-1), UInt64(-1.0), Int64(typemax(UInt64)),
 // Bool(2) all throw; Float32(x) rounds).  The implicit promotions of arithmetic wrap instead (`a % T`, Base int.jl) and do not come here.

@@ -113,6 +113,18 @@
               Am[k] = 0;                                                    // parse(T, ::Missing) is a MethodError, not missing
             }
           } break;
+          case H_DATETIME: {   // datetime19(s): the value, or one of the outcomes of slow_datetime reported with its row
+            const IColDesc& c = prog->cols[in_slot];
+            const int so = w2 >> 24;
+#pragma unroll
+            EACH {
+              const int32_t sz = ((const int32_t*)c.data + base)[idx[k]];   // idx is clamped: always a valid row
+              const bool alive = inb[k] && ((maskword[k] >> lane) & 1ull);
+              const uint8_t* p = c.bytes + (int64_t)lds[((stack_levels + so) * kW + k) * kBlock + tid];
+              A[k] = slow_datetime(p, sz > 0 ? sz : 0, sz < 0, alive, err, (uint64_t)(base + idx[k]));
+              Am[k] = 0;                                                    // string(missing) is a string: a BoundsError, not missing
+            }
+          } break;
           case H_ISMISS: {
             const uint64_t* m = prog->cols[in_slot].missing;
 #pragma unroll

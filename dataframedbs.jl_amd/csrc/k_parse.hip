@@ -10,6 +10,14 @@
 // (SWAR); anything else — whitespace, other characters, 20 digits, a value outside the target, a missing row, Float64 — is slow_parse's, over the same LDS
 // bytes.  A tile whose bytes do not fit the stage is parsed straight from the arena.  Row j * 64 + lane belongs to lane `lane`, so the results of 64
 // neighbouring rows leave in one coalesced store.  SELECTED: only the rows of the bitmap, written compacted at prefix[tile] + rank (as k_gather does).
+//
+// k_str_datetime, below it, is the same kernel for `CAST DFDB_CAST_DATETIME (COL s)`, datetime19.(s): the tutorial's timestamp column to a DateTime column.
+// Its definition is the interpreter's H_DATETIME (slow_datetime / datetime_bytes / datetime_fields).  The tutorial's rows are 23 bytes
+// ("yyyy-mm-dd HH:MM:SS UTC"), so its stage is 24576 bytes per wave: 1024 x 23 + the lead (<= 15) + the 16 bytes of the last piece = 23583 at most.  With
+// the 64 spare bytes that is 24640 bytes per wave, 49280 per two-wave workgroup, and floor(163840 / 49280) = 3 workgroups = 6 waves on a CU's 160 KiB of
+// LDS (k_str_parse: 4 workgroups; one wave per workgroup would give the same 6 waves).  A lane reads its row's first 24 bytes as three shifted 8-byte LDS
+// words, checks n >= 19, ASCII and the 14 digit positions with masks, forms the six fields pairwise in registers and takes rules 4-6 from datetime_fields;
+// a row that is not a plain value (missing, short, non-digit, out of range, hour 24, non-ASCII) is slow_datetime's, over the same LDS bytes.
 #include "device_utils.hpp"
 #include "engine.hpp"
 
@@ -130,6 +138,118 @@ __global__ __launch_bounds__(kParseWaves * 64) void k_str_parse(const int32_t* _
       run_sel += (uint32_t)__popcll(mw);
     }
   }
+}
+
+constexpr uint32_t kDtStage = 24576;         // 1024 rows x 23 bytes + the lead + the last 16-byte piece (23583), see the head of the file
+constexpr int kDtPieces = 6;                 // 16-byte loads per lane in flight while staging: 6 KB per wave and round, four rounds for a full stage
+
+// n >= 19 ASCII bytes whose 14 field bytes are digits and whose fields are a DateTime Julia accepts: true and the value; anything else is the slow path's
+__device__ __forceinline__ bool datetime_fast(uint64_t x0, uint64_t x1, uint64_t x2, int len, uint64_t& out) {
+  constexpr uint64_t kM0 = 0x00FFFF00FFFFFFFFull, kM1 = 0xFFFF00FFFF00FFFFull, kM2 = 0x0000000000FFFF00ull, kZ = 0x3030303030303030ull;   // the field bytes of bytes 0-7, 8-15, 16-23
+  const bool ascii = (((x0 | x1) & 0x8080808080808080ull) | (x2 & 0x0000000000808080ull)) == 0;                                         // bytes 0 .. 18
+  const uint64_t f0 = (x0 & kM0) | (kZ & ~kM0), f1 = (x1 & kM1) | (kZ & ~kM1), f2 = (x2 & kM2) | (kZ & ~kM2);                           // '0' wherever a byte is ignored
+  const bool digits = swar_digits8(f0) && swar_digits8(f1) && swar_digits8(f2);
+  uint64_t v0 = f0 - kZ, v1 = f1 - kZ, v2 = f2 - kZ;
+  v0 = v0 * 10 + (v0 >> 8); v1 = v1 * 10 + (v1 >> 8); v2 = v2 * 10 + (v2 >> 8);                                                         // byte i: digit i * 10 + digit i + 1 (at most 99)
+  const int y = (int)(v0 & 0xff) * 100 + (int)((v0 >> 16) & 0xff), mo = (int)((v0 >> 40) & 0xff);
+  const int d = (int)(v1 & 0xff), h = (int)((v1 >> 24) & 0xff), mi = (int)((v1 >> 48) & 0xff), s = (int)((v2 >> 8) & 0xff);
+  int reason = PR_OK;
+  out = (uint64_t)datetime_fields(digits ? y : 1, digits ? mo : 1, digits ? d : 1, digits ? h : 0, digits ? mi : 0, digits ? s : 0, reason);
+  return len >= 19 && ascii && digits && reason == PR_OK;
+}
+
+template <bool SELECTED>
+__global__ __launch_bounds__(kParseWaves * 64) void k_str_datetime(const int32_t* __restrict__ sizes, const int64_t* __restrict__ tile_off, const uint8_t* __restrict__ bytes,
+                                                                   const uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ prefix, uint64_t* __restrict__ out,
+                                                                   int64_t out_cap, int64_t nrows, int64_t ntiles, int* __restrict__ err) {
+  __shared__ __attribute__((aligned(16))) uint64_t stage_sh[kParseWaves][kDtStage / 8 + 8];
+  const int lane = lane_id();
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  uint64_t* const stage = stage_sh[wid];
+  const int64_t wave = (int64_t)blockIdx.x * kParseWaves + wid, nwaves = (int64_t)gridDim.x * kParseWaves;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    uint32_t m_lo = ~0u, m_hi = ~0u;
+    if (SELECTED) {
+      const uint64_t w = lane < 16 ? bitmap[tile * 16 + lane] : 0ull;
+      if (__ballot(w != 0) == 0) continue;                               // nothing selected in this tile
+      m_lo = (uint32_t)w; m_hi = (uint32_t)(w >> 32);
+    }
+    const int64_t base = tile * kTile;
+    int32_t sz[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? __builtin_nontemporal_load(sizes + i) : 0; }
+    const int64_t o0 = tile_off[tile], a0 = o0 & ~15ll;
+    const uint32_t lead = (uint32_t)(o0 - a0);
+    const int64_t span = tile_off[tile + 1] - a0 + 16;                   // (up to 31 bytes past the tile's end: every arena is allocated with 64 bytes of slack)
+    const bool staged = span <= (int64_t)kDtStage;                      // wave-uniform
+    if (staged) {
+      const uint32_t need = (uint32_t)span, lastc = (need - 1u) & ~15u;
+      // (a piece past the range's end is the range's last piece once more, loaded and stored by several lanes alike: no predication, no divergence)
+      for (uint32_t c0 = 0; c0 < need; c0 += kDtPieces * 1024u) {
+        u32x4 piece[kDtPieces];
+#pragma unroll
+        for (int i = 0; i < kDtPieces; i++) { uint32_t c = c0 + (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; piece[i] = __builtin_nontemporal_load((const u32x4*)(bytes + a0 + c)); }
+#pragma unroll
+        for (int i = 0; i < kDtPieces; i++) { uint32_t c = c0 + (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; *(u32x4*)((uint8_t*)stage + c) = piece[i]; }
+      }
+      wave_lds_fence();
+    }
+    uint32_t run = 0, run_sel = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int32_t s0 = sz[j];
+      const uint32_t len = s0 > 0 ? (uint32_t)s0 : 0u;
+      const uint32_t incl = wave_incl_scan(len);
+      const uint32_t rel = run + incl - len;
+      run += __shfl(incl, 63, 64);
+      const uint64_t mw = SELECTED ? ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)m_hi, j) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)m_lo, j)) : ~0ull;
+      const int64_t row = base + j * 64 + lane;
+      const bool alive = row < nrows && ((mw >> lane) & 1ull);
+      uint64_t v = 0;
+      bool done = false;
+      if (staged && alive && s0 >= 19) {
+        // (the four words stay inside the stage: a row starts at least its own length before `need - 16`, and the array has 64 bytes to spare)
+        const uint32_t p = lead + rel, a = p >> 3, sh = (p & 7u) * 8u;
+        const uint64_t w0 = stage[a], w1 = stage[a + 1], w2 = stage[a + 2], w3 = stage[a + 3];
+        const uint64_t x0 = sh ? (w0 >> sh) | (w1 << (64u - sh)) : w0, x1 = sh ? (w1 >> sh) | (w2 << (64u - sh)) : w1, x2 = sh ? (w2 >> sh) | (w3 << (64u - sh)) : w2;
+        done = datetime_fast(x0, x1, x2, (int)len, v);
+      }
+      if (!done) {
+        const uint8_t* p = staged ? (const uint8_t*)stage + lead + rel : bytes + o0 + rel;
+        v = slow_datetime(p, (int)len, s0 < 0, alive, err, (uint64_t)row);
+      }
+      const int64_t o = SELECTED ? (int64_t)prefix[tile] + run_sel + (int64_t)__popcll(mw & ((1ull << lane) - 1ull)) : row;
+      if (alive && o < out_cap) out[o] = v;
+      run_sel += (uint32_t)__popcll(mw);
+    }
+  }
+}
+
+// `e` is CAST DFDB_CAST_DATETIME (COL s) over a resident String column: the selected rows' DateTime values (Int64 milliseconds), compacted, into dst
+void run_str_datetime(dfdb_query* q, const Node& e, void* dst, int64_t cap) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const Column& c = t->cols[(size_t)e.a->col];
+  if (!c.resident) fail(DFDB_ERR_ARGUMENT, "column %s is not resident on the device (dfdb_table_load it first)", c.name.c_str());
+  const int64_t ntiles = ceil_div(t->nrows, kTile);
+  if (ntiles == 0) return;
+  DevBuf& db = q->tmp_a; db.ensure(64);
+  struct { int flags, pad; uint64_t row[3]; } init{0, 0, {~0ull, ~0ull, ~0ull}};      // the interpreter's error block
+  HIP_CHECK(hipMemcpyAsync(db.p, &init, sizeof init, hipMemcpyHostToDevice, s));
+  stream_wait(ctx);
+  int* derr = (int*)db.p;
+  const bool all = cap == t->nrows;                                     // every row is selected: no bitmap, no compaction
+  int64_t grid = ceil_div(ntiles, kParseWaves); if (grid > 32768) grid = 32768;
+  {
+    LaunchTimer lt(ctx, "str_datetime");
+#define DFDB_DATETIME_LAUNCH(SEL)                                                                                                                                           \
+    hipLaunchKernelGGL((k_str_datetime<SEL>), dim3((unsigned)grid), dim3(kParseWaves * 64), 0, s, c.data.as<int32_t>(), (const int64_t*)c.tile_off.p, c.bytes.as<uint8_t>(), \
+                       q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), (uint64_t*)dst, cap, t->nrows, ntiles, derr)
+    if (all) DFDB_DATETIME_LAUNCH(false); else DFDB_DATETIME_LAUNCH(true);
+#undef DFDB_DATETIME_LAUNCH
+    HIP_CHECK(hipGetLastError());
+  }
+  settle_launch_errors(q, 1, derr);
 }
 
 // `e` is CAST T (COL s) over a resident String column: the selected rows' values, compacted, into dst (cap elements)

@@ -15,6 +15,7 @@ namespace dfdb {
 // launchers living in k_interp.hip / k_parse.hip that take engine-level descriptions
 void run_interp_project(dfdb_query* q, const Node& expr, void* dst, int64_t cap, uint8_t* missing_dst);
 void run_str_parse(dfdb_query* q, const Node& expr, void* dst, int64_t cap);   // k_parse.hip
+void run_str_datetime(dfdb_query* q, const Node& expr, void* dst, int64_t cap);   // k_parse.hip
 
 
 // ---------------------------------------------------------------- compressed-only projection columns
@@ -223,7 +224,8 @@ void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
         launch_gather_transform(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), gather_source(q, tcol->col), dt_base(sc.dtype), tf, dst, t->nrows, cnt);
       }
     } else if (e.op == DFIR_CAST && e.a->op == DFIR_COL && dt_base(e.a->dtype) == DFDB_STRING && ctx_option(ctx, "parse_kernel", 1) != 0)
-      run_str_parse(q, e, dst, cnt);                        // exactly parse.(T, s): the conversion kernel (k_parse.hip); "parse_kernel" = 0: the interpreter
+      // exactly parse.(T, s) or datetime19.(s): the conversion kernels (k_parse.hip); "parse_kernel" = 0: the interpreter
+      e.cast_to == DFDB_CAST_DATETIME ? run_str_datetime(q, e, dst, cnt) : run_str_parse(q, e, dst, cnt);
     else
     run_interp_project(q, e, dst, cnt, mdst);
     if (!dev) {
@@ -275,7 +277,7 @@ void table_add_from_query(dfdb_table* dst, const char* name, dfdb_query* q, int3
     fail(DFDB_ERR_ARGUMENT, "ArgumentError: column has %lld rows but the table has %lld", (long long)cnt, (long long)dst->nrows);
   dfdb_ctx* ctx = dst->ctx; hipStream_t s = ctx->stream;
   Column c; c.name = name; c.dtype = e.dtype; c.id = 1; c.nrows = cnt;
-  if (e.op == DFIR_COL) c.logical = q->t->cols[(size_t)e.col].logical;   // a projected Date / DateTime / Char column keeps its type
+  c.logical = e.op == DFIR_COL ? q->t->cols[(size_t)e.col].logical : e.logical;   // a projected Date / DateTime / Char column keeps its type; datetime19(s) is a DateTime
   for (auto& o : dst->cols) c.id = std::max(c.id, o.id + 1);
   dfdb_outcol o{}; o.memkind = DFDB_MEM_DEVICE;
   DevBuf flags;

@@ -54,7 +54,7 @@ SYMBOLS = [
     "dfdb_table_add_generated", "dfdb_table_decode_resident", "dfdb_table_decode_status", "dfdb_table_resident_bytes", "dfdb_table_compress_column", "dfdb_table_read_probe", "dfdb_table_build_dictionary", "dfdb_table_set_row_base", "dfdb_table_set_logical_type", "dfdb_table_column_stats", "dfdb_table_add_from_query", "dfdb_table_save", "dfdb_table_save_column", "dfdb_query_hint_materialize", "dfdb_query_hint_aggregate", "dfdb_query_unique", "dfdb_query_groupreduce", "dfdb_query_groupreduce_fetch", "dfdb_query_groupreduce_n", "dfdb_query_groupreduce_n_fetch", "dfdb_stream_open", "dfdb_stream_next", "dfdb_stream_stats", "dfdb_stream_read_stats", "dfdb_stream_close",
     "dfdb_query_new", "dfdb_query_free", "dfdb_query_add_range", "dfdb_query_add_indices", "dfdb_query_add_integer",
     "dfdb_query_add_predicate", "dfdb_query_nstages", "dfdb_query_set_projection", "dfdb_query_ncols", "dfdb_query_coltype",
-    "dfdb_expr_result_type", "dfdb_query_set_stage_base", "dfdb_query_count_prefix",
+    "dfdb_expr_result_type", "dfdb_expr_result_logical", "dfdb_query_set_stage_base", "dfdb_query_count_prefix",
     "dfdb_query_execute", "dfdb_query_reset", "dfdb_count", "dfdb_count_to", "dfdb_select_bitmap", "dfdb_select_indices", "dfdb_result_string_bytes",
     "dfdb_materialize", "dfdb_aggregate", "dfdb_query_prepare", "dfdb_table_unload", "dfdb_query_read_stats",
     # multi-GPU groups (block-range shards + RCCL)
@@ -131,6 +131,7 @@ def load() -> C.CDLL:
         lib.dfdb_query_add_integer.argtypes = [C.c_void_p, C.c_int64]
         lib.dfdb_query_add_predicate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.dfdb_expr_result_type.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p]
+        lib.dfdb_expr_result_logical.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         lib.dfdb_query_set_stage_base.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
         lib.dfdb_select_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         lib.dfdb_count_to.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]

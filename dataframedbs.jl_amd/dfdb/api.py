@@ -296,7 +296,10 @@ class DFTable:
 
     def add_column(self, name: str, values, dtype: Optional[int] = None, logical: Optional[str] = None):
         """values: numpy array (datetime64 / timedelta64 become Date / DateTime / Time columns), masked array, or a list of str / None.
-        logical="Char" with 1-character strings makes a Char column."""
+        logical="Char" with 1-character strings makes a Char column.  A lazy DFColumn (or one-column DFView) is add_column!(table, name, lazy_col):
+        add_column_from."""
+        if isinstance(values, (DFColumn, DFView)):
+            return self.add_column_from(name, values)
         L = N.load()
         if logical == "Char":
             values = np.array([ir.julia_char(c) for c in values], np.uint32)
@@ -458,6 +461,13 @@ class DFTable:
         b = e.to_ir()
         N.check(N.load().dfdb_expr_result_type(self._h, b, len(b), C.byref(dt)))
         return dt.value
+
+    def expr_logical(self, e: ir.Expr) -> str:
+        """the bits type the result dtype stands for: "DateTime" for datetime19(s), a plain column's own, "" otherwise (dfdb_expr_result_logical)"""
+        buf = C.create_string_buffer(32)
+        b = e.to_ir()
+        N.check(N.load().dfdb_expr_result_logical(self._h, b, len(b), buf, len(buf)))
+        return buf.value.decode()
 
     def __eq__(self, o):     # table.jl:18-21: path + column metas only (quirk Q12)
         return isinstance(o, DFTable) and (self is o or (self.path != "" and self.path == o.path and self.columns_meta() == o.columns_meta()))
@@ -973,9 +983,16 @@ def materialize(v: Union[DFView, DFTable, "DFColumn"]):
 
 
 def _logicals(v: DFView) -> List[str]:
-    """per projection column: the bits type a plain column stands for ("" for ordinary dtypes and computed columns)"""
-    metas = v.table.columns_meta()
-    return [metas[e.payload].logical if e.op == ir.COL else "" for e in v.projection.cols.values()]
+    """per projection column: the bits type its values stand for, as the engine types the expression ("" for ordinary dtypes)"""
+    metas = None
+    out = []
+    for e in v.projection.cols.values():
+        if e.op == ir.COL:
+            metas = metas or v.table.columns_meta()
+            out.append(metas[e.payload].logical)
+        else:
+            out.append(v.table.expr_logical(e))
+    return out
 
 
 def _to_user(c, logical: str = ""):
@@ -1147,6 +1164,10 @@ float64 = _fn_bc(ir.float64)
 def parse(dtype: int, c):
     """parse.(T, col): a String column (or Expr) as an integer type or Float64; the result type is the engine's (dfdb_expr_result_type): T, never missing."""
     return _fn_bc(lambda e: ir.parse(dtype, e))(c)
+
+
+datetime19 = _fn_bc(ir.datetime19)
+datetime19.__doc__ = """datetime19.(col): a String column of "yyyy-mm-dd HH:MM:SS…" timestamps as a DateTime column (ir.datetime19)."""
 
 
 def coalesce(c, default):

@@ -21,6 +21,7 @@ import numpy as np
 I8, I16, I32, I64, U8, U16, U32, U64, F32, F64, BOOL, STRING = range(1, 13)
 NULLABLE = 0x80
 DTYPE_MASK = 0x3F
+CAST_DATETIME = 0x40 | I64     # not a dtype: the cast target of datetime19 (DFDB_CAST_DATETIME)
 
 _NP_TO_DT = {
     np.dtype("int8"): I8, np.dtype("int16"): I16, np.dtype("int32"): I32, np.dtype("int64"): I64,
@@ -313,6 +314,12 @@ def float64(a) -> Expr: return cast(a, F64)
 def parse(dtype: int, a) -> Expr:
     """`parse.(T, s)` over a String column: the same bytes as `cast(s, T)` — DFIR_CAST applied to a String operand means parse (include/dfdb_ir.h)."""
     return cast(a, dtype)
+
+
+def datetime19(a) -> Expr:
+    """The tutorial's timestamp conversion over a String column: the fields at the fixed positions of "yyyy-mm-dd HH:MM:SS", everything else ignored;
+    Int64 milliseconds with the logical type DateTime (include/dfdb_ir.h: DFIR_CAST with the target DFDB_CAST_DATETIME)."""
+    return cast(a, CAST_DATETIME)
 
 
 def trace(fn, leaves: Sequence[Expr]) -> Expr:

@@ -53,7 +53,8 @@ function check(rc::Int32)
     msg = last_error()
     # InexactError (Int8(300), UInt64(-1) inside a predicate) travels as DFDB_ERR_ARGUMENT with its name in the text (include/dfdb.h)
     rc == 1 && startswith(msg, "InexactError") && throw(InexactError(:convert, Integer, msg))
-    # parse.(T, s): the engine names the error Base raises (include/dfdb_ir.h, DFIR_CAST over a String column)
+    # parse.(T, s) and datetime19.(s): the engine names the error Base raises (include/dfdb_ir.h, DFIR_CAST over a String column); datetime19's
+    # "ArgumentError: DateTime: ..." is the ArgumentError below, its "BoundsError: ..." arrives as status 5
     rc == 1 && startswith(msg, "OverflowError") && throw(OverflowError(msg))
     rc == 1 && startswith(msg, "MethodError") && throw(MethodError(parse, (Number, missing)))
     rc == 1 && throw(ArgumentError(msg))
@@ -136,6 +137,20 @@ Base.convert(::Type{Float64}, a::Tr) = Float64(a)
 const PARSE_TARGETS = (Int8, Int16, Int32, Int64, UInt8, UInt16, UInt32, UInt64, Float64)
 emit_parse(::Type{T}, a::Tr) where {T} = T in PARSE_TARGETS ? Tr(vcat(a.code, 0x50, DT[T])) : throw(Unsupported("parse($(T), s) is outside the IR"))
 Base.parse(::Type{T}, a::Tr) where {T} = emit_parse(T, a)
+# datetime19.(s): the timestamp conversion of the reference's tutorial as a NAMED function, so that a column of "yyyy-mm-dd HH:MM:SS..." strings becomes a
+# DateTime column on the device: DFIR_CAST with the target DFDB_CAST_DATETIME (include/dfdb_ir.h has the rule table).  The method for real values is the
+# definition the device follows (fixed character ranges of string(s), each parsed as Int64, handed to DateTime), so the fallback path and the device agree
+# by definition; what the device does not decide (hour 24, " 1", non-ASCII) comes back as status 7 and this method answers.  An opaque closure that does
+# the same thing is still outside the IR and falls back.
+const CAST_DATETIME = 0x40 | DT[Int64]
+const DATETIME19_RANGES = (1:4, 6:7, 9:10, 12:13, 15:16, 18:19)
+function datetime19(s)
+    str = string(s)                                            # (string(missing) == "missing": a BoundsError below, as in the tutorial)
+    fields = map(r -> parse(Int64, SubString(str, r)), DATETIME19_RANGES)
+    Dates.DateTime(fields...)
+end
+datetime19(a::Tr) = Tr(vcat(a.code, 0x50, CAST_DATETIME))
+export datetime19
 
 # BlockBroadcasting / ColRef -> Tr.  `ord` maps a column Symbol to its 0-based table ordinal.
 lower(c::ColRef, ord) = leaf(io -> emit_col(io, ord[c.name]))

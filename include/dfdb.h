@@ -297,6 +297,10 @@ int32_t dfdb_query_ncols(dfdb_query* q, int32_t* n);                 /* ncol(v):
 int32_t dfdb_query_coltype(dfdb_query* q, int32_t i, int32_t* dtype); /* coltype: projection.jl:80-81 */
 /* result dtype of an expression over the table's columns: Base._return_type in BlockBroadcasting (broadcast.jl:13) */
 int32_t dfdb_expr_result_type(dfdb_table* t, const uint8_t* ir, size_t len, int32_t* dtype);
+/* the bits type that result dtype stands for, the other half of Base._return_type (broadcast.jl:13): "DateTime" for datetime19(s) (include/dfdb_ir.h,
+ * DFDB_CAST_DATETIME), the column's own ("Date", "DateTime", "Time", "Char") for a plain `COL k`, "" for everything else.  NUL-terminated into buf;
+ * DFDB_ERR_ARGUMENT when cap is too small */
+int32_t dfdb_expr_result_logical(dfdb_table* t, const uint8_t* ir, size_t len, char* buf, size_t cap);
 
 /* multi-GPU: survivors of the stages before range stage `stage` that live on lower ranks
  * (exclusive scan of per-shard counts); default 0 */

@@ -23,7 +23,10 @@ enum {
   DFDB_U8 = 5, DFDB_U16 = 6, DFDB_U32 = 7, DFDB_U64 = 8,
   DFDB_F32 = 9, DFDB_F64 = 10, DFDB_BOOL = 11, DFDB_STRING = 12,
   DFDB_DTYPE_MASK = 0x3f,
-  DFDB_NULLABLE = 0x80 /* Union{T,Missing}: "Missing(T)" on disk */
+  DFDB_NULLABLE = 0x80, /* Union{T,Missing}: "Missing(T)" on disk */
+  /* not a dtype: a cast TARGET, valid only as the payload byte of DFIR_CAST over a String column leaf (see DFIR_CAST below).  Bit 0x40 lies outside
+   * DFDB_DTYPE_MASK, so `target & DFDB_DTYPE_MASK` reads Int64, the representation of the result: every consumer tests for the whole byte first. */
+  DFDB_CAST_DATETIME = 0x40 | DFDB_I64
 };
 
 /* ---- leaves ---- */
@@ -92,5 +95,26 @@ enum {
  * fast path; "35.79" is 3579 / 1e2, "-0.0" keeps its sign).  Longer significands, larger exponents, Inf, NaN, hex floats, "1f3", underscores: UNSUPPORTED
  * with the smallest such row; empty, all-whitespace and missing rows raise as for integers.
  * Which rows count as evaluated, and which of several errors is reported (the smallest row among all kinds), follows the rule of DivideError / InexactError. */
+/* DFIR_CAST with the target DFDB_CAST_DATETIME over a String or Union{String,Missing} COLUMN leaf (the same operand restriction as parse; over any other
+ * operand the target is DFDB_ERR_UNSUPPORTED) is the timestamp conversion of the reference's tutorial (docs/src/index.md:417-435), spelled datetime19(s)
+ * by the front ends: string(s) is cut at the fixed character ranges 1:4, 6:7, 9:10, 12:13, 15:16, 18:19, each piece is parsed as Int64, and the six numbers
+ * are the arguments of DateTime(y, m, d, h, mi, s).  Result: DFDB_I64, never nullable, logical type "DateTime" (milliseconds, Dates' Rata Die epoch).
+ * This is the tutorial's function and NOT DateTime(s): the bytes at 4, 7, 10, 13, 16 and everything from byte 19 on are ignored, so
+ * "2019-10-01 00:00:00 UTC", "2019-10-01T00:00:00" and "2019-10-01T00:00:00.123" all give 2019-10-01T00:00:00.  With n = sizeof(s), every evaluated row
+ * is settled by the FIRST rule that applies:
+ *   1. the row is missing (string(missing) is 7 bytes long), or n < 19 and the bytes [0, n) are all < 0x80: status DFDB_ERR_BOUNDS, the message starts
+ *      with "BoundsError:" (SubString raises before any field is parsed);
+ *   2. a byte >= 0x80 among the first min(n, 19): DFDB_ERR_UNSUPPORTED (character indices stop being byte indices: Julia decides);
+ *   3. one of the 14 field bytes (0-3, 5-6, 8-9, 11-12, 14-15, 17-18) is not '0'..'9': DFDB_ERR_UNSUPPORTED (parse(Int64, " 1"), "+1" and "0x1f" are
+ *      values in Julia and "1a" is not; the device does not sort them out);
+ *   4. month outside 1:12; else day outside 1:daysinmonth(y, m) (proleptic Gregorian leap rule, year 0000 is a leap year); else hour 25..99; else, the
+ *      hour being below 24, minute >= 60; else second >= 60: status DFDB_ERR_ARGUMENT, the message starts with "ArgumentError: DateTime:";
+ *   5. hour == 24 (month and day in range), whatever minute and second are: DFDB_ERR_UNSUPPORTED (Julia versions differ on DateTime(y, m, d, 24));
+ *   6. otherwise the value 1000 * (s + 60 mi + 3600 h + 86400 * totaldays(y, m, d)), totaldays as in Dates with floored divisions:
+ *        z = m < 3 ? y - 1 : y;  totaldays = d + SHIFT[m] + 365 z + fld(z, 4) - fld(z, 100) + fld(z, 400) - 306
+ *        SHIFT = (306, 337, 0, 31, 61, 92, 122, 153, 184, 214, 245, 275)
+ *      ("1970-01-01 00:00:00" is 62135683200000; "0000-01-01 00:00:00" is -31536000000, totaldays = -365).
+ * Which rows count as evaluated, and which of several raising rows is reported, is parse's rule: the smallest row of any kind, only selected rows, and the
+ * converted leaf wins a tie on its row. */
 
 #endif
