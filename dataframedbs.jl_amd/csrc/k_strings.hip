@@ -162,7 +162,7 @@ __device__ __forceinline__ void store_small(uint8_t* d, uint64_t v, uint32_t len
 // addresses, a few active lanes per instruction, every 128-byte line of the arena fetched anyway because a line holds ~20 strings — and the pass ran at 0.58-0.64
 // of the HBM peak.  Now the wave streams the tile's byte range [tile_off[t], tile_off[t+1]) with aligned 16-byte loads that are in flight together with the sixteen
 // size loads, parks it in 8 KB of LDS, and the probes read there.  A tile whose strings do not fit (mean length above ~7) keeps the direct probes.
-constexpr uint32_t kStageBytes = 8192;
+constexpr uint32_t kStageBytes = kStrStageBytes;
 __device__ __forceinline__ uint64_t lds_probe(const uint32_t* st, uint32_t off) {     // 8 bytes at byte offset `off` of the staged range
   const uint32_t i = off >> 2, sh = off & 3u;
   const uint32_t w0 = st[i], w1 = st[i + 1], w2 = st[i + 2];
@@ -323,9 +323,9 @@ void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_o
   Pattern pat; memset(&pat, 0, sizeof pat); pat.len = patlen;
   if (patlen > 0 && patlen <= 64) memcpy(pat.w, pat_host, (size_t)patlen);   // short patterns ride in the kernel arguments
   const int grid = grid_for(ntiles, 2048);
-  if (patlen <= 64) {
-    // every tile of the column fits the 8 KB a wave stages (+ 15 bytes below the tile's first, + 16 behind its last): the bytes come through LDS
-    const bool stage = patlen > 0 && max_tile_bytes > 0 && max_tile_bytes + 48u <= kStageBytes;
+  const StrMatchForm form = str_match_form(patlen, max_tile_bytes);
+  if (form != STR_MATCH_LONG) {
+    const bool stage = form == STR_MATCH_STAGED;      // every tile of the column fits the 8 KB a wave stages: the bytes come through LDS
 #define DFDB_SHORT(M) do { if (stage) launch_short<M, true>(s, grid, and_existing, sizes, tile_off, bytes, pat, pat_dev, bitmap, tile_counts, nrows, ntiles, cap); \
                            else launch_short<M, false>(s, grid, and_existing, sizes, tile_off, bytes, pat, pat_dev, bitmap, tile_counts, nrows, ntiles, cap); } while (0)
     switch (mode) { case 0: DFDB_SHORT(0); break; case 1: DFDB_SHORT(1); break; case 2: DFDB_SHORT(2); break; default: DFDB_SHORT(3); break; }

@@ -118,6 +118,14 @@ void launch_str_tile_bytes(hipStream_t s, const int32_t* sizes, uint32_t* tile_b
 // K5: s OP "const" (EQ / NE / STARTSWITH / ENDSWITH) -> bitmap + counts.  mode: 0 EQ, 1 NE, 2 STARTSWITH, 3 ENDSWITH
 // pat_host: the pattern in host memory (<= 64 bytes travel as kernel arguments); pat_dev: device copy for longer ones
 struct StrCapture { int32_t* sizes; uint8_t* bytes; uint32_t* tile_bytes; };   // K5 CAP outputs (see k_str_match_short)
+// the form launch_str_match takes: patterns above 64 bytes run k_str_match; shorter ones k_str_match_short, staged through LDS when every tile of the column
+// fits the 8 KB a wave stages (+ 15 bytes below the tile's first, + 16 behind its last), with direct probes otherwise (and for the empty pattern, which reads nothing)
+constexpr uint32_t kStrStageBytes = 8192;
+enum StrMatchForm { STR_MATCH_STAGED = 0, STR_MATCH_DIRECT = 1, STR_MATCH_LONG = 2 };
+inline StrMatchForm str_match_form(int32_t patlen, uint32_t max_tile_bytes) {
+  if (patlen > 64) return STR_MATCH_LONG;
+  return patlen > 0 && max_tile_bytes > 0 && max_tile_bytes + 48u <= kStrStageBytes ? STR_MATCH_STAGED : STR_MATCH_DIRECT;
+}
 void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const uint8_t* pat_host,
                       const uint8_t* pat_dev, int32_t patlen, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
                       bool and_existing, const StrCapture* cap = nullptr, uint32_t max_tile_bytes = 0);   // max_tile_bytes: Column::max_tile_bytes (0 = not known: probes straight from memory)

@@ -529,6 +529,10 @@ static void run_str_step(dfdb_query* q, const StrStep& st, bool have, bool do_ca
     capture = StrCapture{q->cap_str_sizes.as<int32_t>(), q->cap_str_bytes.as<uint8_t>(), q->cap_str_tb.as<uint32_t>()};
   }
   LaunchTimer lt(ctx, "str_match");
+  if (ctx->profiling) {                 // which form launch_str_match takes, for the tests that must meet every one (tests/test_gpu_str_match.py)
+    const StrMatchForm form = str_match_form((int32_t)pat.size(), col.max_tile_bytes);
+    prof_note(ctx, form == STR_MATCH_STAGED ? "str_match.staged" : form == STR_MATCH_DIRECT ? "str_match.direct" : "str_match.long");
+  }
   launch_str_match(s, col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(), (const uint8_t*)pat.data(),
                    pb.as<uint8_t>(), (int32_t)pat.size(), st.mode, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), nrows, have,
                    do_cap ? &capture : nullptr, col.max_tile_bytes);
