@@ -10,6 +10,7 @@
 //   K6 gather sizes + bytes of selected rows replaces getindex(a, r) (:136-157)
 #include "device_utils.hpp"
 #include "kernels.hpp"
+#include "str_tile.hpp"
 #include <cstring>
 
 namespace dfdb {
@@ -24,8 +25,6 @@ static inline int grid_for(int64_t nunits, int cap = 4096) {
   if (b < 1) b = 1;
   return (int)b;
 }
-
-__device__ __forceinline__ uint32_t clamp_size(int32_t s) { return s > 0 ? (uint32_t)s : 0u; }
 
 // ---------------------------------------------------------------- K4
 __global__ __launch_bounds__(kBlock) void k_str_tile_bytes(const int32_t* __restrict__ sizes, uint32_t* __restrict__ tile_bytes, int64_t nrows,
@@ -91,8 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_str_match(const int32_t* __restrict_
     int64_t run = tile_off[tile];
     const int64_t base = tile * kTile;
     int32_t sz[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? sizes[i] : 0; }
+    tile_sizes<false>(sizes, base, nrows, lane, 0, sz);
     uint64_t myword = 0;
 #pragma unroll
     for (int j = 0; j < 16; j++) {
@@ -117,11 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_str_match(const int32_t* __restrict_
       if (lane == j) myword = m;
     }
     if (AND_EXISTING) myword &= existing;
-    uint32_t cnt = lane < 16 ? (uint32_t)__popcll(myword) : 0u;
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-    if (lane < 16) bitmap[tile * 16 + lane] = myword;
-    if (lane == 0) tile_counts[tile] = cnt;
+    tile_close<false>(bitmap, tile_counts, tile, lane, myword);
   }
 }
 
@@ -189,7 +183,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CAP ? 2 
   const uint64_t want2 = patw1 & mask2;
   __shared__ __attribute__((aligned(16))) uint32_t stage_sh[STAGE ? kWavesPerBlock : 1][STAGE ? kStageBytes / 4 + 8 : 4];
   uint32_t* const stage = stage_sh[STAGE ? (threadIdx.x >> 6) : 0];
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
     uint64_t existing = ~0ull;
     if (AND_EXISTING) {
@@ -199,22 +192,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CAP ? 2 
     const uint8_t* tb = bytes + tile_off[tile];
     const int64_t base = tile * kTile;
     int32_t sz[16];
-#pragma unroll
+#pragma unroll   // (not tile_sizes: through the helper the compiler allocates this kernel's registers differently, and the occupancy of several forms moves)
     for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? __builtin_nontemporal_load(sizes + i) : -2; }
-    // the tile's byte range (from the 16-byte boundary below it to 31 bytes past its end: a probe may read 15 bytes behind its string, and every arena is
-    // allocated with 64 bytes of slack), eight 1-KB pieces at most, all in flight with the size loads
-    const int64_t o0 = tile_off[tile], a0 = o0 & ~15ll;
-    const uint32_t lead = (uint32_t)(o0 - a0), need = (uint32_t)(tile_off[tile + 1] - a0) + 16u;
-    if (STAGE) {                                                       // (the launcher has checked that the column's largest tile fits)
-      // (a piece past the range's end is the range's last piece once more, loaded and stored by several lanes alike: no predication, no divergence)
-      const uint32_t lastc = (need - 1u) & ~15u;
-      u32x4 piece[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) { uint32_t c = (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; piece[i] = __builtin_nontemporal_load((const u32x4*)(bytes + a0 + c)); }
-#pragma unroll
-      for (int i = 0; i < 8; i++) { uint32_t c = (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; *(u32x4*)(stage + (c >> 2)) = piece[i]; }
-      wave_lds_fence();
-    }
+    // the tile's byte range, eight 1-KB pieces at most, all in flight with the size loads (the launcher has checked that the column's largest tile fits)
+    const TileSpan ts = tile_span(tile_off, tile);
+    if (STAGE) stage_tile<8, kStageBytes>(bytes, ts, (uint8_t*)stage, lane);
     uint64_t myword = 0;
     uint32_t run = 0;
     uint32_t cap_n = 0, cap_b = 0;                                    // CAP: selected rows / bytes of this tile so far
@@ -238,8 +220,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CAP ? 2 
         if (cand[j] && plen > 0) {
           const uint32_t po = rel[j] + (uint32_t)(MODE == 3 ? len - plen : 0);
           if (STAGE) {
-            v[j] = lds_probe(stage, lead + po);
-            if (LONG) v2[j] = lds_probe(stage, lead + po + 8u);
+            v[j] = lds_probe(stage, ts.lead + po);
+            if (LONG) v2[j] = lds_probe(stage, ts.lead + po + 8u);
           } else {
             v[j] = load_u64_unaligned(tb + po);
             if (LONG) v2[j] = load_u64_unaligned(tb + po + 8);         // bytes 8..15 of the compared span ride along
@@ -281,11 +263,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CAP ? 2 
     }
     if (CAP && lane == 0) sel_tile_bytes[tile] = cap_b;
     if (AND_EXISTING) myword &= existing;
-    uint32_t cnt = lane < 16 ? (uint32_t)__popcll(myword) : 0u;
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-    if (lane < 16) __hip_atomic_store(&bitmap[tile * 16 + lane], myword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // write-through: see k_scan_cmp
-    if (lane == 0) tile_counts[tile] = cnt;
+    tile_close<true>(bitmap, tile_counts, tile, lane, myword);       // write-through: see k_scan_cmp
   }
 }
 
@@ -375,12 +353,8 @@ __global__ __launch_bounds__(kBlock) void k_str_pair(const int32_t* __restrict__
     }
     const int64_t base = tile * kTile;
     int32_t sa[16], sb[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const int64_t i = base + j * 64 + lane;
-      sa[j] = i < nrows ? __builtin_nontemporal_load(sizes_a + i) : -2;
-      sb[j] = i < nrows ? __builtin_nontemporal_load(sizes_b + i) : -2;
-    }
+    tile_sizes(sizes_a, base, nrows, lane, -2, sa);
+    tile_sizes(sizes_b, base, nrows, lane, -2, sb);
     const int64_t oa0 = toff_a[tile], ob0 = toff_b[tile];
     const uint8_t* const ta = bytes_a + oa0;
     const uint8_t* const tb = bytes_b + ob0;
@@ -403,8 +377,7 @@ __global__ __launch_bounds__(kBlock) void k_str_pair(const int32_t* __restrict__
         // (-2: past the last row; -1: missing — a comparison with a missing side selects nothing: coalesce(term, false))
         alive[j] = s0 >= 0 && s1 >= 0;
         if (AND_EXISTING) {
-          const uint64_t ew = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)ex_hi, h * 8 + j) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)ex_lo, h * 8 + j);
-          alive[j] = alive[j] && ((ew >> lane) & 1ull);               // a row the stages before dropped reads nothing (a dead word: nobody probes)
+          alive[j] = alive[j] && ((tile_word(ex_lo, ex_hi, h * 8 + j) >> lane) & 1ull);   // a row the stages before dropped reads nothing (a dead word: nobody probes)
         }
         probe[j] = alive[j] && la > 0 && lb > 0 && (ordered || la == lb);
         va[j] = 0; vb[j] = 0;
@@ -428,11 +401,7 @@ __global__ __launch_bounds__(kBlock) void k_str_pair(const int32_t* __restrict__
         if (lane == h * 8 + j) myword = mw;
       }
     }
-    uint32_t cnt = lane < 16 ? (uint32_t)__popcll(myword) : 0u;
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-    if (lane < 16) __hip_atomic_store(&bitmap[tile * 16 + lane], myword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // write-through: see k_scan_cmp
-    if (lane == 0) tile_counts[tile] = cnt;
+    tile_close<true>(bitmap, tile_counts, tile, lane, myword);         // write-through: see k_scan_cmp
   }
 }
 

@@ -14,8 +14,7 @@ namespace dfdb {
 
 // launchers living in k_interp.hip / k_parse.hip that take engine-level descriptions
 void run_interp_project(dfdb_query* q, const Node& expr, void* dst, int64_t cap, uint8_t* missing_dst);
-void run_str_parse(dfdb_query* q, const Node& expr, void* dst, int64_t cap);   // k_parse.hip
-void run_str_datetime(dfdb_query* q, const Node& expr, void* dst, int64_t cap);   // k_parse.hip
+void run_str_convert(dfdb_query* q, const Node& expr, void* dst, int64_t cap);   // k_parse.hip
 
 
 // ---------------------------------------------------------------- compressed-only projection columns
@@ -224,8 +223,8 @@ void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
         launch_gather_transform(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), gather_source(q, tcol->col), dt_base(sc.dtype), tf, dst, t->nrows, cnt);
       }
     } else if (e.op == DFIR_CAST && e.a->op == DFIR_COL && dt_base(e.a->dtype) == DFDB_STRING && ctx_option(ctx, "parse_kernel", 1) != 0)
-      // exactly parse.(T, s) or datetime19.(s): the conversion kernels (k_parse.hip); "parse_kernel" = 0: the interpreter
-      e.cast_to == DFDB_CAST_DATETIME ? run_str_datetime(q, e, dst, cnt) : run_str_parse(q, e, dst, cnt);
+      // exactly parse.(T, s) or datetime19.(s): the conversion kernel (k_parse.hip); "parse_kernel" = 0: the interpreter
+      run_str_convert(q, e, dst, cnt);
     else
     run_interp_project(q, e, dst, cnt, mdst);
     if (!dev) {

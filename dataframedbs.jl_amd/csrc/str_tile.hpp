@@ -1,0 +1,71 @@
+// str_tile.hpp — the walk of a String column one wave per 1024-row tile, as k_parse.hip and k_strings.hip share it.  Device only.
+//
+// A tile is sixteen steps of 64 rows: row j * 64 + lane of the tile belongs to lane `lane` in step j, step j makes word j of the tile's bitmap, and lanes
+// 0..15 hold the tile's sixteen words.  The layout of a String column (sizes, one arena, one byte offset per tile) is at the head of k_strings.hip.
+#pragma once
+#include "common.hpp"
+#include "device_utils.hpp"
+
+namespace dfdb {
+
+static_assert(kTileRows == 16 * 64 && kTileWords == 16, "a tile is sixteen 64-row steps of one wave, one bitmap word per step");
+
+__device__ __forceinline__ uint32_t clamp_size(int32_t s) { return s > 0 ? (uint32_t)s : 0u; }   // the bytes of a row (a missing row, -1, has none)
+
+// the sizes of the tile's rows, sixteen loads in flight; `past` stands for the rows behind the column's last.  NT: the loads are non-temporal
+template <bool NT = true>
+__device__ __forceinline__ void tile_sizes(const int32_t* sizes, int64_t base, int64_t nrows, int lane, int32_t past, int32_t (&sz)[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? (NT ? __builtin_nontemporal_load(sizes + i) : sizes[i]) : past; }
+}
+
+// The tile's byte range in the arena, from the 16-byte boundary below its first byte: o0 = tile_off[tile], a0 the boundary, lead = o0 - a0 (0..15), and
+// span = the bytes from a0 that the staging moves: up to 31 bytes past the tile's end (a reader may look 15 bytes behind its string, and every arena is
+// allocated with 64 bytes of slack).  Wave-uniform.
+struct TileSpan { int64_t o0, a0, span; uint32_t lead; };
+__device__ __forceinline__ TileSpan tile_span(const int64_t* tile_off, int64_t tile) {
+  const int64_t o0 = tile_off[tile], a0 = o0 & ~15ll;
+  return TileSpan{o0, a0, tile_off[tile + 1] - a0 + 16, (uint32_t)(o0 - a0)};
+}
+
+// Park ts.span bytes from bytes + ts.a0 in this wave's LDS stage (16-byte aligned, CAP bytes and room for what the caller reads past a row), as aligned
+// 16-byte loads, PIECES per lane in flight per round.  The caller has seen to ts.span <= CAP; where CAP is one round's bytes there is no loop.
+template <int PIECES, uint32_t CAP>
+__device__ __forceinline__ void stage_tile(const uint8_t* bytes, const TileSpan& ts, uint8_t* stage, int lane) {
+  static_assert(CAP % 16 == 0, "the last piece of a range of CAP bytes ends inside the stage only if CAP is a whole number of pieces");
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  constexpr uint32_t kRound = (uint32_t)PIECES * 1024u;
+  const uint32_t need = (uint32_t)ts.span, lastc = (need - 1u) & ~15u;
+  // (a piece past the range's end is the range's last piece once more, loaded and stored by several lanes alike: no predication, no divergence)
+  uint32_t c0 = 0;
+  do {
+    u32x4 piece[PIECES];
+#pragma unroll
+    for (int i = 0; i < PIECES; i++) { uint32_t c = c0 + (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; piece[i] = __builtin_nontemporal_load((const u32x4*)(bytes + ts.a0 + c)); }
+#pragma unroll
+    for (int i = 0; i < PIECES; i++) { uint32_t c = c0 + (uint32_t)i * 1024u + (uint32_t)lane * 16u; c = c < lastc ? c : lastc; *(u32x4*)(stage + c) = piece[i]; }
+    c0 += kRound;
+  } while (CAP > kRound && c0 < need);
+  wave_lds_fence();
+}
+
+// word j (wave-uniform) of a tile's bitmap, from the halves that lanes 0..15 hold of their words
+__device__ __forceinline__ uint64_t tile_word(uint32_t lo, uint32_t hi, int j) {
+  return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, j) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)lo, j);
+}
+
+// the end of a tile that made a bitmap: its words (lane j < 16 holds word j) and its selected-row count go out.  WRITE_THROUGH: the words leave in relaxed
+// system-scope atomic stores (see k_scan_cmp), else in plain stores
+template <bool WRITE_THROUGH>
+__device__ __forceinline__ void tile_close(uint64_t* bitmap, uint32_t* tile_counts, int64_t tile, int lane, uint64_t myword) {
+  uint32_t cnt = lane < 16 ? (uint32_t)__popcll(myword) : 0u;
+#pragma unroll
+  for (int d = 8; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+  if (lane < 16) {
+    if (WRITE_THROUGH) __hip_atomic_store(&bitmap[tile * 16 + lane], myword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else bitmap[tile * 16 + lane] = myword;
+  }
+  if (lane == 0) tile_counts[tile] = cnt;
+}
+
+}  // namespace dfdb

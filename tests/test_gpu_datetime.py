@@ -165,6 +165,60 @@ def test_a_tile_too_large_for_the_stage_equals_the_staged_path(dfdb_mod, ctx):
         project_raw(dfdb_mod, table_of(dfdb_mod, long))
 
 
+DT_STAGE = 24576             # the bytes a wave stages for datetime19 (csrc/k_parse.hip: DatetimeConv::kStage)
+
+
+def stage_edge_rows(rng, lead, tile1_bytes):
+    """2048 rows, the two tiles of one workgroup: valid 23-byte rows, the second row of each tile with ignored bytes behind it up to the tile's byte total.
+    Tile 0 holds the most bytes that are staged and leave tile 1 `lead` bytes above a 16-byte boundary; tile 1 holds tile1_bytes"""
+    strs = []
+    for total in (DT_STAGE - 16 - (16 - lead) % 16, tile1_bytes):
+        rows = [stamp(rng, 23) for _ in range(1024)]
+        assert total >= 23 * 1024
+        rows[1] += "." * (total - 23 * 1024)
+        strs += rows
+    return strs
+
+
+@pytest.mark.parametrize("mode", [(1, 0)], ids=["kernel"], indirect=True)
+@pytest.mark.parametrize("lead", [0, 15])
+def test_the_largest_staged_tile_and_the_smallest_direct_tile(dfdb_mod, ctx, mode, lead):
+    """a tile `lead` bytes above a 16-byte boundary is staged exactly when its bytes + lead + 16 <= DT_STAGE: the tile that fills the stage to its last byte,
+    and the same tile one byte longer, which is converted from the arena.  Both tiles belong to one workgroup, whose two stages are neighbours in LDS.  Then
+    the same columns with an invalid row in each tile (the last row of tile 1 ends where the stage ends): values, error kind and error row"""
+    from dfdb import ir
+    staged = stage_edge_rows(np.random.default_rng(2300 + lead), lead, DT_STAGE - 16 - lead)
+    direct = list(staged)
+    direct[1025] += "."
+    for strs, over in ((staged, 0), (direct, 1)):
+        size = [len(s) for s in strs]
+        assert len(size) == 2048 and set(size) - {size[1], size[1025]} == {23}
+        assert sum(size[:1024]) % 16 == lead and sum(size[:1024]) + 16 <= DT_STAGE             # tile 0, at lead 0, is staged
+        assert sum(size[1024:]) + lead + 16 == DT_STAGE + over
+    want = expected(staged)
+    same_bits(expected(direct), want)
+    bad_rows = (700, 2047)
+    good = np.ones(2048, bool)
+    good[list(bad_rows)] = False
+    got = []
+    for strs in (staged, direct):
+        t = table_of(dfdb_mod, strs)
+        nk, ni = launches(ctx, lambda: got.append(project_raw(dfdb_mod, t)))
+        assert nk >= 1 and ni == 0, (nk, ni)
+        same_bits(got[-1], want)
+        bad = list(strs)
+        for r in bad_rows:
+            bad[r] = strs[r][:5] + "13" + strs[r][7:]                     # month 13: the same bytes in all, an ArgumentError
+            assert datetime_ref(bad[r])[0] == ARGUMENT and len(bad[r]) == len(strs[r])
+        tb = table_of(dfdb_mod, bad)
+        with raises(ARGUMENT, bad_rows[0]):
+            project_raw(dfdb_mod, tb)
+        with raises(ARGUMENT, bad_rows[1]):
+            project_raw(dfdb_mod, tb, sel=ir.col(1) != bad_rows[0])
+        same_bits(project_raw(dfdb_mod, tb, sel=(ir.col(1) != bad_rows[0]) & (ir.col(1) != bad_rows[1])), want[good])
+    same_bits(got[0], got[1])
+
+
 def test_selections_give_compacted_results_in_order(dfdb_mod, ctx):
     from dfdb import ir
     strs = mixed_rows(5 * 1024 + 100, seed=3)

@@ -372,6 +372,51 @@ def test_long_strings_take_the_direct_path(dfdb_mod, ctx, jit, path):
         project(dfdb_mod, table_of(dfdb_mod, strs), lambda s: ir.parse(ir.I32, s))
 
 
+PARSE_STAGE = 19968          # the bytes a wave stages for parse (csrc/k_parse.hip: ParseConv::kStage)
+
+
+def stage_edge_rows(rng, lead, tile1_bytes):
+    """2048 rows, the two tiles of one workgroup: Int64 digit strings of up to 19 bytes, the second row of each tile widened with whitespace to the tile's
+    byte total.  Tile 0 holds the most bytes that are staged and leave tile 1 `lead` bytes above a 16-byte boundary; tile 1 holds tile1_bytes"""
+    strs = []
+    for total in (PARSE_STAGE - 16 - (16 - lead) % 16, tile1_bytes):
+        rows = []
+        for _ in range(1024):
+            nd = 19 if rng.random() < 0.8 else int(rng.integers(1, 19))
+            v = int(rng.integers(10**18, 2**63 - 1, dtype=np.int64)) if nd == 19 else int(rng.integers(10**(nd - 1) if nd > 1 else 0, 10**nd))
+            rows.append(("-" if nd < 19 and rng.random() < 0.3 else "") + str(v))
+        pad = total - sum(len(r) for r in rows)
+        assert pad > 0, pad
+        rows[1] = " " * (pad // 2) + rows[1] + "\t" * (pad - pad // 2)
+        strs += rows
+    return strs
+
+
+@pytest.mark.parametrize("lead", [0, 15])
+def test_the_largest_staged_tile_and_the_smallest_direct_tile(dfdb_mod, ctx, lead):
+    """a tile `lead` bytes above a 16-byte boundary is staged exactly when its bytes + lead + 16 <= PARSE_STAGE: the tile that fills the stage to its last
+    byte, and the same tile one byte longer, which is parsed from the arena.  Both tiles belong to one workgroup, whose two stages are neighbours in LDS"""
+    from dfdb import ir
+    staged = stage_edge_rows(np.random.default_rng(1900 + lead), lead, PARSE_STAGE - 16 - lead)
+    direct = list(staged)
+    direct[1025] += " "
+    for strs, over in ((staged, 0), (direct, 1)):
+        size = [len(s) for s in strs]
+        assert len(size) == 2048 and max(len(s.strip()) for s in strs) <= 19
+        assert sum(size[:1024]) % 16 == lead and sum(size[:1024]) + 16 <= PARSE_STAGE          # tile 0, at lead 0, is staged
+        assert sum(size[1024:]) + lead + 16 == PARSE_STAGE + over
+    want = expected(R.I64, staged)
+    same_bits(expected(R.I64, direct), want)
+    ctx.set_option("parse_kernel", 1)
+    got = []
+    for strs in (staged, direct):
+        t = table_of(dfdb_mod, strs)
+        nk, ni = launches(ctx, lambda: got.append(project(dfdb_mod, t, lambda s: ir.parse(ir.I64, s))))
+        assert nk >= 1 and ni == 0, (nk, ni)
+        same_bits(got[-1], want)
+    same_bits(got[0], got[1])
+
+
 @pytest.mark.parametrize("bad,kind", [("12a", ARGUMENT), ("9" * 25, OVERFLOW), ("0x10", UNSUPPORTED), ("1\u2003", UNSUPPORTED), (None, METHOD)])
 def test_a_parsed_divisor_reports_the_parse_outcome_not_a_divide_error(dfdb_mod, ctx, jit, bad, kind):
     """a row without a value goes on as 0, so `x ÷ parse(T, s)` meets a division by zero of its own on the same row: the parse outcome is the one reported

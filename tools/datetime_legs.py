@@ -7,10 +7,10 @@ warm-up of each, every call timed with HIP events on the engine stream (dfdb_ctx
 rounds.  The kernels' own times come from the per-launch profile (dfdb_ctx_profile_*) of one more call per leg, outside the rounds.  GB/s counts the
 algorithmic bytes per row (4 of size + the string + 8 of result; the scan writes a bit) against the 8 TB/s peak.
 
-  datetime, kernel        add_column of datetime19.(s) into a new resident DateTime column through k_str_datetime (parse_kernel = 1)
+  datetime, kernel        add_column of datetime19.(s) into a new resident DateTime column through k_str_convert, datetime conversion (parse_kernel = 1)
   datetime, compiled      the same through the interpreter's H_DATETIME compiled at run time (parse_kernel = 0, jit = 2)
   datetime, interpreted   the same interpreted (parse_kernel = 0, jit = 0)
-  parse 19 digits         k_str_parse over as many 19-digit strings: the README's parse row, in this process
+  parse 19 digits         k_str_convert (parse conversion) over as many 19-digit strings: the README's parse row, in this process
   scan s == const         the String equality count over the timestamp column: the read ceiling for these sizes and bytes
 
 The last line applies the acceptance rule: the kernel stays the default route only if its median is below the compiled interpreter's by more than the two

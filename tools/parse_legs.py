@@ -5,7 +5,7 @@ Input: --rows (default 1e8) 19-digit decimal strings built with numpy and handed
 beside them for the 10 % selection.  Every leg is timed with HIP events on the engine stream (dfdb_ctx_timer_*), best of five after a warm-up; the
 kernel's own time comes from the per-launch profile (dfdb_ctx_profile_*) of one more run.  GB/s counts (4 + len + 8) bytes per row against the 8 TB/s peak.
 
-  add_column_from   parse(Int64, s) of every row into a new resident column: the conversion kernel k_str_parse, and the interpreter form of the same
+  add_column_from   parse(Int64, s) of every row into a new resident column: the conversion kernel k_str_convert (parse conversion), and the interpreter form of the same
                     expression (ctx option parse_kernel = 0) as its run-time compiled kernel (jit = 2) and interpreted (jit = 0)
   materialize 10 %  the selection `k % 10 == 3` executed beforehand, then the parsed column of the selected rows delivered to the host
   yardstick         the String equality scan `s == "<a value>"` over the same column: reads the same sizes and bytes, writes a bitmap
