@@ -408,6 +408,7 @@ int32_t dfdb_query_add_predicate(dfdb_query* q, const uint8_t* ir, size_t len) {
     NEEDQ(q); NEED(ir);
     ooc_reset(q);
     Stage s; s.kind = ST_PRED; s.pred = parse_ir(*q->t, ir, len);
+    if (is_string_coalesce(*s.pred)) fail(DFDB_ERR_UNSUPPORTED, "a String coalesce is only valid as a whole projection column, not as a predicate");
     if (s.pred->dtype != DFDB_BOOL) fail(DFDB_ERR_ARGUMENT, "ArgumentError: Function for selection must have Bool result type");   // selection.jl:52-55
     query_add_stage(q, std::move(s));
   });

@@ -84,7 +84,8 @@ static int infer_base(int op, int ta, int tb);
 static int infer(int op, int ta, int tb) {
   if (op == DFIR_ISMISSING) return DFDB_BOOL;
   if (op == DFIR_COALESCE) {
-    if (dt_base(ta) != dt_base(tb) || !dt_isnum(dt_base(ta)))
+    // (two Strings: the operand shapes are parse_ir's to check — a column leaf, then a column leaf or a constant)
+    if (dt_base(ta) != dt_base(tb) || !(dt_isnum(dt_base(ta)) || dt_base(ta) == DFDB_STRING))
       fail(DFDB_ERR_UNSUPPORTED, "coalesce(%s, %s): the result would be a Union of two value types", dt_name(ta).c_str(), dt_name(tb).c_str());
     return dt_base(ta) | (dt_nullable(tb) ? DFDB_NULLABLE : 0);
   }
@@ -159,6 +160,11 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
   size_t pos = 0;
   auto need = [&](size_t n) { if (pos + n > len) fail(DFDB_ERR_ARGUMENT, "truncated IR"); };
   auto pop = [&]() -> NodePtr { if (st.empty()) fail(DFDB_ERR_ARGUMENT, "IR stack underflow"); NodePtr n = std::move(st.back()); st.pop_back(); return n; };
+  // a String-typed coalesce (include/dfdb_ir.h) is a whole projection column: no operation takes it as an operand
+  auto no_string_coalesce = [](const Node& x) {
+    if (is_string_coalesce(x))
+      fail(DFDB_ERR_UNSUPPORTED, "a String coalesce is only valid as a whole projection column, not as an operand: materialise it as a column first (dfdb_table_add_from_query)");
+  };
   while (pos < len) {
     const int op = ir[pos++];
     auto n = std::make_unique<Node>();
@@ -188,6 +194,7 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
         if (op == DFIR_CAST) { need(1); n->cast_to = ir[pos++]; }
         n->a = pop();
         if (n->a->op == DFIR_CONST_SET) fail(DFDB_ERR_ARGUMENT, "a set is only valid as the second argument of in");
+        no_string_coalesce(*n->a);
         if (op == DFIR_CAST && (n->cast_to & 0x40)) {
           // the only target outside the dtypes: datetime19(s) over a String column leaf (include/dfdb_ir.h); Int64 milliseconds, never Union{DateTime,Missing}
           if (n->cast_to != DFDB_CAST_DATETIME || n->a->op != DFIR_COL || dt_base(n->a->dtype) != DFDB_STRING)
@@ -213,6 +220,7 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
                            op == DFIR_IN_SET || op == DFIR_STARTSWITH || op == DFIR_ENDSWITH || op == DFIR_COALESCE;
         if (!known) fail(DFDB_ERR_UNSUPPORTED, "unknown IR opcode 0x%02x", op);
         n->b = pop(); n->a = pop();
+        no_string_coalesce(*n->a); no_string_coalesce(*n->b);
         if (op == DFIR_IN_SET) {
           if (n->b->op != DFIR_CONST_SET || n->a->op == DFIR_CONST_SET) fail(DFDB_ERR_ARGUMENT, "in needs (value, set)");
           n->dtype = infer(op, n->a->dtype, 0);
@@ -220,6 +228,12 @@ NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len) {
           if (n->a->op == DFIR_CONST_SET || n->b->op == DFIR_CONST_SET) fail(DFDB_ERR_ARGUMENT, "a set is only valid as the second argument of in");
           if ((op == DFIR_STARTSWITH || op == DFIR_ENDSWITH) && n->b->op != DFIR_CONST_STR) fail(DFDB_ERR_UNSUPPORTED, "startswith/endswith need a constant pattern");
           n->dtype = infer(op, n->a->dtype, n->b->dtype);
+          if (op == DFIR_COALESCE && dt_base(n->dtype) == DFDB_STRING) {
+            const bool leaves = n->a->op == DFIR_COL && (n->b->op == DFIR_COL || n->b->op == DFIR_CONST_STR);
+            if (!leaves) fail(DFDB_ERR_UNSUPPORTED, "coalesce over Strings takes a String column, then a String column or a string constant");
+            if (n->b->op == DFIR_CONST_STR && n->b->str.size() > kMaxCoalesceConst)
+              fail(DFDB_ERR_UNSUPPORTED, "coalesce over Strings: the constant holds %zu bytes, at most %zu are taken", n->b->str.size(), kMaxCoalesceConst);
+          }
         }
         break;
       }

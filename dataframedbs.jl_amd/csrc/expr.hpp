@@ -24,6 +24,12 @@ struct Node {
 };
 using NodePtr = std::unique_ptr<Node>;
 
+// the longest constant of a String coalesce: 1024 rows of it stay far inside the 32-bit selected byte total of a tile (k_str_coalesce_sizes)
+constexpr size_t kMaxCoalesceConst = 65535;
+// `coalesce(a, b)` with a String result: a whole projection column (k_strings.hip K6c).  parse_ir admits no other shape: a is a String column leaf, b a
+// String column leaf or a string constant
+inline bool is_string_coalesce(const Node& n) { return n.op == DFIR_COALESCE && (n.dtype & DFDB_DTYPE_MASK) == DFDB_STRING; }
+
 NodePtr parse_ir(const dfdb_table& t, const uint8_t* ir, size_t len);
 NodePtr make_and(NodePtr a, NodePtr b);            // BlockBroadcasting(&, (old, new)): selection.jl:44-47
 void required_columns(const Node& n, std::vector<int>& out);  // first-appearance order, unique

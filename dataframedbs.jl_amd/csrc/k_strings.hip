@@ -476,6 +476,22 @@ void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64
   hipLaunchKernelGGL(k_str_gather_sizes, dim3(grid_for((nt + group - 1) / group)), dim3(kBlock), 0, s, bitmap, prefix, sizes, out_sizes, sel_tile_bytes, nt, out_cap, group);
 }
 
+// the byte offset of every row of a tile from the tile's first byte (exclusive prefix of the clamped sizes of ALL its rows) -> pre[1024] in this wave's LDS:
+// 16 coalesced size loads + 16 in-register scans.  The caller fences before it reads
+__device__ __forceinline__ void stage_tile_prefix(const int32_t* sizes, int64_t base, int64_t nrows, int lane, uint32_t* pre) {
+  int32_t sz[16];
+#pragma unroll
+  for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? sizes[i] : 0; }
+  uint32_t run = 0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const uint32_t c = clamp_size(sz[j]);
+    const uint32_t incl = wave_incl_scan(c);
+    pre[j * 64 + lane] = run + incl - c;
+    run += __shfl(incl, 63, 64);
+  }
+}
+
 // pass 2: bytes.  The tile's per-row source offsets (exclusive prefix of the sizes of ALL rows) go to LDS once
 // (16 coalesced size loads + 16 in-register scans); then 64 selected rows at a time: destination offsets by a
 // wave prefix-sum of the selected sizes, and every lane copies its own string.
@@ -500,7 +516,7 @@ __global__ __launch_bounds__(kBlock) void k_str_gather_bytes(const uint64_t* __r
     if (total == 0) { wave_lds_fence(); continue; }        // wave-uniform: late materialization of the arena
     const int64_t base = tile * kTile;
     int32_t sz[16];
-#pragma unroll
+#pragma unroll   // (stage_tile_prefix, spelled out: through the helper the compiler hoists and allocates differently here, and this kernel stays as it was measured)
     for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? sizes[i] : 0; }
     uint32_t run = 0;
 #pragma unroll
@@ -540,6 +556,121 @@ void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const int32_
   const int group = gather_group(nt);
   hipLaunchKernelGGL(k_str_gather_bytes, dim3(grid_for((nt + group - 1) / group)), dim3(kBlock), 0, s, bitmap, sizes, tile_off, bytes, out_tile_off, out_bytes, nrows,
                      nt, out_bytes_cap, group);
+}
+
+// ---------------------------------------------------------------- K6c: coalesce(a, b) as a String projection column
+// Row i of the result is a[i] unless a[i] is missing (size -1), else b[i] — b a String column of the same table (TWO) or one constant.  K6's two passes with a
+// source select per row: the sizes pass writes `sa >= 0 ? sa : (TWO ? sb : clen)` and adds up the clamped sizes per tile (a row missing on both sides stays
+// -1 and adds nothing); the bytes pass stages a's per-row source offsets in LDS, b's beside them (TWO: 4 KB more per wave), and every lane copies its row out
+// of a's arena, b's arena or the constant (device memory, padded for copy_string's 8-byte tail load).  Both passes read the columns' own sizes and bytes.
+struct StrSide { const int32_t* sizes; const int64_t* tile_off; const uint8_t* bytes; };
+
+template <bool TWO>
+__global__ __launch_bounds__(kBlock) void k_str_coalesce_sizes(const uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ prefix,
+                                                               const int32_t* __restrict__ sizes_a, const int32_t* __restrict__ sizes_b, int32_t clen,
+                                                               int32_t* __restrict__ out_sizes, uint32_t* __restrict__ sel_tile_bytes, int64_t ntiles,
+                                                               int64_t out_cap, int group) {
+  __shared__ uint16_t pos_sh[kWavesPerBlock][1024];
+  const int lane = lane_id();
+  const int wib = threadIdx.x >> 6;
+  uint16_t* pos = pos_sh[wib];
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wib;
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t c0 = wave * group; c0 < ntiles; c0 += nwaves * group) {      // (`group` tiles at a time, the empty ones skipped: see k_str_gather_sizes)
+   const int64_t tl = c0 + lane;
+   const bool mine = lane < group && tl < ntiles;
+   const bool some = mine && prefix[tl + 1] > prefix[tl];
+   if (mine && !some) sel_tile_bytes[tl] = 0;
+   for (uint64_t todo = __ballot(some); todo; todo &= todo - 1) {
+    const int64_t tile = c0 + __builtin_ctzll(todo);
+    const uint32_t total = stage_tile_positions(bitmap, tile, pos, lane);
+    const int64_t obase = (int64_t)prefix[tile];
+    const int32_t* ta = sizes_a + tile * kTile;
+    const int32_t* tb = TWO ? sizes_b + tile * kTile : nullptr;
+    uint32_t bsum = 0;
+    for (uint32_t k = lane; k < total; k += 64) {
+      const uint32_t p = pos[k];
+      const int32_t sa = ta[p];
+      const int32_t sz = sa >= 0 ? sa : (TWO ? tb[p] : clen);
+      bsum += clamp_size(sz);
+      if (obase + k < out_cap) out_sizes[obase + k] = sz;
+    }
+    bsum = wave_sum(bsum);
+    if (lane == 0) sel_tile_bytes[tile] = bsum;
+    wave_lds_fence();
+   }
+  }
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(kBlock) void k_str_coalesce_bytes(const uint64_t* __restrict__ bitmap, StrSide a, StrSide b, const uint8_t* __restrict__ cbytes,
+                                                               uint32_t clen, const uint64_t* __restrict__ out_tile_off, uint8_t* __restrict__ out_bytes,
+                                                               int64_t nrows, int64_t ntiles, int64_t out_cap, int group) {
+  __shared__ uint16_t pos_sh[kWavesPerBlock][1024];
+  __shared__ uint32_t pre_sh[TWO ? 2 : 1][kWavesPerBlock][1024];
+  const int lane = lane_id();
+  const int wib = threadIdx.x >> 6;
+  uint16_t* pos = pos_sh[wib];
+  uint32_t* pre_a = pre_sh[0][wib];
+  uint32_t* pre_b = pre_sh[TWO ? 1 : 0][wib];
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wib;
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t c0 = wave * group; c0 < ntiles; c0 += nwaves * group) {
+   const int64_t tl = c0 + lane;
+   const bool some = lane < group && tl < ntiles && out_tile_off[tl + 1] > out_tile_off[tl];
+   for (uint64_t todo = __ballot(some); todo; todo &= todo - 1) {
+    const int64_t tile = c0 + __builtin_ctzll(todo);
+    const uint32_t total = stage_tile_positions(bitmap, tile, pos, lane);
+    if (total == 0) { wave_lds_fence(); continue; }
+    const int64_t base = tile * kTile;
+    stage_tile_prefix(a.sizes, base, nrows, lane, pre_a);
+    if (TWO) stage_tile_prefix(b.sizes, base, nrows, lane, pre_b);
+    wave_lds_fence();
+    const uint8_t* ba = a.bytes + a.tile_off[tile];
+    const uint8_t* bb = TWO ? b.bytes + b.tile_off[tile] : cbytes;
+    int64_t drun = (int64_t)out_tile_off[tile];
+    const int32_t* tsa = a.sizes + base;
+    const int32_t* tsb = TWO ? b.sizes + base : nullptr;
+    for (uint32_t k0 = 0; k0 < total; k0 += 64) {
+      const uint32_t k = k0 + lane;
+      const bool valid = k < total;
+      const uint32_t p = valid ? pos[k] : 0u;
+      const int32_t sa = valid ? tsa[p] : 0;
+      const bool from_a = sa >= 0;
+      uint32_t cs = 0;
+      if (valid) cs = from_a ? (uint32_t)sa : (TWO ? clamp_size(tsb[p]) : clen);
+      const uint32_t incl = wave_incl_scan(cs);
+      if (cs) {
+        const uint8_t* sp = from_a ? ba + pre_a[p] : (TWO ? bb + pre_b[p] : bb);
+        const int64_t d0 = drun + (int64_t)(incl - cs);
+        if (d0 + cs <= out_cap) copy_string(out_bytes + d0, sp, cs);
+      }
+      drun += (int64_t)__shfl(incl, 63, 64);
+    }
+    wave_lds_fence();
+   }
+  }
+}
+
+void launch_str_coalesce_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const int32_t* sizes_a, const int32_t* sizes_b, int32_t clen,
+                               int32_t* out_sizes, uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap) {
+  const int64_t nt = (nrows + kTile - 1) / kTile;
+  if (nt == 0) return;
+  const int group = gather_group(nt);
+  const dim3 g(grid_for((nt + group - 1) / group)), b(kBlock);
+  if (sizes_b) hipLaunchKernelGGL((k_str_coalesce_sizes<true>), g, b, 0, s, bitmap, prefix, sizes_a, sizes_b, clen, out_sizes, sel_tile_bytes, nt, out_cap, group);
+  else hipLaunchKernelGGL((k_str_coalesce_sizes<false>), g, b, 0, s, bitmap, prefix, sizes_a, sizes_b, clen, out_sizes, sel_tile_bytes, nt, out_cap, group);
+}
+void launch_str_coalesce_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes_a, const int64_t* tile_off_a, const uint8_t* bytes_a,
+                               const int32_t* sizes_b, const int64_t* tile_off_b, const uint8_t* bytes_b, const uint8_t* const_dev, int32_t clen,
+                               const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap) {
+  const int64_t nt = (nrows + kTile - 1) / kTile;
+  if (nt == 0) return;
+  const int group = gather_group(nt);
+  const dim3 g(grid_for((nt + group - 1) / group)), b(kBlock);
+  const StrSide sa{sizes_a, tile_off_a, bytes_a}, sb{sizes_b, tile_off_b, bytes_b};
+  if (sizes_b) hipLaunchKernelGGL((k_str_coalesce_bytes<true>), g, b, 0, s, bitmap, sa, sb, const_dev, (uint32_t)clen, out_tile_off, out_bytes, nrows, nt, out_bytes_cap, group);
+  else hipLaunchKernelGGL((k_str_coalesce_bytes<false>), g, b, 0, s, bitmap, sa, sb, const_dev, (uint32_t)clen, out_tile_off, out_bytes, nrows, nt, out_bytes_cap, group);
 }
 
 // projection of a String column whose selected rows K5 kept (CAP): per 1024-row tile a contiguous copy of its sizes and bytes

@@ -139,6 +139,13 @@ void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64
                              uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap);
 void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes,
                              const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap);
+// K6c: coalesce(a, b) as a String column — a's row unless it is missing, else b's row (sizes_b set) or the constant (sizes_b null: const_dev holds clen
+// bytes and 8 of padding).  The same two passes and the same outputs as K6
+void launch_str_coalesce_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const int32_t* sizes_a, const int32_t* sizes_b, int32_t clen,
+                               int32_t* out_sizes, uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap);
+void launch_str_coalesce_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes_a, const int64_t* tile_off_a, const uint8_t* bytes_a,
+                               const int32_t* sizes_b, const int64_t* tile_off_b, const uint8_t* bytes_b, const uint8_t* const_dev, int32_t clen,
+                               const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap);
 
 // n rows that all hold the same string: sizes[i] = plen, bytes = the pattern (device memory) n times
 void launch_fill_const_strings(hipStream_t s, int32_t* out_sizes, uint8_t* out_bytes, int64_t n, const uint8_t* pat_dev, int32_t plen);

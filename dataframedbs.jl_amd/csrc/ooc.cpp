@@ -340,9 +340,9 @@ int64_t ooc_string_bytes(dfdb_query* q, int32_t i) {
   if (i < 0 || (size_t)i >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", i);
   const Node& e = *q->proj[(size_t)i].expr;
   if (dt_base(e.dtype) != DFDB_STRING) return 0;
-  if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
+  if (e.op != DFIR_COL && !is_string_coalesce(e)) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
   OocState& o = state(q);
-  if (o.narrowed && o.merged_col == e.col) return (int64_t)o.merged.keys[0].key_bytes.size();
+  if (o.narrowed && e.op == DFIR_COL && o.merged_col == e.col) return (int64_t)o.merged.keys[0].key_bytes.size();
   if (!o.narrowed && o.str_bytes[(size_t)i] >= 0) return o.str_bytes[(size_t)i];
   // a sizing pass of its own: the selection with this one column as its projection
   TempQuery tq(q, !o.narrowed);

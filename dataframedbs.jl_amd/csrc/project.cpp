@@ -77,8 +77,12 @@ static bool string_captured(const dfdb_query* q, const Column& col) {
   return q->left.cap_str_col >= 0 && &q->t->cols[(size_t)q->left.cap_str_col] == &col && reflects_all_stages(q);
 }
 
-// selected string bytes per 1024-row tile -> exclusive scan (output arena offsets); returns total
-static int64_t string_out_offsets(dfdb_query* q, const Column& col, DevBuf& out_sizes_tmp, int32_t* out_sizes, int64_t cap, DevBuf& tile_off_out) {
+// coalesce(a, b) with a String result (expr.hpp is_string_coalesce): the second side as K6c takes it — column b's sizes, or null and the constant's length
+static const Column* coalesce_second(dfdb_query* q, const Node& e) { return e.b->op == DFIR_COL ? &need_resident(q->t, e.b->col) : nullptr; }
+
+// selected string bytes per 1024-row tile -> exclusive scan (output arena offsets); returns total.  `co`: the column is coalesce(col, b), not col itself
+static int64_t string_out_offsets(dfdb_query* q, const Column& col, DevBuf& out_sizes_tmp, int32_t* out_sizes, int64_t cap, DevBuf& tile_off_out,
+                                  const Node* co = nullptr) {
   dfdb_ctx* ctx = q->t->ctx; hipStream_t s = ctx->stream;
   const int64_t nct = ceil_div(q->t->nrows, kTileRows);
   DevBuf& tb = q->tmp_c; tb.ensure((size_t)(nct + 8) * 4);
@@ -93,6 +97,15 @@ static int64_t string_out_offsets(dfdb_query* q, const Column& col, DevBuf& out_
   };
   int32_t* dst_sizes = out_sizes;
   if (!dst_sizes) { out_sizes_tmp.ensure((size_t)std::max<int64_t>(cap, 1) * 4); dst_sizes = out_sizes_tmp.as<int32_t>(); }
+  if (co) {
+    // K6c reads the flat sizes of both sides through the bitmap.  What the execution left behind for a plain projection of `col` — K5's capture, "every
+    // selected row holds the constant", the compacted dictionary codes — answers for col's own rows, not for the coalesced ones, and is not looked at
+    const Column* cb = coalesce_second(q, *co);
+    { LaunchTimer lt(ctx, "str_coalesce_sizes");
+      launch_str_coalesce_sizes(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), col.data.as<int32_t>(), cb ? cb->data.as<int32_t>() : nullptr,
+                                (int32_t)co->b->str.size(), dst_sizes, tb.as<uint32_t>(), q->t->nrows, cap); }
+    return scan_total(tb.as<uint32_t>(), nct);
+  }
   if (col.dict_n > 0) {
     // K9: the selected rows' codes, compacted by K3 (kept in q->dict_sel for the bytes pass), then sizes and byte totals per 1024 OUTPUT rows
     const int64_t n = std::min<int64_t>(cap, query_count(q, -1));
@@ -117,11 +130,42 @@ int64_t query_string_bytes(dfdb_query* q, int i) {
   if (i < 0 || (size_t)i >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", i);
   const Node& e = *q->proj[(size_t)i].expr;
   if (dt_base(e.dtype) != DFDB_STRING) return 0;
+  if (is_string_coalesce(e)) return string_out_offsets(q, need_resident(q->t, e.a->col), q->str_sizes, nullptr, query_count(q, -1), q->str_toff, &e);
   if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
   const Column& col = need_resident(q->t, e.col);
   const int64_t cnt = query_count(q, -1);
   if (q->left.const_str_col == e.col && reflects_all_stages(q)) return cnt * (int64_t)q->left.const_str.size();
   return string_out_offsets(q, col, q->str_sizes, nullptr, cnt, q->str_toff);
+}
+
+// the output column coalesce(a, b) over Strings: K6's two passes with a source select per row (k_strings.hip K6c).  No row raises
+static void materialize_str_coalesce(dfdb_query* q, const Node& e, int32_t p, dfdb_outcol& o, int64_t cnt) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const bool dev = o.memkind == DFDB_MEM_DEVICE;
+  const Column& ca = need_resident(t, e.a->col);
+  const Column* cb = coalesce_second(q, e);
+  DevBuf &dsz = q->str_sizes, &toff = q->str_toff, &dbytes = q->str_bytes;
+  int32_t* d_sizes = dev ? (int32_t*)o.data : nullptr;
+  const int64_t total = string_out_offsets(q, ca, dsz, d_sizes, cnt, toff, &e);
+  if (!d_sizes) d_sizes = dsz.as<int32_t>();
+  o.nbytes = total;
+  if (total > o.bytes_cap) fail(DFDB_ERR_ARGUMENT, "output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)o.bytes_cap);
+  uint8_t* d_bytes = dev ? o.bytes : nullptr;
+  if (!dev) { dbytes.ensure((size_t)total + 64); d_bytes = dbytes.as<uint8_t>(); }
+  if (total > 0) {
+    const std::string& k = e.b->str;                 // (empty when b is a column)
+    DevBuf& kb = q->tmp_a; kb.ensure(k.size() + 64);   // the constant on the device, with room behind it for copy_string's 8-byte tail load
+    if (!cb && !k.empty()) { HIP_CHECK(hipMemcpyAsync(kb.p, k.data(), k.size(), hipMemcpyHostToDevice, s)); stream_wait(ctx); }
+    LaunchTimer lt(ctx, "str_coalesce_bytes");
+    launch_str_coalesce_bytes(s, q->bitmap.as<uint64_t>(), ca.data.as<int32_t>(), (const int64_t*)ca.tile_off.p, ca.bytes.as<uint8_t>(),
+                              cb ? cb->data.as<int32_t>() : nullptr, cb ? (const int64_t*)cb->tile_off.p : nullptr, cb ? cb->bytes.as<uint8_t>() : nullptr,
+                              kb.as<uint8_t>(), (int32_t)k.size(), toff.as<uint64_t>(), d_bytes, t->nrows, total);
+  }
+  if (!dev) {
+    HIP_CHECK(hipMemcpyAsync(o.data, d_sizes, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+    if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, d_bytes, (size_t)total, hipMemcpyDeviceToHost, s));
+    stream_wait(ctx);
+  }
 }
 
 // one output column of the projection (ProjectionExecutor.eval_on_range for column p: projection.jl:128-154)
@@ -206,6 +250,7 @@ void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
     }
     if (!dev) stream_wait(ctx);   // staging buffers die at scope exit; device outputs stay stream-ordered, no host wait
   } else {                  // BroadcastExecutor: computed column (projection.jl:128-129)
+    if (is_string_coalesce(e)) { materialize_str_coalesce(q, e, p, o, cnt); return; }
     if (dt_base(e.dtype) == DFDB_STRING) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
     DevBuf stage, mstage; void* dst = o.data;
     if (!dev) { stage.ensure((size_t)cnt * w); dst = stage.p; }

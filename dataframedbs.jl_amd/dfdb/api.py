@@ -1178,6 +1178,16 @@ def coalesce(c, default):
     return ir.coalesce(c, default)
 
 
+def string(c):
+    """string.(col) over a String column: coalesce.(col, "missing") where the column is Union{String,Missing} (Julia's string(missing)), the column itself
+    where it is a plain String column.  An Expr carries no type: it is taken as nullable, which gives a plain column back unchanged too."""
+    if isinstance(c, DFColumn):
+        if (c.eltype & ir.DTYPE_MASK) != ir.STRING:
+            raise NotImplementedError(f"string.(col) over {ir.dtype_name(c.eltype)} is not built: String columns only")
+        return coalesce(c, "missing") if c.eltype & ir.NULLABLE else c
+    return ir.string(c)
+
+
 def view_from_columns(**cols: DFColumn) -> DFView:
     """DFView(a = col1, g = col2) (column.jl:143-164)."""
     first = None

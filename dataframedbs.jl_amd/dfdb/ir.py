@@ -298,8 +298,15 @@ def sizeof(a) -> Expr:
 
 
 def coalesce(a, b) -> Expr:
-    """coalesce(a, b): a where it is not missing, else b (the way a Union{T,Missing} expression becomes a predicate)."""
+    """coalesce(a, b): a where it is not missing, else b (the way a Union{T,Missing} expression becomes a predicate).  Over a String column and a string
+    constant or a second String column it is a computed String column, valid as a whole projection column only (include/dfdb_ir.h)."""
     return Expr(COALESCE, (wrap(a), wrap(b)))
+
+
+def string(a, nullable: bool = True) -> Expr:
+    """`string.(s)` over a String column: over Union{String,Missing} it is coalesce(s, "missing") — Julia's string(missing), the tutorial's
+    docs/src/index.md:424 — and over a plain String column (nullable=False) the column itself."""
+    return coalesce(a, "missing") if nullable else wrap(a)
 
 
 def rem(a, b) -> Expr: return Expr(REM, (wrap(a), wrap(b)))

@@ -152,6 +152,12 @@ end
 datetime19(a::Tr) = Tr(vcat(a.code, 0x50, CAST_DATETIME))
 export datetime19
 
+# string.(s) over a String column: coalesce.(s, "missing") — string(missing) == "missing", the tutorial's docs/src/index.md:424 — which the engine types as a
+# computed String column (include/dfdb_ir.h DFIR_COALESCE); over a plain String column that is the column itself.  Valid as a whole column only
+# (add_column!, materialize): inside a larger expression the engine answers status 7 and the view takes the Julia path.  The tutorial's own closure,
+# x -> ismissing(x) ? "" : String(x), needs a Bool out of a traced value and cannot be traced: write coalesce.(t.s, "").
+Base.string(a::Tr) = cat2(a, "missing", OPS[coalesce])
+
 # BlockBroadcasting / ColRef -> Tr.  `ord` maps a column Symbol to its 0-based table ordinal.
 lower(c::ColRef, ord) = leaf(io -> emit_col(io, ord[c.name]))
 lower(x, ord) = tr(x)

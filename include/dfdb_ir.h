@@ -73,6 +73,17 @@ enum {
 #define DFIR_ISMISSING   0x43 /* unary on a nullable column -> Bool */
 #define DFIR_SIZEOF      0x44 /* unary: sizeof(string) -> Int64 */
 #define DFIR_COALESCE    0x45 /* binary: coalesce(a, b) = a unless it is missing, else b (same base type; result nullable iff b is) */
+/* DFIR_COALESCE over numeric operands takes any expressions.  Over Strings it makes a computed String column (the tutorial's string_convert,
+ * docs/src/index.md:437-453, and string(missing) at :424) and takes two leaves only:
+ *   a        a String or Union{String,Missing} COLUMN leaf
+ *   b        a string constant (DFIR_CONST_STR, at most 65535 bytes) or a String / Union{String,Missing} COLUMN leaf of the same table
+ *   row i    a[i] where a[i] is not missing, else b[i] (or the constant); no row raises
+ *   type     String; Union{String,Missing} iff b is a nullable column — a row missing on both sides stays missing (size -1, no bytes).  Over a
+ *            non-nullable a the result equals column a
+ * The expression is valid only as a WHOLE projection column (dfdb_result_string_bytes, dfdb_materialize, dfdb_table_add_from_query, resident, streamed
+ * and sharded).  Everything else is DFDB_ERR_UNSUPPORTED: a String coalesce as an operand of any operation (a comparison, sizeof, parse, startswith, a
+ * second coalesce) or as a predicate, any other operand shape, a longer constant; coalesce(String, number) is refused as a Union of two value types;
+ * unique / groupreduce over it keep their refusal of computed columns — dfdb_table_add_from_query makes it a column first. */
 
 /* ---- conversion ---- */
 #define DFIR_CAST  0x50 /* payload: u8 dtype ; Julia T(x) / convert */
