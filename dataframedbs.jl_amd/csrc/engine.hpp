@@ -63,6 +63,7 @@ struct Column {
   size_t data_off = 0;  // first block inside the file
   std::shared_ptr<BlockIndex> bix;   // block locations of `file`, as far as a stream or table_column_stats has walked them
 };
+inline StrSide str_side(const Column& c) { return StrSide{c.data.as<int32_t>(), (const int64_t*)c.tile_off.p, c.bytes.as<uint8_t>()}; }   // a resident String column, as the kernels take it
 
 enum StageKind { ST_RANGE = 0, ST_INTEGER = 1, ST_INDICES = 2, ST_PRED = 3 };
 

@@ -24,9 +24,9 @@ struct Node {
 };
 using NodePtr = std::unique_ptr<Node>;
 
-// the longest constant of a String coalesce: 1024 rows of it stay far inside the 32-bit selected byte total of a tile (k_str_coalesce_sizes)
+// the longest constant of a String coalesce: 1024 rows of it stay far inside the 32-bit selected byte total of a tile (k_str_gather_sizes)
 constexpr size_t kMaxCoalesceConst = 65535;
-// `coalesce(a, b)` with a String result: a whole projection column (k_strings.hip K6c).  parse_ir admits no other shape: a is a String column leaf, b a
+// `coalesce(a, b)` with a String result: a whole projection column (k_strings.hip K6, the two filled forms).  parse_ir admits no other shape: a is a String column leaf, b a
 // String column leaf or a string constant
 inline bool is_string_coalesce(const Node& n) { return n.op == DFIR_COALESCE && (n.dtype & DFDB_DTYPE_MASK) == DFDB_STRING; }
 

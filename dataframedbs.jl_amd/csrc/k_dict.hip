@@ -13,6 +13,7 @@
 //   k_dict_expand_* the projection: compacted codes (K3) -> sizes, then bytes out of the dictionary
 #include "device_utils.hpp"
 #include "kernels.hpp"
+#include "str_tile.hpp"
 
 namespace dfdb {
 
@@ -27,30 +28,9 @@ inline int grid_for(int64_t nunits, int cap = 4096) {
   if (b < 1) b = 1;
   return (int)b;
 }
-__device__ __forceinline__ uint32_t clamp_size(int32_t s) { return s > 0 ? (uint32_t)s : 0u; }
-__device__ __forceinline__ uint64_t load_u64_unaligned(const uint8_t* p) {
-  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
-  return *(const u64u*)p;
-}
 __device__ __forceinline__ bool bytes_equal(const uint8_t* a, const uint8_t* b, uint32_t n) {
   for (uint32_t k = 0; k < n; k++) if (a[k] != b[k]) return false;
   return true;
-}
-// exact copy of one string (len bytes): unaligned 8-byte moves, then ONE 8-byte load (the arenas are padded) and <= 3 stores
-__device__ __forceinline__ void copy_string(uint8_t* dp, const uint8_t* sp, uint32_t len) {
-  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
-  typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
-  typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
-  uint32_t b = 0;
-  for (; b + 8 <= len; b += 8) *(u64u*)(dp + b) = *(const u64u*)(sp + b);
-  const uint32_t rem = len - b;
-  if (rem) {
-    uint64_t v = *(const u64u*)(sp + b);
-    uint8_t* d = dp + b;
-    if (rem & 4u) { *(u32u*)d = (uint32_t)v; d += 4; v >>= 32; }
-    if (rem & 2u) { *(u16u*)d = (uint16_t)v; d += 2; v >>= 16; }
-    if (rem & 1u) *d = (uint8_t)v;
-  }
 }
 }  // namespace
 

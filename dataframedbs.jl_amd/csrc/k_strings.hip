@@ -52,10 +52,6 @@ void launch_str_tile_bytes(hipStream_t s, const int32_t* sizes, uint32_t* tile_b
 // ---------------------------------------------------------------- K5
 struct Pattern { uint64_t w[8]; int32_t len; };   // patterns up to 64 bytes travel in the kernel arguments
 
-__device__ __forceinline__ uint64_t load_u64_unaligned(const uint8_t* p) {
-  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
-  return *(const u64u*)p;
-}
 // compare `len` bytes at p with the pattern (8 bytes at a time; the arena is padded so the last probe is safe)
 __device__ __forceinline__ bool bytes_equal(const uint8_t* p, const Pattern& pat, int len) {
   int k = 0, wi = 0;
@@ -124,34 +120,6 @@ __global__ __launch_bounds__(kBlock) void k_str_match(const int32_t* __restrict_
 //   A  wave prefix-sums of the sizes -> per-row byte offsets       (ALU only)
 //   B  one unaligned 8-byte probe per candidate row (size matches) (8 loads in flight per lane)
 //   C  masked compare + ballot = bitmap word
-// exact copy of one string (len bytes): unaligned 8-byte moves, then ONE 8-byte load (the arenas are padded) and <= 3 stores
-__device__ __forceinline__ void copy_string(uint8_t* dp, const uint8_t* sp, uint32_t len) {
-  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
-  typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
-  typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
-  uint32_t b = 0;
-  for (; b + 8 <= len; b += 8) *(u64u*)(dp + b) = *(const u64u*)(sp + b);
-  const uint32_t rem = len - b;
-  if (rem) {
-    uint64_t v = *(const u64u*)(sp + b);
-    uint8_t* d = dp + b;
-    if (rem & 4u) { *(u32u*)d = (uint32_t)v; d += 4; v >>= 32; }
-    if (rem & 2u) { *(u16u*)d = (uint16_t)v; d += 2; v >>= 16; }
-    if (rem & 1u) *d = (uint8_t)v;
-  }
-}
-
-// the low `len` (<= 8) bytes of v
-__device__ __forceinline__ void store_small(uint8_t* d, uint64_t v, uint32_t len) {
-  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
-  typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
-  typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
-  if (len >= 8u) { *(u64u*)d = v; return; }
-  if (len & 4u) { *(u32u*)d = (uint32_t)v; d += 4; v >>= 32; }
-  if (len & 2u) { *(u16u*)d = (uint16_t)v; d += 2; v >>= 16; }
-  if (len & 1u) *d = (uint8_t)v;
-}
-
 // round 4: the tile's bytes arrive through LDS.  The probes of the candidate rows used to be the only readers of the arena — 8-byte loads at byte-granular
 // addresses, a few active lanes per instruction, every 128-byte line of the arena fetched anyway because a line holds ~20 strings — and the pass ran at 0.58-0.64
 // of the HBM peak.  Now the wave streams the tile's byte range [tile_off[t], tile_off[t+1]) with aligned 16-byte loads that are in flight together with the sixteen
@@ -405,13 +373,12 @@ __global__ __launch_bounds__(kBlock) void k_str_pair(const int32_t* __restrict__
   }
 }
 
-void launch_str_pair(hipStream_t s, const int32_t* sizes_a, const int64_t* toff_a, const uint8_t* bytes_a, const int32_t* sizes_b, const int64_t* toff_b,
-                     const uint8_t* bytes_b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing) {
+void launch_str_pair(hipStream_t s, const StrSide& a, const StrSide& b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing) {
   const int64_t ntiles = (nrows + kTile - 1) / kTile;
   if (ntiles == 0) return;
   const int g = grid_for(ntiles, 2048);
-  if (and_existing) hipLaunchKernelGGL((k_str_pair<true>), dim3(g), dim3(kBlock), 0, s, sizes_a, toff_a, bytes_a, sizes_b, toff_b, bytes_b, op, bitmap, tile_counts, nrows, ntiles);
-  else hipLaunchKernelGGL((k_str_pair<false>), dim3(g), dim3(kBlock), 0, s, sizes_a, toff_a, bytes_a, sizes_b, toff_b, bytes_b, op, bitmap, tile_counts, nrows, ntiles);
+  if (and_existing) hipLaunchKernelGGL((k_str_pair<true>), dim3(g), dim3(kBlock), 0, s, a.sizes, a.tile_off, a.bytes, b.sizes, b.tile_off, b.bytes, op, bitmap, tile_counts, nrows, ntiles);
+  else hipLaunchKernelGGL((k_str_pair<false>), dim3(g), dim3(kBlock), 0, s, a.sizes, a.tile_off, a.bytes, b.sizes, b.tile_off, b.bytes, op, bitmap, tile_counts, nrows, ntiles);
 }
 
 // ---------------------------------------------------------------- K6
@@ -434,11 +401,18 @@ __device__ __forceinline__ uint32_t stage_tile_positions(const uint64_t* __restr
   return total;
 }
 
+// Row i of the output is a[i], or — FILL — what stands behind a missing row (size -1) of a: nothing (STR_FILL_NONE, the plain projection: the sizes go out as
+// they are, -1 included), one constant (STR_FILL_CONST: device memory, padded for copy_string's 8-byte tail load) or row i of a second column of the same table
+// (STR_FILL_COL): coalesce(a, b).  A row missing on both sides stays -1 and adds no byte.  The plain form reads, computes and keeps nothing for a second side.
+
 // pass 1: selected sizes -> out_sizes at the tile's row offset, plus the selected byte total of the tile
+template <StrFillKind FILL>
 __global__ __launch_bounds__(kBlock) void k_str_gather_sizes(const uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ prefix,
-                                                             const int32_t* __restrict__ sizes, int32_t* __restrict__ out_sizes,
-                                                             uint32_t* __restrict__ sel_tile_bytes, int64_t ntiles, int64_t out_cap, int group) {
+                                                             const int32_t* __restrict__ sizes_a, const int32_t* __restrict__ sizes_b, int32_t clen,
+                                                             int32_t* __restrict__ out_sizes, uint32_t* __restrict__ sel_tile_bytes, int64_t ntiles,
+                                                             int64_t out_cap, int group) {
   __shared__ uint16_t pos_sh[kWavesPerBlock][1024];
+  static_assert(sizeof pos_sh == 8192, "workgroup LDS of the sizes pass");
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
   uint16_t* pos = pos_sh[wib];
@@ -455,10 +429,13 @@ __global__ __launch_bounds__(kBlock) void k_str_gather_sizes(const uint64_t* __r
     const int64_t tile = c0 + __builtin_ctzll(todo);
     const uint32_t total = stage_tile_positions(bitmap, tile, pos, lane);
     const int64_t obase = (int64_t)prefix[tile];
-    const int32_t* ts = sizes + tile * kTile;
+    const int32_t* ta = sizes_a + tile * kTile;
+    const int32_t* tb = FILL == STR_FILL_COL ? sizes_b + tile * kTile : nullptr;
     uint32_t bsum = 0;
     for (uint32_t k = lane; k < total; k += 64) {
-      const int32_t sz = ts[pos[k]];
+      const uint32_t p = pos[k];
+      const int32_t sa = ta[p];
+      const int32_t sz = FILL == STR_FILL_NONE || sa >= 0 ? sa : (FILL == STR_FILL_COL ? tb[p] : clen);
       bsum += clamp_size(sz);
       if (obase + k < out_cap) out_sizes[obase + k] = sz;
     }
@@ -468,43 +445,23 @@ __global__ __launch_bounds__(kBlock) void k_str_gather_sizes(const uint64_t* __r
    }
   }
 }
-void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const int32_t* sizes, int32_t* out_sizes,
-                             uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap) {
-  const int64_t nt = (nrows + kTile - 1) / kTile;
-  if (nt == 0) return;
-  const int group = gather_group(nt);
-  hipLaunchKernelGGL(k_str_gather_sizes, dim3(grid_for((nt + group - 1) / group)), dim3(kBlock), 0, s, bitmap, prefix, sizes, out_sizes, sel_tile_bytes, nt, out_cap, group);
-}
 
-// the byte offset of every row of a tile from the tile's first byte (exclusive prefix of the clamped sizes of ALL its rows) -> pre[1024] in this wave's LDS:
-// 16 coalesced size loads + 16 in-register scans.  The caller fences before it reads
-__device__ __forceinline__ void stage_tile_prefix(const int32_t* sizes, int64_t base, int64_t nrows, int lane, uint32_t* pre) {
-  int32_t sz[16];
-#pragma unroll
-  for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? sizes[i] : 0; }
-  uint32_t run = 0;
-#pragma unroll
-  for (int j = 0; j < 16; j++) {
-    const uint32_t c = clamp_size(sz[j]);
-    const uint32_t incl = wave_incl_scan(c);
-    pre[j * 64 + lane] = run + incl - c;
-    run += __shfl(incl, 63, 64);
-  }
-}
-
-// pass 2: bytes.  The tile's per-row source offsets (exclusive prefix of the sizes of ALL rows) go to LDS once
-// (16 coalesced size loads + 16 in-register scans); then 64 selected rows at a time: destination offsets by a
-// wave prefix-sum of the selected sizes, and every lane copies its own string.
-__global__ __launch_bounds__(kBlock) void k_str_gather_bytes(const uint64_t* __restrict__ bitmap, const int32_t* __restrict__ sizes,
-                                                             const int64_t* __restrict__ tile_off, const uint8_t* __restrict__ bytes,
-                                                             const uint64_t* __restrict__ out_tile_off, uint8_t* __restrict__ out_bytes,
+// pass 2: bytes.  Per side, the byte offset of every row of the tile from the tile's first byte (exclusive prefix of the clamped sizes of ALL its rows) goes to
+// LDS once: 16 coalesced size loads + 16 in-register scans (STR_FILL_COL: 4 KB more per wave for b's).  Then 64 selected rows at a time: destination offsets by a
+// wave prefix-sum of the selected sizes, and every lane copies its own string out of a's arena, b's arena or the constant.
+template <StrFillKind FILL>
+__global__ __launch_bounds__(kBlock) void k_str_gather_bytes(const uint64_t* __restrict__ bitmap, StrSide a, StrSide b, const uint8_t* __restrict__ cbytes,
+                                                             uint32_t clen, const uint64_t* __restrict__ out_tile_off, uint8_t* __restrict__ out_bytes,
                                                              int64_t nrows, int64_t ntiles, int64_t out_cap, int group) {
+  constexpr bool TWO = FILL == STR_FILL_COL;
   __shared__ uint16_t pos_sh[kWavesPerBlock][1024];
-  __shared__ uint32_t pre_sh[kWavesPerBlock][1024];
+  __shared__ uint32_t pre_sh[TWO ? 2 : 1][kWavesPerBlock][1024];
+  static_assert(sizeof pos_sh + sizeof pre_sh == (TWO ? 40960 : 24576), "workgroup LDS of the bytes pass");
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
   uint16_t* pos = pos_sh[wib];
-  uint32_t* pre = pre_sh[wib];
+  uint32_t* pre_a = pre_sh[0][wib];
+  uint32_t* pre_b = pre_sh[TWO ? 1 : 0][wib];
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wib;
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
   for (int64_t c0 = wave * group; c0 < ntiles; c0 += nwaves * group) {      // (`group` tiles at a time, as in pass 1: a tile without selected BYTES has nothing to copy)
@@ -515,116 +472,22 @@ __global__ __launch_bounds__(kBlock) void k_str_gather_bytes(const uint64_t* __r
     const uint32_t total = stage_tile_positions(bitmap, tile, pos, lane);
     if (total == 0) { wave_lds_fence(); continue; }        // wave-uniform: late materialization of the arena
     const int64_t base = tile * kTile;
-    int32_t sz[16];
-#pragma unroll   // (stage_tile_prefix, spelled out: through the helper the compiler hoists and allocates differently here, and this kernel stays as it was measured)
-    for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? sizes[i] : 0; }
-    uint32_t run = 0;
+#pragma unroll   // (the loop written here, not in a helper: through one the compiler hoists and allocates differently, and the plain form stays as it was measured)
+    for (int side = 0; side < (TWO ? 2 : 1); side++) {
+      const int32_t* ss = side ? b.sizes : a.sizes;
+      uint32_t* pre = side ? pre_b : pre_a;
+      int32_t sz[16];
 #pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const uint32_t c = clamp_size(sz[j]);
-      const uint32_t incl = wave_incl_scan(c);
-      pre[j * 64 + lane] = run + incl - c;
-      run += __shfl(incl, 63, 64);
-    }
-    wave_lds_fence();
-    const uint8_t* sb = bytes + tile_off[tile];
-    int64_t drun = (int64_t)out_tile_off[tile];
-    const int32_t* ts = sizes + base;
-    for (uint32_t k0 = 0; k0 < total; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool valid = k < total;
-      const uint32_t p = valid ? pos[k] : 0u;
-      const uint32_t cs = valid ? clamp_size(ts[p]) : 0u;
-      const uint32_t incl = wave_incl_scan(cs);
-      if (cs) {
-        const uint8_t* sp = sb + pre[p];
-        const int64_t d0 = drun + (int64_t)(incl - cs);
-        if (d0 + cs <= out_cap) {
-          copy_string(out_bytes + d0, sp, cs);
-        }
+      for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? ss[i] : 0; }
+      uint32_t run = 0;
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const uint32_t c = clamp_size(sz[j]);
+        const uint32_t incl = wave_incl_scan(c);
+        pre[j * 64 + lane] = run + incl - c;
+        run += __shfl(incl, 63, 64);
       }
-      drun += (int64_t)__shfl(incl, 63, 64);
     }
-    wave_lds_fence();
-   }
-  }
-}
-void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes,
-                             const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap) {
-  const int64_t nt = (nrows + kTile - 1) / kTile;
-  if (nt == 0) return;
-  const int group = gather_group(nt);
-  hipLaunchKernelGGL(k_str_gather_bytes, dim3(grid_for((nt + group - 1) / group)), dim3(kBlock), 0, s, bitmap, sizes, tile_off, bytes, out_tile_off, out_bytes, nrows,
-                     nt, out_bytes_cap, group);
-}
-
-// ---------------------------------------------------------------- K6c: coalesce(a, b) as a String projection column
-// Row i of the result is a[i] unless a[i] is missing (size -1), else b[i] — b a String column of the same table (TWO) or one constant.  K6's two passes with a
-// source select per row: the sizes pass writes `sa >= 0 ? sa : (TWO ? sb : clen)` and adds up the clamped sizes per tile (a row missing on both sides stays
-// -1 and adds nothing); the bytes pass stages a's per-row source offsets in LDS, b's beside them (TWO: 4 KB more per wave), and every lane copies its row out
-// of a's arena, b's arena or the constant (device memory, padded for copy_string's 8-byte tail load).  Both passes read the columns' own sizes and bytes.
-struct StrSide { const int32_t* sizes; const int64_t* tile_off; const uint8_t* bytes; };
-
-template <bool TWO>
-__global__ __launch_bounds__(kBlock) void k_str_coalesce_sizes(const uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ prefix,
-                                                               const int32_t* __restrict__ sizes_a, const int32_t* __restrict__ sizes_b, int32_t clen,
-                                                               int32_t* __restrict__ out_sizes, uint32_t* __restrict__ sel_tile_bytes, int64_t ntiles,
-                                                               int64_t out_cap, int group) {
-  __shared__ uint16_t pos_sh[kWavesPerBlock][1024];
-  const int lane = lane_id();
-  const int wib = threadIdx.x >> 6;
-  uint16_t* pos = pos_sh[wib];
-  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wib;
-  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t c0 = wave * group; c0 < ntiles; c0 += nwaves * group) {      // (`group` tiles at a time, the empty ones skipped: see k_str_gather_sizes)
-   const int64_t tl = c0 + lane;
-   const bool mine = lane < group && tl < ntiles;
-   const bool some = mine && prefix[tl + 1] > prefix[tl];
-   if (mine && !some) sel_tile_bytes[tl] = 0;
-   for (uint64_t todo = __ballot(some); todo; todo &= todo - 1) {
-    const int64_t tile = c0 + __builtin_ctzll(todo);
-    const uint32_t total = stage_tile_positions(bitmap, tile, pos, lane);
-    const int64_t obase = (int64_t)prefix[tile];
-    const int32_t* ta = sizes_a + tile * kTile;
-    const int32_t* tb = TWO ? sizes_b + tile * kTile : nullptr;
-    uint32_t bsum = 0;
-    for (uint32_t k = lane; k < total; k += 64) {
-      const uint32_t p = pos[k];
-      const int32_t sa = ta[p];
-      const int32_t sz = sa >= 0 ? sa : (TWO ? tb[p] : clen);
-      bsum += clamp_size(sz);
-      if (obase + k < out_cap) out_sizes[obase + k] = sz;
-    }
-    bsum = wave_sum(bsum);
-    if (lane == 0) sel_tile_bytes[tile] = bsum;
-    wave_lds_fence();
-   }
-  }
-}
-
-template <bool TWO>
-__global__ __launch_bounds__(kBlock) void k_str_coalesce_bytes(const uint64_t* __restrict__ bitmap, StrSide a, StrSide b, const uint8_t* __restrict__ cbytes,
-                                                               uint32_t clen, const uint64_t* __restrict__ out_tile_off, uint8_t* __restrict__ out_bytes,
-                                                               int64_t nrows, int64_t ntiles, int64_t out_cap, int group) {
-  __shared__ uint16_t pos_sh[kWavesPerBlock][1024];
-  __shared__ uint32_t pre_sh[TWO ? 2 : 1][kWavesPerBlock][1024];
-  const int lane = lane_id();
-  const int wib = threadIdx.x >> 6;
-  uint16_t* pos = pos_sh[wib];
-  uint32_t* pre_a = pre_sh[0][wib];
-  uint32_t* pre_b = pre_sh[TWO ? 1 : 0][wib];
-  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wib;
-  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t c0 = wave * group; c0 < ntiles; c0 += nwaves * group) {
-   const int64_t tl = c0 + lane;
-   const bool some = lane < group && tl < ntiles && out_tile_off[tl + 1] > out_tile_off[tl];
-   for (uint64_t todo = __ballot(some); todo; todo &= todo - 1) {
-    const int64_t tile = c0 + __builtin_ctzll(todo);
-    const uint32_t total = stage_tile_positions(bitmap, tile, pos, lane);
-    if (total == 0) { wave_lds_fence(); continue; }
-    const int64_t base = tile * kTile;
-    stage_tile_prefix(a.sizes, base, nrows, lane, pre_a);
-    if (TWO) stage_tile_prefix(b.sizes, base, nrows, lane, pre_b);
     wave_lds_fence();
     const uint8_t* ba = a.bytes + a.tile_off[tile];
     const uint8_t* bb = TWO ? b.bytes + b.tile_off[tile] : cbytes;
@@ -636,9 +499,9 @@ __global__ __launch_bounds__(kBlock) void k_str_coalesce_bytes(const uint64_t* _
       const bool valid = k < total;
       const uint32_t p = valid ? pos[k] : 0u;
       const int32_t sa = valid ? tsa[p] : 0;
-      const bool from_a = sa >= 0;
-      uint32_t cs = 0;
-      if (valid) cs = from_a ? (uint32_t)sa : (TWO ? clamp_size(tsb[p]) : clen);
+      const bool from_a = FILL == STR_FILL_NONE || sa >= 0;
+      uint32_t cs = clamp_size(sa);
+      if (valid && !from_a) cs = TWO ? clamp_size(tsb[p]) : clen;
       const uint32_t incl = wave_incl_scan(cs);
       if (cs) {
         const uint8_t* sp = from_a ? ba + pre_a[p] : (TWO ? bb + pre_b[p] : bb);
@@ -652,25 +515,25 @@ __global__ __launch_bounds__(kBlock) void k_str_coalesce_bytes(const uint64_t* _
   }
 }
 
-void launch_str_coalesce_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const int32_t* sizes_a, const int32_t* sizes_b, int32_t clen,
-                               int32_t* out_sizes, uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap) {
+void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const StrSide& a, const StrFill& fill, int32_t* out_sizes,
+                             uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap) {
   const int64_t nt = (nrows + kTile - 1) / kTile;
   if (nt == 0) return;
   const int group = gather_group(nt);
   const dim3 g(grid_for((nt + group - 1) / group)), b(kBlock);
-  if (sizes_b) hipLaunchKernelGGL((k_str_coalesce_sizes<true>), g, b, 0, s, bitmap, prefix, sizes_a, sizes_b, clen, out_sizes, sel_tile_bytes, nt, out_cap, group);
-  else hipLaunchKernelGGL((k_str_coalesce_sizes<false>), g, b, 0, s, bitmap, prefix, sizes_a, sizes_b, clen, out_sizes, sel_tile_bytes, nt, out_cap, group);
+#define DFDB_SIZES(F) hipLaunchKernelGGL((k_str_gather_sizes<F>), g, b, 0, s, bitmap, prefix, a.sizes, fill.b.sizes, fill.clen, out_sizes, sel_tile_bytes, nt, out_cap, group)
+  switch (fill.kind) { case STR_FILL_NONE: DFDB_SIZES(STR_FILL_NONE); break; case STR_FILL_CONST: DFDB_SIZES(STR_FILL_CONST); break; default: DFDB_SIZES(STR_FILL_COL); break; }
+#undef DFDB_SIZES
 }
-void launch_str_coalesce_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes_a, const int64_t* tile_off_a, const uint8_t* bytes_a,
-                               const int32_t* sizes_b, const int64_t* tile_off_b, const uint8_t* bytes_b, const uint8_t* const_dev, int32_t clen,
-                               const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap) {
+void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const StrSide& a, const StrFill& fill, const uint64_t* out_tile_off, uint8_t* out_bytes,
+                             int64_t nrows, int64_t out_bytes_cap) {
   const int64_t nt = (nrows + kTile - 1) / kTile;
   if (nt == 0) return;
   const int group = gather_group(nt);
   const dim3 g(grid_for((nt + group - 1) / group)), b(kBlock);
-  const StrSide sa{sizes_a, tile_off_a, bytes_a}, sb{sizes_b, tile_off_b, bytes_b};
-  if (sizes_b) hipLaunchKernelGGL((k_str_coalesce_bytes<true>), g, b, 0, s, bitmap, sa, sb, const_dev, (uint32_t)clen, out_tile_off, out_bytes, nrows, nt, out_bytes_cap, group);
-  else hipLaunchKernelGGL((k_str_coalesce_bytes<false>), g, b, 0, s, bitmap, sa, sb, const_dev, (uint32_t)clen, out_tile_off, out_bytes, nrows, nt, out_bytes_cap, group);
+#define DFDB_BYTES(F) hipLaunchKernelGGL((k_str_gather_bytes<F>), g, b, 0, s, bitmap, a, fill.b, fill.const_dev, (uint32_t)fill.clen, out_tile_off, out_bytes, nrows, nt, out_bytes_cap, group)
+  switch (fill.kind) { case STR_FILL_NONE: DFDB_BYTES(STR_FILL_NONE); break; case STR_FILL_CONST: DFDB_BYTES(STR_FILL_CONST); break; default: DFDB_BYTES(STR_FILL_COL); break; }
+#undef DFDB_BYTES
 }
 
 // projection of a String column whose selected rows K5 kept (CAP): per 1024-row tile a contiguous copy of its sizes and bytes

@@ -113,6 +113,7 @@ void launch_gen_brand_bytes(hipStream_t s, const int32_t* sizes, const int64_t* 
                             int64_t row_first, int64_t n);
 
 // ---- strings (K4-K6) -------------------------------------------------------------------------------
+struct StrSide { const int32_t* sizes; const int64_t* tile_off; const uint8_t* bytes; };   // a String column on the device: int32 sizes, u64 byte offset per tile, arena
 // per-1024-row byte totals of max(size,0)  (first half of unsafe_remake_offsets!)
 void launch_str_tile_bytes(hipStream_t s, const int32_t* sizes, uint32_t* tile_bytes, int64_t nrows, uint32_t* max_tile_bytes = nullptr);   // (max: one zeroed device word)
 // K5: s OP "const" (EQ / NE / STARTSWITH / ENDSWITH) -> bitmap + counts.  mode: 0 EQ, 1 NE, 2 STARTSWITH, 3 ENDSWITH
@@ -130,22 +131,18 @@ void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_o
                       const uint8_t* pat_dev, int32_t patlen, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
                       bool and_existing, const StrCapture* cap = nullptr, uint32_t max_tile_bytes = 0);   // max_tile_bytes: Column::max_tile_bytes (0 = not known: probes straight from memory)
 // K5b: s1 OP s2 (CmpOp) over two String columns -> bitmap + counts; a row with a missing side (size -1) selects nothing
-void launch_str_pair(hipStream_t s, const int32_t* sizes_a, const int64_t* toff_a, const uint8_t* bytes_a, const int32_t* sizes_b, const int64_t* toff_b,
-                     const uint8_t* bytes_b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
+void launch_str_pair(hipStream_t s, const StrSide& a, const StrSide& b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
 void launch_str_compact_captured(hipStream_t s, const StrCapture& cap, const uint64_t* prefix, const int64_t* tile_off, const uint64_t* out_tile_off,
                                  int32_t* out_sizes, uint8_t* out_bytes, int64_t nrows, int64_t out_rows, int64_t out_bytes_cap);
-// K6: selected sizes -> out sizes (+ per-ctile selected byte totals); then bytes
-void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const int32_t* sizes, int32_t* out_sizes,
+// K6: the selected rows of String column `a` -> out sizes (+ per-ctile selected byte totals); then bytes.  StrFill says what stands behind a missing row
+// (size -1) of a: nothing (the plain projection, -1 goes out), a constant (const_dev: clen bytes and 8 of padding, read by the bytes pass only) or row i of a
+// second column b: coalesce(a, b).  One kernel pair in three forms (k_strings.hip)
+enum StrFillKind { STR_FILL_NONE = 0, STR_FILL_CONST = 1, STR_FILL_COL = 2 };
+struct StrFill { StrFillKind kind; StrSide b; const uint8_t* const_dev; int32_t clen; };
+void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const StrSide& a, const StrFill& fill, int32_t* out_sizes,
                              uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap);
-void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes,
-                             const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap);
-// K6c: coalesce(a, b) as a String column — a's row unless it is missing, else b's row (sizes_b set) or the constant (sizes_b null: const_dev holds clen
-// bytes and 8 of padding).  The same two passes and the same outputs as K6
-void launch_str_coalesce_sizes(hipStream_t s, const uint64_t* bitmap, const uint64_t* prefix, const int32_t* sizes_a, const int32_t* sizes_b, int32_t clen,
-                               int32_t* out_sizes, uint32_t* sel_tile_bytes, int64_t nrows, int64_t out_cap);
-void launch_str_coalesce_bytes(hipStream_t s, const uint64_t* bitmap, const int32_t* sizes_a, const int64_t* tile_off_a, const uint8_t* bytes_a,
-                               const int32_t* sizes_b, const int64_t* tile_off_b, const uint8_t* bytes_b, const uint8_t* const_dev, int32_t clen,
-                               const uint64_t* out_tile_off, uint8_t* out_bytes, int64_t nrows, int64_t out_bytes_cap);
+void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const StrSide& a, const StrFill& fill, const uint64_t* out_tile_off, uint8_t* out_bytes,
+                             int64_t nrows, int64_t out_bytes_cap);
 
 // n rows that all hold the same string: sizes[i] = plen, bytes = the pattern (device memory) n times
 void launch_fill_const_strings(hipStream_t s, int32_t* out_sizes, uint8_t* out_bytes, int64_t n, const uint8_t* pat_dev, int32_t plen);

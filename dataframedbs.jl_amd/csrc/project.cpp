@@ -72,18 +72,52 @@ static const void* gather_source(dfdb_query* q, int ord) {
   return (const void*)(a.buf.as<uint8_t>() - (intptr_t)a.first_row * w);
 }
 
-// ---------------------------------------------------------------- materialize
+// ---------------------------------------------------------------- String output columns
 static bool string_captured(const dfdb_query* q, const Column& col) {
   return q->left.cap_str_col >= 0 && &q->t->cols[(size_t)q->left.cap_str_col] == &col && reflects_all_stages(q);
 }
 
-// coalesce(a, b) with a String result (expr.hpp is_string_coalesce): the second side as K6c takes it — column b's sizes, or null and the constant's length
-static const Column* coalesce_second(dfdb_query* q, const Node& e) { return e.b->op == DFIR_COL ? &need_resident(q->t, e.b->col) : nullptr; }
+// What a String projection column is made of: column `a` and what stands behind its missing rows — nothing (the column itself), or the constant or the column b
+// of coalesce(a, b) (expr.hpp is_string_coalesce) — and which producer writes the selected rows:
+//   STR_CONST_FILL  every selected row holds the constant of a conjunct `a == "const"` (query.cpp run_str_step): the constant, count times
+//   STR_DICT        K9: the selected rows' dictionary codes, expanded
+//   STR_CAPTURED    K5 kept the selected rows while it matched: one contiguous copy per tile
+//   STR_GATHER      K6 reads the flat sizes and bytes through the bitmap, in the form of `fill`
+// What the execution left behind for a plain projection of `a` — K5's capture, "every selected row holds the constant", the compacted dictionary codes —
+// answers for a's own rows, not for the coalesced ones: a coalesce is always STR_GATHER
+enum StrProducer { STR_CONST_FILL, STR_DICT, STR_CAPTURED, STR_GATHER };
+struct StrSource { const Column* a; StrFillKind fill; const Column* b; const std::string* k; StrProducer by; };
 
-// selected string bytes per 1024-row tile -> exclusive scan (output arena offsets); returns total.  `co`: the column is coalesce(col, b), not col itself
-static int64_t string_out_offsets(dfdb_query* q, const Column& col, DevBuf& out_sizes_tmp, int32_t* out_sizes, int64_t cap, DevBuf& tile_off_out,
-                                  const Node* co = nullptr) {
+static StrSource string_source(dfdb_query* q, const Node& e) {
+  if (is_string_coalesce(e)) {
+    const Column& a = need_resident(q->t, e.a->col);
+    if (e.b->op == DFIR_COL) return StrSource{&a, STR_FILL_COL, &need_resident(q->t, e.b->col), nullptr, STR_GATHER};
+    return StrSource{&a, STR_FILL_CONST, nullptr, &e.b->str, STR_GATHER};
+  }
+  if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
+  const Column& a = need_resident(q->t, e.col);
+  const StrProducer by = q->left.const_str_col == e.col && reflects_all_stages(q) ? STR_CONST_FILL
+                         : a.dict_n > 0 ? STR_DICT : string_captured(q, a) ? STR_CAPTURED : STR_GATHER;
+  return StrSource{&a, STR_FILL_NONE, nullptr, nullptr, by};
+}
+static StrFill str_fill(const StrSource& src, const uint8_t* const_dev) {
+  return StrFill{src.fill, src.b ? str_side(*src.b) : StrSide{nullptr, nullptr, nullptr}, const_dev, src.k ? (int32_t)src.k->size() : 0};
+}
+
+// a constant on the device (q->tmp_a), with room behind it for copy_string's 8-byte tail load; waits for the upload (`k` may be gone after the call)
+static const uint8_t* upload_constant(dfdb_query* q, const std::string& k) {
+  dfdb_ctx* ctx = q->t->ctx;
+  DevBuf& kb = q->tmp_a; kb.ensure(k.size() + 64);
+  if (!k.empty()) { HIP_CHECK(hipMemcpyAsync(kb.p, k.data(), k.size(), hipMemcpyHostToDevice, ctx->stream)); stream_wait(ctx); }
+  return kb.as<uint8_t>();
+}
+
+// selected string bytes per 1024-row tile -> exclusive scan into tile_off_out (output arena offsets), the selected sizes -> dst_sizes (`cap` rows); returns
+// the byte total.  (STR_CONST_FILL has its total without a launch; STR_CAPTURED leaves dst_sizes to the copy)
+static int64_t string_out_offsets(dfdb_query* q, const StrSource& src, int32_t* dst_sizes, int64_t cap, DevBuf& tile_off_out) {
+  if (src.by == STR_CONST_FILL) return cap * (int64_t)q->left.const_str.size();
   dfdb_ctx* ctx = q->t->ctx; hipStream_t s = ctx->stream;
+  const Column& col = *src.a;
   const int64_t nct = ceil_div(q->t->nrows, kTileRows);
   DevBuf& tb = q->tmp_c; tb.ensure((size_t)(nct + 8) * 4);
   tile_off_out.ensure((size_t)(nct + 8) * 8);
@@ -95,18 +129,7 @@ static int64_t string_out_offsets(dfdb_query* q, const Column& col, DevBuf& out_
     stream_wait(ctx);
     return ctx->pinned_scalar[1];
   };
-  int32_t* dst_sizes = out_sizes;
-  if (!dst_sizes) { out_sizes_tmp.ensure((size_t)std::max<int64_t>(cap, 1) * 4); dst_sizes = out_sizes_tmp.as<int32_t>(); }
-  if (co) {
-    // K6c reads the flat sizes of both sides through the bitmap.  What the execution left behind for a plain projection of `col` — K5's capture, "every
-    // selected row holds the constant", the compacted dictionary codes — answers for col's own rows, not for the coalesced ones, and is not looked at
-    const Column* cb = coalesce_second(q, *co);
-    { LaunchTimer lt(ctx, "str_coalesce_sizes");
-      launch_str_coalesce_sizes(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), col.data.as<int32_t>(), cb ? cb->data.as<int32_t>() : nullptr,
-                                (int32_t)co->b->str.size(), dst_sizes, tb.as<uint32_t>(), q->t->nrows, cap); }
-    return scan_total(tb.as<uint32_t>(), nct);
-  }
-  if (col.dict_n > 0) {
+  if (src.by == STR_DICT) {
     // K9: the selected rows' codes, compacted by K3 (kept in q->dict_sel for the bytes pass), then sizes and byte totals per 1024 OUTPUT rows
     const int64_t n = std::min<int64_t>(cap, query_count(q, -1));
     const int64_t not_ = ceil_div(std::max<int64_t>(n, 1), kTileRows);
@@ -119,53 +142,80 @@ static int64_t string_out_offsets(dfdb_query* q, const Column& col, DevBuf& out_
     { LaunchTimer lt(ctx, "dict_expand_sizes"); launch_dict_expand_sizes(s, q->dict_sel.as<uint16_t>(), n, col.dict_len.as<int32_t>(), dst_sizes, otb.as<uint32_t>()); }
     return scan_total(otb.as<uint32_t>(), not_);
   }
-  if (string_captured(q, col)) return scan_total(q->cap_str_tb.as<uint32_t>(), nct);     // K5 kept the selected rows: their byte totals per tile are already there
-  { LaunchTimer lt(ctx, "str_gather_sizes");
-    launch_str_gather_sizes(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), col.data.as<int32_t>(), dst_sizes, tb.as<uint32_t>(), q->t->nrows, cap); }
+  if (src.by == STR_CAPTURED) return scan_total(q->cap_str_tb.as<uint32_t>(), nct);     // K5 kept the selected rows: their byte totals per tile are already there
+  { LaunchTimer lt(ctx, src.fill == STR_FILL_NONE ? "str_gather_sizes" : "str_coalesce_sizes");
+    launch_str_gather_sizes(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), str_side(col), str_fill(src, nullptr), dst_sizes, tb.as<uint32_t>(), q->t->nrows, cap); }
   return scan_total(tb.as<uint32_t>(), nct);
 }
+
+// the sizes staging buffer (q->str_sizes, reused across calls: hipFree would sync the device) for `cnt` rows
+static int32_t* string_sizes_staging(dfdb_query* q, int64_t cnt) { q->str_sizes.ensure((size_t)std::max<int64_t>(cnt, 1) * 4); return q->str_sizes.as<int32_t>(); }
 
 int64_t query_string_bytes(dfdb_query* q, int i) {
   ensure_executed_checked(q);
   if (i < 0 || (size_t)i >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", i);
   const Node& e = *q->proj[(size_t)i].expr;
   if (dt_base(e.dtype) != DFDB_STRING) return 0;
-  if (is_string_coalesce(e)) return string_out_offsets(q, need_resident(q->t, e.a->col), q->str_sizes, nullptr, query_count(q, -1), q->str_toff, &e);
-  if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
-  const Column& col = need_resident(q->t, e.col);
+  const StrSource src = string_source(q, e);
   const int64_t cnt = query_count(q, -1);
-  if (q->left.const_str_col == e.col && reflects_all_stages(q)) return cnt * (int64_t)q->left.const_str.size();
-  return string_out_offsets(q, col, q->str_sizes, nullptr, cnt, q->str_toff);
+  return string_out_offsets(q, src, string_sizes_staging(q, cnt), cnt, q->str_toff);
 }
 
-// the output column coalesce(a, b) over Strings: K6's two passes with a source select per row (k_strings.hip K6c).  No row raises
-static void materialize_str_coalesce(dfdb_query* q, const Node& e, int32_t p, dfdb_outcol& o, int64_t cnt) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  const bool dev = o.memkind == DFDB_MEM_DEVICE;
-  const Column& ca = need_resident(t, e.a->col);
-  const Column* cb = coalesce_second(q, e);
-  DevBuf &dsz = q->str_sizes, &toff = q->str_toff, &dbytes = q->str_bytes;
-  int32_t* d_sizes = dev ? (int32_t*)o.data : nullptr;
-  const int64_t total = string_out_offsets(q, ca, dsz, d_sizes, cnt, toff, &e);
-  if (!d_sizes) d_sizes = dsz.as<int32_t>();
-  o.nbytes = total;
-  if (total > o.bytes_cap) fail(DFDB_ERR_ARGUMENT, "output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)o.bytes_cap);
-  uint8_t* d_bytes = dev ? o.bytes : nullptr;
-  if (!dev) { dbytes.ensure((size_t)total + 64); d_bytes = dbytes.as<uint8_t>(); }
-  if (total > 0) {
-    const std::string& k = e.b->str;                 // (empty when b is a column)
-    DevBuf& kb = q->tmp_a; kb.ensure(k.size() + 64);   // the constant on the device, with room behind it for copy_string's 8-byte tail load
-    if (!cb && !k.empty()) { HIP_CHECK(hipMemcpyAsync(kb.p, k.data(), k.size(), hipMemcpyHostToDevice, s)); stream_wait(ctx); }
-    LaunchTimer lt(ctx, "str_coalesce_bytes");
-    launch_str_coalesce_bytes(s, q->bitmap.as<uint64_t>(), ca.data.as<int32_t>(), (const int64_t*)ca.tile_off.p, ca.bytes.as<uint8_t>(),
-                              cb ? cb->data.as<int32_t>() : nullptr, cb ? (const int64_t*)cb->tile_off.p : nullptr, cb ? cb->bytes.as<uint8_t>() : nullptr,
-                              kb.as<uint8_t>(), (int32_t)k.size(), toff.as<uint64_t>(), d_bytes, t->nrows, total);
+// Where the producers of a String output column write: the caller's own buffers (device output: stream-ordered, never waited on) or the query's staging
+// buffers (host output: copied back and waited for by finish()).  The sizes are there from the start, the bytes once the total is known
+struct StrOut {
+  dfdb_query* q; dfdb_outcol& o; int64_t cnt; bool dev;
+  int32_t* sizes; uint8_t* bytes = nullptr;
+  StrOut(dfdb_query* q_, dfdb_outcol& o_, int64_t cnt_)
+      : q(q_), o(o_), cnt(cnt_), dev(o_.memkind == DFDB_MEM_DEVICE), sizes(dev ? (int32_t*)o_.data : string_sizes_staging(q_, cnt_)) {}
+  void reserve_bytes(int32_t p, int64_t total) {
+    o.nbytes = total;
+    if (total > o.bytes_cap) fail(DFDB_ERR_ARGUMENT, "output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)o.bytes_cap);
+    bytes = dev ? o.bytes : (q->str_bytes.ensure((size_t)total + 64), q->str_bytes.as<uint8_t>());
   }
-  if (!dev) {
-    HIP_CHECK(hipMemcpyAsync(o.data, d_sizes, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-    if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, d_bytes, (size_t)total, hipMemcpyDeviceToHost, s));
+  void finish() {
+    if (dev) return;
+    dfdb_ctx* ctx = q->t->ctx;
+    HIP_CHECK(hipMemcpyAsync(o.data, sizes, (size_t)cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (o.nbytes > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, bytes, (size_t)o.nbytes, hipMemcpyDeviceToHost, ctx->stream));
     stream_wait(ctx);
   }
+};
+
+// one String output column (FlatStringsVector gather, FlatStringsVectors.jl:136-157; coalesce over Strings: no row raises)
+static void materialize_string(dfdb_query* q, const StrSource& src, int32_t p, dfdb_outcol& o, int64_t cnt) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const Column& col = *src.a;
+  DevBuf& toff = q->str_toff;
+  StrOut out(q, o, cnt);
+  const int64_t total = string_out_offsets(q, src, out.sizes, cnt, toff);
+  out.reserve_bytes(p, total);
+  switch (src.by) {
+    case STR_CONST_FILL: {
+      const uint8_t* pat = upload_constant(q, q->left.const_str);
+      LaunchTimer lt(ctx, "fill_const_strings");
+      launch_fill_const_strings(s, out.sizes, out.bytes, cnt, pat, (int32_t)q->left.const_str.size());
+    } break;
+    case STR_DICT:                     // the compacted codes of string_out_offsets -> bytes out of the dictionary
+      if (total > 0) {
+        LaunchTimer lt(ctx, "dict_expand_bytes");
+        launch_dict_expand_bytes(s, q->dict_sel.as<uint16_t>(), cnt, col.dict_len.as<int32_t>(), col.dict_off.as<uint32_t>(), col.dict_bytes.as<uint8_t>(), toff.as<uint64_t>(), out.bytes, total);
+      }
+      break;
+    case STR_CAPTURED: {               // sizes and bytes: one contiguous copy per tile out of the match pass's capture
+      LaunchTimer lt(ctx, "str_compact_captured");
+      const StrCapture sc{q->cap_str_sizes.as<int32_t>(), q->cap_str_bytes.as<uint8_t>(), q->cap_str_tb.as<uint32_t>()};
+      launch_str_compact_captured(s, sc, q->prefix.as<uint64_t>(), (const int64_t*)col.tile_off.p, toff.as<uint64_t>(), out.sizes, out.bytes, t->nrows, cnt, total);
+    } break;
+    case STR_GATHER:
+      if (total > 0) {
+        const StrFill fill = str_fill(src, src.fill == STR_FILL_CONST ? upload_constant(q, *src.k) : nullptr);
+        LaunchTimer lt(ctx, src.fill == STR_FILL_NONE ? "str_gather_bytes" : "str_coalesce_bytes");
+        launch_str_gather_bytes(s, q->bitmap.as<uint64_t>(), str_side(col), fill, toff.as<uint64_t>(), out.bytes, t->nrows, total);
+      }
+      break;
+  }
+  out.finish();
 }
 
 // one output column of the projection (ProjectionExecutor.eval_on_range for column p: projection.jl:128-154)
@@ -177,61 +227,15 @@ void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
   const int w = dt_width(e.dtype);
   if (cnt == 0) return;
   if (!o.data) fail(DFDB_ERR_ARGUMENT, "output column %d has no data buffer", p);
+  if (dt_base(e.dtype) == DFDB_STRING) { materialize_string(q, string_source(q, e), p, o, cnt); return; }
   if (e.op == DFIR_COL) {   // ColProjExec: buffer .= data[name][range] (projection.jl:130-133)
     const void* gsrc = nullptr;
-    if (t->cols[(size_t)e.col].comp_only && !dt_nullable(e.dtype) && dt_base(e.dtype) != DFDB_STRING) {
+    if (t->cols[(size_t)e.col].comp_only && !dt_nullable(e.dtype)) {
       if (!t->cols[(size_t)e.col].resident) fail(DFDB_ERR_ARGUMENT, "column %s is not resident on the device (dfdb_table_load it first)", t->cols[(size_t)e.col].name.c_str());
       gsrc = gather_source(q, e.col);        // compressed-only: the blocks with survivors, decoded for this query (no whole-column decode)
     }
     const Column& col = gsrc ? t->cols[(size_t)e.col] : need_resident(t, e.col);
     if (!gsrc) gsrc = col.data.p;
-    if (dt_base(e.dtype) == DFDB_STRING) {   // FlatStringsVector gather (FlatStringsVectors.jl:136-157)
-      if (q->left.const_str_col == e.col && reflects_all_stages(q)) {   // every selected row holds the constant (query.cpp run_str_step)
-        const int64_t plen = (int64_t)q->left.const_str.size(), total = cnt * plen;
-        o.nbytes = total;
-        if (total > o.bytes_cap) fail(DFDB_ERR_ARGUMENT, "output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)o.bytes_cap);
-        DevBuf &csz = q->str_sizes, &cby = q->str_bytes;
-        int32_t* d_sizes = dev ? (int32_t*)o.data : (csz.ensure((size_t)cnt * 4), csz.as<int32_t>());
-        uint8_t* d_bytes = dev ? o.bytes : (cby.ensure((size_t)total + 64), cby.as<uint8_t>());
-        DevBuf& pb = q->tmp_a; pb.ensure((size_t)plen + 64);
-        if (plen) { HIP_CHECK(hipMemcpyAsync(pb.p, q->left.const_str.data(), (size_t)plen, hipMemcpyHostToDevice, s)); stream_wait(ctx); }
-        { LaunchTimer lt(ctx, "fill_const_strings"); launch_fill_const_strings(s, d_sizes, d_bytes, cnt, pb.as<uint8_t>(), (int32_t)plen); }
-        if (!dev) {
-          HIP_CHECK(hipMemcpyAsync(o.data, d_sizes, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-          if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, d_bytes, (size_t)total, hipMemcpyDeviceToHost, s));
-          stream_wait(ctx);
-        }
-        return;
-      }
-      DevBuf &dsz = q->str_sizes, &toff = q->str_toff, &dbytes = q->str_bytes;   // reused across calls (hipFree would sync the device)
-      int32_t* d_sizes = dev ? (int32_t*)o.data : nullptr;
-      const int64_t total = string_out_offsets(q, col, dsz, d_sizes, cnt, toff);
-      if (!d_sizes) d_sizes = dsz.as<int32_t>();
-      o.nbytes = total;
-      if (total > o.bytes_cap) fail(DFDB_ERR_ARGUMENT, "output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)o.bytes_cap);
-      uint8_t* d_bytes = dev ? o.bytes : nullptr;
-      if (!dev) { dbytes.ensure((size_t)total + 64); d_bytes = dbytes.as<uint8_t>(); }
-      if (col.dict_n > 0) {              // K9: the compacted codes of string_out_offsets -> bytes out of the dictionary
-        if (total > 0) {
-          LaunchTimer lt(ctx, "dict_expand_bytes");
-          launch_dict_expand_bytes(s, q->dict_sel.as<uint16_t>(), cnt, col.dict_len.as<int32_t>(), col.dict_off.as<uint32_t>(), col.dict_bytes.as<uint8_t>(), toff.as<uint64_t>(), d_bytes, total);
-        }
-      } else if (string_captured(q, col)) {     // sizes and bytes: one contiguous copy per tile out of the match pass's capture
-        LaunchTimer lt(ctx, "str_compact_captured");
-        const StrCapture sc{q->cap_str_sizes.as<int32_t>(), q->cap_str_bytes.as<uint8_t>(), q->cap_str_tb.as<uint32_t>()};
-        launch_str_compact_captured(s, sc, q->prefix.as<uint64_t>(), (const int64_t*)col.tile_off.p, toff.as<uint64_t>(), d_sizes, d_bytes, t->nrows, cnt, total);
-      } else if (total > 0) {
-        LaunchTimer lt(ctx, "str_gather_bytes");
-        launch_str_gather_bytes(s, q->bitmap.as<uint64_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                                toff.as<uint64_t>(), d_bytes, t->nrows, total);
-      }
-      if (!dev) {
-        HIP_CHECK(hipMemcpyAsync(o.data, d_sizes, (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-        if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, d_bytes, (size_t)total, hipMemcpyDeviceToHost, s));
-        stream_wait(ctx);
-      }
-      return;
-    }
     DevBuf stage; void* dst = o.data;
     if (!dev) { stage.ensure((size_t)cnt * w); dst = stage.p; }
     if ((q->left.cap_col == e.col || q->left.cap_col2 == e.col) && w == 8 && reflects_all_stages(q)) {   // the scan kept these values: contiguous copy per tile
@@ -250,8 +254,6 @@ void materialize_col(dfdb_query* q, int32_t p, dfdb_outcol& o, int64_t cnt) {
     }
     if (!dev) stream_wait(ctx);   // staging buffers die at scope exit; device outputs stay stream-ordered, no host wait
   } else {                  // BroadcastExecutor: computed column (projection.jl:128-129)
-    if (is_string_coalesce(e)) { materialize_str_coalesce(q, e, p, o, cnt); return; }
-    if (dt_base(e.dtype) == DFDB_STRING) fail(DFDB_ERR_UNSUPPORTED, "computed String columns are outside the IR");
     DevBuf stage, mstage; void* dst = o.data;
     if (!dev) { stage.ensure((size_t)cnt * w); dst = stage.p; }
     uint8_t* mdst = nullptr;                               // Union{R,Missing} result: one flag byte per selected row

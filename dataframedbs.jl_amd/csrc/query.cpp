@@ -544,8 +544,7 @@ static void run_pair_step(dfdb_query* q, const PairStep& pt, bool have) {
   const Column &ca = t->cols[(size_t)pt.a], &cb = t->cols[(size_t)pt.b];
   if (ca.dict_n > 0 && cb.dict_n > 0) { run_dict_pair(q, ca, cb, pt.op, have); return; }      // (a dictionary column is never nullable)
   LaunchTimer lt(ctx, "str_pair");
-  launch_str_pair(ctx->stream, ca.data.as<int32_t>(), (const int64_t*)ca.tile_off.p, ca.bytes.as<uint8_t>(), cb.data.as<int32_t>(), (const int64_t*)cb.tile_off.p,
-                  cb.bytes.as<uint8_t>(), pt.op, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have);
+  launch_str_pair(ctx->stream, str_side(ca), str_side(cb), pt.op, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have);
 }
 // a compressed-only column: one K7 launch per term — every block decoded into the waves' history rings, the comparison applied to the bytes as they leave
 // the LDS ring, bitmap + tile counts the only output.  From the second mask on the words are AND-ed in and a block without a survivor

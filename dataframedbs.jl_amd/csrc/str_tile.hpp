@@ -1,4 +1,5 @@
-// str_tile.hpp — the walk of a String column one wave per 1024-row tile, as k_parse.hip and k_strings.hip share it.  Device only.
+// str_tile.hpp — the walk of a String column one wave per 1024-row tile, and the moves of single strings, as k_parse.hip, k_strings.hip and k_dict.hip share
+// them.  Device only.
 //
 // A tile is sixteen steps of 64 rows: row j * 64 + lane of the tile belongs to lane `lane` in step j, step j makes word j of the tile's bitmap, and lanes
 // 0..15 hold the tile's sixteen words.  The layout of a String column (sizes, one arena, one byte offset per tile) is at the head of k_strings.hip.
@@ -11,6 +12,37 @@ namespace dfdb {
 static_assert(kTileRows == 16 * 64 && kTileWords == 16, "a tile is sixteen 64-row steps of one wave, one bitmap word per step");
 
 __device__ __forceinline__ uint32_t clamp_size(int32_t s) { return s > 0 ? (uint32_t)s : 0u; }   // the bytes of a row (a missing row, -1, has none)
+
+__device__ __forceinline__ uint64_t load_u64_unaligned(const uint8_t* p) {
+  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
+  return *(const u64u*)p;
+}
+// exact copy of one string (len bytes): unaligned 8-byte moves, then ONE 8-byte load (the arenas are padded) and <= 3 stores
+__device__ __forceinline__ void copy_string(uint8_t* dp, const uint8_t* sp, uint32_t len) {
+  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
+  typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
+  typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
+  uint32_t b = 0;
+  for (; b + 8 <= len; b += 8) *(u64u*)(dp + b) = *(const u64u*)(sp + b);
+  const uint32_t rem = len - b;
+  if (rem) {
+    uint64_t v = *(const u64u*)(sp + b);
+    uint8_t* d = dp + b;
+    if (rem & 4u) { *(u32u*)d = (uint32_t)v; d += 4; v >>= 32; }
+    if (rem & 2u) { *(u16u*)d = (uint16_t)v; d += 2; v >>= 16; }
+    if (rem & 1u) *d = (uint8_t)v;
+  }
+}
+// the low `len` (<= 8) bytes of v
+__device__ __forceinline__ void store_small(uint8_t* d, uint64_t v, uint32_t len) {
+  typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
+  typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
+  typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
+  if (len >= 8u) { *(u64u*)d = v; return; }
+  if (len & 4u) { *(u32u*)d = (uint32_t)v; d += 4; v >>= 32; }
+  if (len & 2u) { *(u16u*)d = (uint16_t)v; d += 2; v >>= 16; }
+  if (len & 1u) *d = (uint8_t)v;
+}
 
 // the sizes of the tile's rows, sixteen loads in flight; `past` stands for the rows behind the column's last.  NT: the loads are non-temporal
 template <bool NT = true>

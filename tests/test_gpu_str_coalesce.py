@@ -1,4 +1,4 @@
-"""coalesce(a, b) with a String result on the device (include/dfdb_ir.h DFIR_COALESCE; csrc/k_strings.hip K6c): a String column leaf, then a string constant
+"""coalesce(a, b) with a String result on the device (include/dfdb_ir.h DFIR_COALESCE; csrc/k_strings.hip K6, the filled forms): a String column leaf, then a string constant
 or a second String column, as a whole projection column.  The yardstick is tests/str_coalesce_cases.py (pinned by tests/test_str_coalesce_cpu.py), applied to
 the lists the columns were made of; every comparison is bit-exact: the sizes array (-1 for missing), the byte arena, the string-bytes total and the count."""
 import ctypes as C
@@ -349,3 +349,62 @@ def test_out_of_core_gives_the_same_answers(oracle, dfdb_mod, ctx, data, tmp_pat
         for tb in (t2, t3, lazy):
             tb.close()
         c2.close()
+
+
+# ---------------------------------------------------------------- a wave that takes two tiles at a time
+GATHER_PASSES = ("str_gather_sizes", "str_gather_bytes", "str_coalesce_sizes", "str_coalesce_bytes")
+
+
+def launches(ctx, fn):
+    """(what fn returns, launches per profile name of the K6 passes while it ran)"""
+    ctx.profile(True)
+    try:
+        before = {k: ctx.profile_get(k)[0] for k in GATHER_PASSES}
+        out = fn()
+        return out, {k: ctx.profile_get(k)[0] - before[k] for k in GATHER_PASSES}
+    finally:
+        ctx.profile(False)
+
+
+def test_two_tiles_per_wave_plain_and_coalesce(oracle, dfdb_mod, ctx):
+    """From 16 384 tiles on, a wave of either K6 pass looks at `group` >= 2 tiles together (k_strings.hip gather_group).  16 386 tiles, the last one ragged:
+    group is 2, the pairs are tiles (2m, 2m + 1).  The selection keeps rows in a few tiles only, so nearly every pair is empty and skipped: row 1; 200 rows
+    over the boundary inside pair (2000, 2001), 100 per tile (more than one round of 64); 100 rows in tile 10001, whose partner 10000 is empty; the last
+    1025 rows (a whole tile and the one-row ragged tile, which are a pair).  The columns are generated on the device."""
+    from dfdb import ir
+    n = 16384 * 1024 + 1025
+    seed, seed2 = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03
+    windows = [(0, 1), (2001 * 1024 - 100, 200), (10001 * 1024 + 300, 100), (n - 1025, 1025)]          # (first row, rows), rows counted from 0
+    t = dfdb_mod.DFTable.new()
+    try:
+        t.add_generated("s", dfdb_mod.GEN_STR_BRANDS10, seed, n)
+        t.add_generated("sm", dfdb_mod.GEN_STR_BRANDS10_MISSING, seed, n)
+        t.add_generated("s2", dfdb_mod.GEN_STR_BRANDS10, seed2, n)
+        t.add_generated("i", dfdb_mod.GEN_I64_IOTA, 0, n)                                               # i = the row number, from 1
+        i, pred = ir.col(t.ordinal("i")), None
+        for r0, k in windows:
+            term = (i >= r0 + 1) & (i <= r0 + k)
+            pred = term if pred is None else pred | term
+        v = dfdb_mod.DFView(t)[pred, dfdb_mod.ALL]
+        want_s = []
+        for r0, k in windows:
+            want_s += unflat(*oracle.gen_str(seed, r0, k))
+        assert len(want_s) == sum(k for _, k in windows)
+
+        q, ran = launches(ctx, lambda: check(dfdb_mod, t, want_s, v[dfdb_mod.ALL, ["s"]]))
+        assert ran["str_gather_sizes"] >= 1 and ran["str_gather_bytes"] == 1 and ran["str_coalesce_sizes"] == 0 and ran["str_coalesce_bytes"] == 0, ran
+        plain_s = q.materialize()[0]
+        (sm_sizes, sm_arena), (s2_sizes, s2_arena) = v[dfdb_mod.ALL, ["sm", "s2"]]._query().materialize()
+        got_sm, got_s2 = unflat(sm_sizes, sm_arena), unflat(s2_sizes, s2_arena)
+        assert any(x is None for x in got_sm) and any(x is not None for x in got_sm)
+        assert got_s2 == [x for r0, k in windows for x in unflat(*oracle.gen_str(seed2, r0, k))]
+
+        q, ran = launches(ctx, lambda: check(dfdb_mod, t, want_s, v[dfdb_mod.ALL, project(dfdb_mod, t, "s", b"")]))     # a non-nullable a: the column itself
+        assert ran["str_coalesce_sizes"] >= 1 and ran["str_coalesce_bytes"] == 1 and ran["str_gather_sizes"] == 0 and ran["str_gather_bytes"] == 0, ran
+        got = q.materialize()[0]
+        assert np.array_equal(got[0], plain_s[0]) and np.array_equal(got[1], plain_s[1])
+        for b, second in (("s2", got_s2), (b"?", b"?")):
+            _, ran = launches(ctx, lambda: check(dfdb_mod, t, coalesce_ref(got_sm, second), v[dfdb_mod.ALL, project(dfdb_mod, t, "sm", b)]))
+            assert ran["str_coalesce_sizes"] >= 1 and ran["str_coalesce_bytes"] == 1 and ran["str_gather_sizes"] == 0 and ran["str_gather_bytes"] == 0, ran
+    finally:
+        t.close()

@@ -8,9 +8,9 @@ HIP events on the engine stream (dfdb_ctx_timer_*); reported are the median and 
 from the per-launch profile (dfdb_ctx_profile_*) of one more call per leg, outside the rounds.  GB/s counts the algorithmic bytes per row (4 of size in, the
 bytes in, 4 of size out, the bytes out) against the 8 TB/s peak.
 
-  plain copy              add_column of the column s itself into a new resident column (K6: k_str_gather_sizes / _bytes): the baseline, which the parent commit
-                          runs too; it moves the same sizes and the same bytes
-  coalesce(s, "")         add_column of coalesce.(s, "") (K6c: k_str_coalesce_sizes / _bytes, the constant form)
+  plain copy              add_column of the column s itself into a new resident column (K6: k_str_gather_sizes / _bytes in the plain form): the baseline; it
+                          moves the same sizes and the same bytes
+  coalesce(s, "")         add_column of coalesce.(s, "") (the same kernel pair in the constant form; profile names str_coalesce_sizes / _bytes)
   coalesce(s, s2)         add_column of coalesce.(s, s2), s2 a second column of the same strings shifted by one row (the two-column form: 4 KB more LDS per wave)
 
 The last line applies the expectation: the coalesce leg's median lies within the two spreads combined of the plain copy's; a larger gap means the per-row
