@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "../../include/dfdb.h"
+#include "value_rules.hpp"
 
 namespace dfdb {
 
@@ -31,8 +32,11 @@ struct Error : std::runtime_error {
 inline int dt_base(int32_t dt) { return dt & DFDB_DTYPE_MASK; }
 inline bool dt_nullable(int32_t dt) { return (dt & DFDB_NULLABLE) != 0; }
 inline bool dt_isint(int32_t dt) { int b = dt_base(dt); return b >= DFDB_I8 && b <= DFDB_U64; }
-inline bool dt_issigned(int32_t dt) { int b = dt_base(dt); return b >= DFDB_I8 && b <= DFDB_I64; }
-inline bool dt_isfloat(int32_t dt) { int b = dt_base(dt); return b == DFDB_F32 || b == DFDB_F64; }
+inline bool dt_issigned(int32_t dt) { return is_signed(dt_base(dt)); }      // (value_rules.hpp states the rules on base dtypes; these take a column's full dtype)
+inline bool dt_isfloat(int32_t dt) { return is_float(dt_base(dt)); }
+// the dtype a whole-column sum / minimum / maximum is reduced and returned in (it reaches the exchange callback).  Not kind_dtype(value_kind(dt)): the narrow
+// unsigned types and Bool report Int64 here — their sums and extremes read the same either way
+inline int agg_dtype(int32_t dt) { return dt_isfloat(dt) ? DFDB_F64 : (dt_base(dt) == DFDB_U64 ? DFDB_U64 : DFDB_I64); }
 inline bool dt_isnum(int32_t dt) { return dt_isint(dt) || dt_isfloat(dt) || dt_base(dt) == DFDB_BOOL; }
 int dt_width(int32_t dt);
 std::string dt_name(int32_t dt);

@@ -258,13 +258,8 @@ static int flip(int op) {  // c OP x  ==  x flip(OP) c
 
 struct IntRange { __int128 lo, hi; };
 static IntRange int_range(int dt) {
-  switch (dt_base(dt)) {
-    case DFDB_I8: return {-128, 127}; case DFDB_I16: return {-32768, 32767};
-    case DFDB_I32: return {-(__int128)2147483648LL, 2147483647}; case DFDB_I64: return {(__int128)INT64_MIN, (__int128)INT64_MAX};
-    case DFDB_U8: return {0, 255}; case DFDB_U16: return {0, 65535}; case DFDB_U32: return {0, 4294967295LL};
-    case DFDB_BOOL: return {0, 1};
-    default: return {0, (__int128)UINT64_MAX};
-  }
+  if (dt_base(dt) == DFDB_BOOL) return {0, 1};
+  return {(__int128)int_lo(dt_base(dt)), (__int128)int_hi(dt_base(dt))};
 }
 static uint64_t int_bits(__int128 v) { return (uint64_t)v; }
 

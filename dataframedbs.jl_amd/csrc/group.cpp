@@ -281,7 +281,7 @@ static void group_alloc_exchange(dfdb_group* g) {
 static ncclDataType_t nccl_type(int dt) { return dt == DFDB_F64 ? ncclFloat64 : (dt == DFDB_U64 ? ncclUint64 : ncclInt64); }
 static ncclRedOp_t nccl_op(int op) { return op == DFDB_AGG_MIN ? ncclMin : (op == DFDB_AGG_MAX ? ncclMax : ncclSum); }
 
-// (fold_f64 / fold_bits: ooc.cpp — Julia's NaN and signed-zero rules, wrapping Int sums; shared with the block-streamed merges)
+// (fold_bits: ooc.cpp — wrapping Int sums, value_rules.hpp's Float64 min / max; shared with the block-streamed merges)
 
 // stream-ordered host value -> slot of shard l
 static void put_slot(dfdb_group* g, int l, int slot, int64_t v) {
@@ -963,7 +963,7 @@ int32_t dfdb_group_aggregate(dfdb_gquery* gq, int32_t op, int32_t i, int64_t* ou
     });
     // the accumulator type follows from the projection's dtype, which every shard shares (a shard that failed before it could say still knows it)
     const int32_t pdt = i >= 0 && (size_t)i < gq->shard[0]->proj.size() ? dt_base(gq->shard[0]->proj[(size_t)i].expr->dtype) : DFDB_I64;
-    const int dt = dt_isfloat(pdt) ? DFDB_F64 : (pdt == DFDB_U64 ? DFDB_U64 : DFDB_I64);      // = what query_aggregate_device returns
+    const int dt = agg_dtype(pdt);      // = what query_aggregate_device returns
     for (int d : dts) if (d != dt && g->fault_key == ~0ull) fail(DFDB_ERR_DEVICE, "shards disagree on the accumulator type");
     int64_t res[2] = {0, 0};
     if (dt == DFDB_F64 && op != DFDB_AGG_SUM && (g->exchange == DFDB_EXCHANGE_RCCL || g->exchange == DFDB_EXCHANGE_CALLBACK) && exchanges(g)) {
@@ -1274,6 +1274,29 @@ int32_t dfdb_selftest(const char* name, int64_t arg, int64_t* out, int32_t nout)
       st_fail_at = 0;
       const int64_t second = one();
       out[0] = st_starts; out[1] = st_ends; out[2] = st_calls; out[3] = first; out[4] = second; out[5] = cs.dead ? 1 : 0;
+      return;
+    }
+    if (!strcmp(name, "value_rules")) {
+      // the host side of value_rules.hpp (the text the kernels compile): arg = function | parameter << 8 | is_min << 16, operands in out as bit patterns (a
+      // narrow column value in the low bytes), results in place
+      const int fn = (int)(arg & 0xff), par = (int)((arg >> 8) & 0xff); const bool is_min = ((arg >> 16) & 1) != 0;
+      if (nout < 1 || (fn == 3 && (nout & 1))) fail(DFDB_ERR_ARGUMENT, "ArgumentError: value_rules works on at least one operand (minmax_f64: on pairs)");
+      for (int32_t i = 0; i < nout; i++) {
+        const uint64_t x = (uint64_t)out[i];
+        switch (fn) {
+          case 0: out[i] = (int64_t)key_image(&x, par, 0); break;
+          case 1: out[i] = (int64_t)value_image(&x, par, 0); break;
+          case 2: out[i] = (int64_t)order_image(x, par, is_min); break;
+          case 3: { if (i & 1) break; double a, b; memcpy(&a, &out[i], 8); memcpy(&b, &out[i + 1], 8); const double r = minmax_f64(a, b, is_min); memcpy(&out[i], &r, 8); } break;
+          case 4: out[i] = int_lo(par); break;
+          case 5: out[i] = (int64_t)int_hi(par); break;
+          case 6: out[i] = wrap_int((int64_t)x, par); break;
+          case 7: out[i] = value_kind(par); break;
+          case 8: out[i] = kind_dtype(par); break;
+          case 9: out[i] = (int64_t)reduce_identity_bits(par, x == DFDB_AGG_MIN, x == DFDB_AGG_MAX); break;
+          default: fail(DFDB_ERR_ARGUMENT, "ArgumentError: value_rules has no function %d", fn);
+        }
+      }
       return;
     }
     fail(DFDB_ERR_ARGUMENT, "ArgumentError: no self-test named %s", name);

@@ -142,7 +142,7 @@ std::string disk_path(const JitKernel& k, const std::string& arch, const char* c
   uint64_t h1 = 0xCBF29CE484222325ull, h2 = 0x84222325CBF29CE4ull;
   auto mix = [&](const void* p, size_t n) { h1 = fnv1a(p, n, h1); h2 = fnv1a(p, n, h2 ^ 0x9E3779B97F4A7C15ull); };
   mix(k.source.data(), k.source.size());
-  for (const char* t : {src_device_utils_hpp, src_k_interp_handlers_inc, src_k_interp_step_inc, src_k_interp_device_inc, src_dfdb_ir_h}) mix(t, strlen(t));
+  for (const char* t : {src_device_utils_hpp, src_value_rules_hpp, src_k_interp_handlers_inc, src_k_interp_step_inc, src_k_interp_device_inc, src_dfdb_ir_h}) mix(t, strlen(t));
   mix(arch.data(), arch.size());
   for (int i = 0; i < nopts; i++) mix(opts[i], strlen(opts[i]));
   char name[64];
@@ -191,13 +191,13 @@ void compile_one(JitKernel& k) {
     cache().from_disk++; k.state = 1; return;
   }
   hiprtcProgram prog = nullptr;
-  const char* headers[] = {src_device_utils_hpp, src_k_interp_handlers_inc, src_k_interp_step_inc, src_k_interp_device_inc, src_dfdb_ir_h, nullptr};
-  const char* names[] = {"device_utils.hpp", "k_interp_handlers.inc", "k_interp_step.inc", "k_interp_device.inc", "dfdb_ir.h", "jit_steps.inc"};
+  const char* headers[] = {src_device_utils_hpp, src_value_rules_hpp, src_k_interp_handlers_inc, src_k_interp_step_inc, src_k_interp_device_inc, src_dfdb_ir_h, nullptr};
+  const char* names[] = {"device_utils.hpp", "value_rules.hpp", "k_interp_handlers.inc", "k_interp_step.inc", "k_interp_device.inc", "dfdb_ir.h", "jit_steps.inc"};
   // the per-program include (`#define PC n / #include "k_interp_step.inc"` for every instruction) travels at the front of the source, up to a marker line
   const size_t cut = k.source.find("//@@STEPS-END\n");
   const std::string steps = k.source.substr(0, cut), main_src = k.source.substr(cut + 14);
-  headers[5] = steps.c_str();
-  if (r.CreateProgram(&prog, main_src.c_str(), "dfdb_jit.hip", 6, headers, names) != HIPRTC_SUCCESS) { k.log = "hiprtcCreateProgram failed"; k.state = -1; return; }
+  headers[6] = steps.c_str();
+  if (r.CreateProgram(&prog, main_src.c_str(), "dfdb_jit.hip", 7, headers, names) != HIPRTC_SUCCESS) { k.log = "hiprtcCreateProgram failed"; k.state = -1; return; }
   const hiprtcResult rc = r.CompileProgram(prog, 5, opts);
   size_t n = 0;
   if (r.GetProgramLogSize(prog, &n) == HIPRTC_SUCCESS && n > 1) { k.log.resize(n); r.GetProgramLog(prog, &k.log[0]); }
@@ -322,7 +322,7 @@ std::shared_ptr<JitKernel> jit_request(dfdb_ctx* ctx, const JitShape& sh, bool w
            "typedef unsigned char uint8_t; typedef unsigned short uint16_t; typedef unsigned int uint32_t; typedef unsigned long uint64_t;\n"
            "typedef unsigned long uintptr_t;\n";
       s += "#ifndef INT64_MIN\n#define INT64_MIN (-9223372036854775807L - 1)\n#endif\n";
-      s += "#include \"dfdb_ir.h\"\n#include \"device_utils.hpp\"\n";
+      s += "#include \"dfdb_ir.h\"\n#include \"device_utils.hpp\"\n#include \"value_rules.hpp\"\n";
       std::vector<int64_t> v;
       auto tab = [&](const char* type, const char* name, auto&& src, bool hex) { v.clear(); for (auto x : src) v.push_back((int64_t)x); table_fn(s, type, name, v, hex); };
       tab("unsigned", "jit_w0", sh.w0, true); tab("unsigned", "jit_w1", sh.w1, true); tab("unsigned", "jit_w2", sh.w2, true);

@@ -14,6 +14,7 @@
 // the gathers (K3) keep the one-ctile form.
 //   algorithmic bytes / row: 1/8 (bitmap) + sigma * 8 (index)  |  gather: 1/8 + sigma * 2 * width
 #include "device_utils.hpp"
+#include "value_rules.hpp"
 #include "kernels.hpp"
 #include "../../include/dfdb_ir.h"
 
@@ -393,28 +394,13 @@ template <> struct Acc<uint8_t> { using type = uint64_t; }; template <> struct A
 template <> struct Acc<uint32_t> { using type = uint64_t; }; template <> struct Acc<uint64_t> { using type = uint64_t; };
 template <> struct Acc<float> { using type = double; };     template <> struct Acc<double> { using type = double; };
 
-template <typename A> __device__ __forceinline__ A red_identity(int op);
-template <> __device__ __forceinline__ int64_t red_identity<int64_t>(int op) { return op == DFDB_AGG_MIN ? INT64_MAX : (op == DFDB_AGG_MAX ? INT64_MIN : 0); }
-template <> __device__ __forceinline__ uint64_t red_identity<uint64_t>(int op) { return op == DFDB_AGG_MIN ? ~0ull : 0ull; }
-template <> __device__ __forceinline__ double red_identity<double>(int op) { return op == DFDB_AGG_MIN ? __builtin_inf() : (op == DFDB_AGG_MAX ? -__builtin_inf() : 0.0); }
-
 template <typename A> __device__ __forceinline__ A red_combine(A a, A b, int op) {
   if (op == DFDB_AGG_SUM) return a + b;
   if (op == DFDB_AGG_MIN) return b < a ? b : a;
   return b > a ? b : a;
 }
-__device__ __forceinline__ double red_combine_f(double a, double b, int op) {   // Julia min/max propagate NaN, and -0.0 orders below 0.0 (Base.min / Base.max)
-  if (op == DFDB_AGG_SUM) return a + b;
-  if (a != a) return a;
-  if (b != b) return b;
-  // (a == b: equal values share their bits except the two zeros — OR keeps a sign bit either of them has, AND drops one either lacks.  `b < a ? b : a` kept
-  // whichever zero came first, so minimum() of a column holding 0.0 and -0.0 depended on the grid: found by the block-streamed aggregates, round 6)
-  if (a == b) { const unsigned long long x = __double_as_longlong(a), y = __double_as_longlong(b); return __longlong_as_double(op == DFDB_AGG_MIN ? (x | y) : (x & y)); }
-  if (op == DFDB_AGG_MIN) return b < a ? b : a;
-  return b > a ? b : a;
-}
 template <typename A> __device__ __forceinline__ A comb(A a, A b, int op) { return red_combine<A>(a, b, op); }
-template <> __device__ __forceinline__ double comb<double>(double a, double b, int op) { return red_combine_f(a, b, op); }
+template <> __device__ __forceinline__ double comb<double>(double a, double b, int op) { return op == DFDB_AGG_SUM ? a + b : minmax_f64(a, b, op == DFDB_AGG_MIN); }      // (value_rules.hpp: Julia's NaN and signed-zero rules)
 
 template <typename A> __device__ __forceinline__ A wave_reduce(A v, int op) {
 #pragma unroll
@@ -433,7 +419,7 @@ __global__ __launch_bounds__(kBlock) void k_reduce_partial(const uint64_t* __res
   const int wib = threadIdx.x >> 6;
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + wib;
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  A acc = red_identity<A>(op);
+  A acc = reduce_identity<A>(op == DFDB_AGG_MIN, op == DFDB_AGG_MAX);
   uint64_t cnt = 0;
   const int64_t ntiles = (nwords + 15) / 16;
   for (int64_t tile = wave; tile < ntiles; tile += nwaves) {   // 1024 rows per wave step, 16 column loads in flight
@@ -468,7 +454,7 @@ __global__ __launch_bounds__(kBlock) void k_reduce_final(const A* __restrict__ p
                                                          A* __restrict__ result, uint64_t* __restrict__ rcount) {
   __shared__ A sh[kWavesPerBlock];
   __shared__ uint64_t shc[kWavesPerBlock];
-  A acc = red_identity<A>(op); uint64_t cnt = 0;
+  A acc = reduce_identity<A>(op == DFDB_AGG_MIN, op == DFDB_AGG_MAX); uint64_t cnt = 0;
   // fixed association: thread t folds partials t, t+256, ... then a fixed tree
   for (int i = threadIdx.x; i < n; i += kBlock) { acc = comb<A>(acc, partials[i], op); cnt += pcounts[i]; }
   acc = wave_reduce<A>(acc, op); cnt = wave_sum64(cnt);

@@ -18,6 +18,7 @@
 // (Round-1 history: the first interpreter dispatched per 64 rows with an LDS register file: 193 SALU + 77
 // VALU instructions per word, 0.73 TB/s.  profiles/r1_README.md has the counters.)
 #include "device_utils.hpp"
+#include "value_rules.hpp"
 #include "engine.hpp"
 
 namespace dfdb {
@@ -86,16 +87,11 @@ struct Compiler {
     if (b == DFDB_F32) { float f; memcpy(&f, &n.cbits, 4); double d = f; uint64_t u; memcpy(&u, &d, 8); return u; }
     if (b == DFDB_F64 || b == DFDB_I64 || b == DFDB_U64) return n.cbits;
     if (b == DFDB_BOOL) return n.cbits != 0;
-    int64_t v = (int64_t)n.cbits;
-    switch (b) { case DFDB_I8: v = (int8_t)v; break; case DFDB_I16: v = (int16_t)v; break; case DFDB_I32: v = (int32_t)v; break;
-                 case DFDB_U8: v = (uint8_t)v; break; case DFDB_U16: v = (uint16_t)v; break; case DFDB_U32: v = (uint32_t)v; break; }
-    return (uint64_t)v;
+    return (uint64_t)wrap_int((int64_t)n.cbits, b);
   }
-  static bool hisf(int t) { return t == DFDB_F32 || t == DFDB_F64; }
-  static bool hsigned(int t) { return t >= DFDB_I8 && t <= DFDB_I64; }
   // conversion of an operand image of type t to the float compute type ct (as_float on the device)
   static int cv_for(int t, int ct) {
-    if (hisf(t)) return (ct == DFDB_F32 && t == DFDB_F64) ? CV_D2F : CV_NONE;
+    if (is_float(t)) return (ct == DFDB_F32 && t == DFDB_F64) ? CV_D2F : CV_NONE;
     if (ct == DFDB_F32) return t == DFDB_U64 ? CV_U2F : CV_S2F;
     return t == DFDB_U64 ? CV_U2D : CV_S2D;
   }
@@ -112,14 +108,10 @@ struct Compiler {
     uint64_t u; memcpy(&u, &d, 8); return u;
   }
   static void wrap_of(IInstr& in, int t) {   // result wrap of the integer type t
-    int bits = 64; bool sg = hsigned(t);
+    int bits = 64; bool sg = is_signed(t);
     switch (t) { case DFDB_I8: case DFDB_U8: bits = 8; break; case DFDB_I16: case DFDB_U16: bits = 16; break;
                  case DFDB_I32: case DFDB_U32: bits = 32; break; case DFDB_BOOL: bits = 1; sg = false; break; }
     in.wsh = (uint8_t)(64 - bits); in.wsg = sg ? 1 : 0;
-  }
-  static int64_t type_min_of(int t) {
-    switch (t) { case DFDB_I8: return -128; case DFDB_I16: return -32768; case DFDB_I32: return -2147483648LL; case DFDB_I64: return INT64_MIN; }
-    return 0;
   }
   static int mirror(int op) {
     switch (op) { case DFIR_LT: return DFIR_GT; case DFIR_LE: return DFIR_GE; case DFIR_GT: return DFIR_LT; case DFIR_GE: return DFIR_LE; }
@@ -243,9 +235,9 @@ struct Compiler {
       if (n.op == DFIR_NOT) { op_on(*n.a, H_NOT); return; }
       if (n.op == DFIR_CAST) { IInstr& in = op_on(*n.a, H_CAST); in.ta = (uint8_t)ta; in.rt = (uint8_t)dt_base(n.cast_to); return; }
       if (n.op == DFIR_NEG || n.op == DFIR_ABS) {
-        if (hisf(rt)) { IInstr& in = op_on(*n.a, n.op == DFIR_NEG ? H_FNEG : H_FABS); in.cva = (uint8_t)cv_for(ta, rt); return; }
+        if (is_float(rt)) { IInstr& in = op_on(*n.a, n.op == DFIR_NEG ? H_FNEG : H_FABS); in.cva = (uint8_t)cv_for(ta, rt); return; }
         if (rt == DFDB_BOOL) { eval(*n.a); return; }
-        IInstr& in = op_on(*n.a, n.op == DFIR_NEG ? H_INEG : (hsigned(rt) ? H_IABS : H_WRAP)); wrap_of(in, rt);
+        IInstr& in = op_on(*n.a, n.op == DFIR_NEG ? H_INEG : (is_signed(rt) ? H_IABS : H_WRAP)); wrap_of(in, rt);
         return;
       }
       fail(DFDB_ERR_UNSUPPORTED, "unary operation 0x%x is not supported by the device interpreter", n.op);
@@ -256,7 +248,7 @@ struct Compiler {
       int ct = rt;   // compute type: the promoted type; Float for `/`; Int for Bool ± Bool
       if (n.op == DFIR_DIV) { const int p = promote_num(n.a->dtype, n.b->dtype); ct = dt_isfloat(p) ? dt_base(p) : DFDB_F64; }
       else if ((n.op == DFIR_ADD || n.op == DFIR_SUB) && ta == DFDB_BOOL && tb == DFDB_BOOL) ct = DFDB_I64;
-      if (hisf(ct)) {
+      if (is_float(ct)) {
         int h = H_FADD;
         switch (n.op) { case DFIR_ADD: h = H_FADD; break; case DFIR_SUB: h = H_FSUB; break; case DFIR_MUL: h = H_FMUL; break; case DFIR_DIV: h = H_FDIV; break;
                         case DFIR_REM: h = H_FREM; break; case DFIR_MOD: h = H_FMOD; break; case DFIR_IDIV: h = H_FIDIV; break; case DFIR_MIN: h = H_FMIN; break;
@@ -273,12 +265,12 @@ struct Compiler {
                         default: h = H_IDIVOP; break; }
         fetch_operands(n, pin, h);
         wrap_of(*pin, ct);
-        if (h == H_IDIVOP) { pin->cmp = (uint8_t)n.op; if (!hsigned(ct)) pin->flags |= F_UNS; pin->imm2 = (uint64_t)type_min_of(ct); }
+        if (h == H_IDIVOP) { pin->cmp = (uint8_t)n.op; if (!is_signed(ct)) pin->flags |= F_UNS; pin->imm2 = (uint64_t)int_lo(ct); }
       }
       return;
     }
     if (n.op >= DFIR_EQ && n.op <= DFIR_GE) {
-      const bool fa = hisf(ta), fb = hisf(tb);
+      const bool fa = is_float(ta), fb = is_float(tb);
       int h, op = n.op; bool exchange = false, uns = false;
       if (fa && fb) h = H_CMP_FF;
       else if (fa) { h = H_CMP_IF; exchange = true; uns = tb == DFDB_U64; }        // float OP int  ==  int mirror(OP) float

@@ -54,7 +54,7 @@ struct IInstr {                // host-side form (the Compiler fills these field
   uint64_t imm;                // immediate bits / pool offset
   uint8_t ta, tb, rt, so;      // generic handlers (H_CAST, H_INSET): operand/result dtypes; so: offset-array index of the string column (H_STRCMP2: ta / tb = the second column's slot / offset-array index)
   int32_t aslot;               // 1 + column slot loaded into A before the operation (fused leaf load), 0 = A is the running value
-  uint64_t imm2;               // type_min of the compute type (typemin ÷ -1 check)
+  uint64_t imm2;               // int_lo of the compute type (typemin ÷ -1 check)
 };
 // device form: the same fields packed into dwords so that the whole instruction arrives with ONE scalar load
 // (sub-dword fields would be fetched with vector loads + s_waitcnt vmcnt(0): three exposed round trips per dispatch)
@@ -81,25 +81,9 @@ struct IProgram {
 };
 
 // ---------------------------------------------------------------- scalar helpers
-__device__ __forceinline__ double bits_d(uint64_t x) { return __longlong_as_double((long long)x); }
-__device__ __forceinline__ uint64_t d_bits(double d) { return (uint64_t)__double_as_longlong(d); }
-__device__ __forceinline__ bool isf(int t) { return t == DFDB_F32 || t == DFDB_F64; }
-__device__ __forceinline__ bool issigned(int t) { return t >= DFDB_I8 && t <= DFDB_I64; }
-
-__device__ __forceinline__ int64_t wrap_to(int64_t x, int t) {
-  switch (t) {
-    case DFDB_I8: return (int8_t)x; case DFDB_I16: return (int16_t)x; case DFDB_I32: return (int32_t)x;
-    case DFDB_U8: return (uint8_t)x; case DFDB_U16: return (uint16_t)x; case DFDB_U32: return (uint32_t)x;
-    default: return x;
-  }
-}
-__device__ __forceinline__ int64_t type_min(int t) {
-  switch (t) { case DFDB_I8: return -128; case DFDB_I16: return -32768; case DFDB_I32: return -2147483648LL; case DFDB_I64: return INT64_MIN; }
-  return 0;
-}
 // operand (64-bit register image of type t) as a float of compute type ct, one rounding from the source
 __device__ __forceinline__ double as_float(uint64_t x, int t, int ct) {
-  if (isf(t)) { const double d = bits_d(x); return ct == DFDB_F32 ? (double)(float)d : d; }
+  if (is_float(t)) { const double d = bits_f64(x); return ct == DFDB_F32 ? (double)(float)d : d; }
   if (ct == DFDB_F32) return t == DFDB_U64 ? (double)(float)x : (double)(float)(int64_t)x;
   return t == DFDB_U64 ? (double)x : (double)(int64_t)x;
 }
@@ -123,10 +107,10 @@ __device__ __forceinline__ int cmp_int_float(int64_t x, bool xu, double y) {
   return fr > 0.0 ? -1 : (fr < 0.0 ? 1 : 0);
 }
 __device__ __forceinline__ int cmp3(uint64_t xa, int ta, uint64_t xb, int tb) {
-  const bool fa = isf(ta), fb = isf(tb);
-  if (fa && fb) { const double a = bits_d(xa), b = bits_d(xb); if (a != a || b != b) return 2; return a < b ? -1 : (a > b ? 1 : 0); }
-  if (fa) { const int r = cmp_int_float((int64_t)xb, tb == DFDB_U64, bits_d(xa)); return r == 2 ? 2 : -r; }
-  if (fb) return cmp_int_float((int64_t)xa, ta == DFDB_U64, bits_d(xb));
+  const bool fa = is_float(ta), fb = is_float(tb);
+  if (fa && fb) { const double a = bits_f64(xa), b = bits_f64(xb); if (a != a || b != b) return 2; return a < b ? -1 : (a > b ? 1 : 0); }
+  if (fa) { const int r = cmp_int_float((int64_t)xb, tb == DFDB_U64, bits_f64(xa)); return r == 2 ? 2 : -r; }
+  if (fb) return cmp_int_float((int64_t)xa, ta == DFDB_U64, bits_f64(xb));
   const bool ua = ta == DFDB_U64, ub = tb == DFDB_U64;
   if (ua == ub) { if (ua) return xa < xb ? -1 : (xa > xb ? 1 : 0); const int64_t a = (int64_t)xa, b = (int64_t)xb; return a < b ? -1 : (a > b ? 1 : 0); }
   if (ua) { if ((int64_t)xb < 0) return 1; return xa < xb ? -1 : (xa > xb ? 1 : 0); }
@@ -205,7 +189,7 @@ __device__ __forceinline__ uint64_t parse_bytes(const uint8_t* p, int len, int r
   while (b < e && parse_ws(p[b])) b++;
   while (e > b && parse_ws(p[e - 1])) e--;
   if (b == e) { reason = PR_ARGUMENT; return 0; }                                                // empty or all whitespace
-  const bool flt = rt == DFDB_F64, sgn = flt || issigned(rt);
+  const bool flt = rt == DFDB_F64, sgn = flt || is_signed(rt);
   bool neg = false;
   if (p[b] == '+' || (sgn && p[b] == '-')) {
     neg = p[b] == '-'; b++;
@@ -214,11 +198,7 @@ __device__ __forceinline__ uint64_t parse_bytes(const uint8_t* p, int len, int r
   }
   if (!flt) {
     if (p[b] == '0' && b + 1 < e && (p[b + 1] == 'x' || p[b + 1] == 'o' || p[b + 1] == 'b')) { reason = PR_UNSUPPORTED; return 0; }
-    uint64_t lim;                                                                                // the largest magnitude of this sign
-    switch (rt) {
-      case DFDB_I8: lim = 127; break; case DFDB_I16: lim = 32767; break; case DFDB_I32: lim = 2147483647ull; break; case DFDB_I64: lim = 9223372036854775807ull; break;
-      case DFDB_U8: lim = 255; break; case DFDB_U16: lim = 65535; break; case DFDB_U32: lim = 4294967295ull; break; default: lim = ~0ull; break;
-    }
+    uint64_t lim = int_hi(rt);                                                                   // the largest magnitude of this sign
     if (neg) lim += 1;
     uint64_t v = 0;
     for (; b < e; b++) {
@@ -252,7 +232,7 @@ __device__ __forceinline__ uint64_t parse_bytes(const uint8_t* p, int len, int r
   double p10 = 1.0;                                                                              // 10^|e10|: exact up to 10^22 (every partial product is)
   for (int i = e10 < 0 ? -e10 : e10; i > 0; i--) p10 *= 10.0;
   const double d = e10 < 0 ? (double)m / p10 : (double)m * p10;
-  return d_bits(neg ? -d : d);
+  return f64_bits(neg ? -d : d);
 }
 // alive: the row is inside the table and selected; only such a row is parsed, and only it can raise
 DFDB_SLOW uint64_t slow_parse(const uint8_t* p, int len, bool missing, int rt, bool alive, int* err, uint64_t row) {
@@ -306,23 +286,16 @@ DFDB_SLOW uint64_t slow_datetime(const uint8_t* p, int len, bool missing, bool a
 // DFIR_CAST = Julia's T(x) / convert(T, x): exact or InexactError (Int8(300), Int8(300.0), UInt64(-1), UInt64(-1.0), Int64(typemax(UInt64)),
 // Bool(2) all throw; Float32(x) rounds).  The implicit promotions of arithmetic wrap instead (`a % T`, Base int.jl) and do not come here.
 __device__ __forceinline__ bool int_fits(uint64_t x, bool src_unsigned, int rt) {
-  int64_t lo, hi;                                   // [typemin, typemax] of the targets below 64 bits
-  switch (rt) {
-    case DFDB_I8: lo = -128; hi = 127; break;        case DFDB_I16: lo = -32768; hi = 32767; break;
-    case DFDB_I32: lo = -2147483648LL; hi = 2147483647LL; break;
-    case DFDB_U8: lo = 0; hi = 255; break;           case DFDB_U16: lo = 0; hi = 65535; break;
-    case DFDB_U32: lo = 0; hi = 4294967295LL; break;
-    case DFDB_I64: return !src_unsigned || (int64_t)x >= 0;      // a UInt64 above typemax(Int64)
-    case DFDB_U64: return src_unsigned || (int64_t)x >= 0;       // a negative signed value
-    default: return true;
-  }
-  if (src_unsigned) return x <= (uint64_t)hi;
-  return (int64_t)x >= lo && (int64_t)x <= hi;
+  if (rt == DFDB_I64) return !src_unsigned || (int64_t)x >= 0;      // a UInt64 above typemax(Int64)
+  if (rt == DFDB_U64) return src_unsigned || (int64_t)x >= 0;       // a negative signed value
+  if (rt < DFDB_I8 || rt > DFDB_U32) return true;
+  if (src_unsigned) return x <= int_hi(rt);
+  return (int64_t)x >= int_lo(rt) && (int64_t)x <= (int64_t)int_hi(rt);
 }
 DFDB_SLOW uint64_t slow_cast(uint64_t xa, int ta, int rt, bool alive, int* err, uint64_t row) {
-  if (isf(rt)) return d_bits(as_float(xa, ta, rt));
-  if (isf(ta)) {   // Float -> Int / Bool: InexactError unless integral and inside the TARGET's range
-    const double d = bits_d(xa);
+  if (is_float(rt)) return f64_bits(as_float(xa, ta, rt));
+  if (is_float(ta)) {   // Float -> Int / Bool: InexactError unless integral and inside the TARGET's range
+    const double d = bits_f64(xa);
     bool okr = d == __builtin_trunc(d);
     uint64_t v = 0;
     if (rt == DFDB_U64) { okr = okr && d >= 0.0 && d < 18446744073709551616.0; if (okr) v = (uint64_t)d; }
@@ -330,11 +303,11 @@ DFDB_SLOW uint64_t slow_cast(uint64_t xa, int ta, int rt, bool alive, int* err, 
     if (!okr && alive) flag_error(err, 2, row);
     if (!okr) v = 0;
     if (rt == DFDB_BOOL) { if (v > 1 && alive) flag_error(err, 2, row); return v != 0; }
-    return (uint64_t)wrap_to((int64_t)v, rt);
+    return (uint64_t)wrap_int((int64_t)v, rt);
   }
   if (rt == DFDB_BOOL) { if (xa > 1 && alive) flag_error(err, 2, row); return xa != 0; }
   if (ta != DFDB_BOOL && !int_fits(xa, ta >= DFDB_U8 && ta <= DFDB_U64, rt) && alive) flag_error(err, 2, row);
-  return (uint64_t)wrap_to((int64_t)xa, rt);
+  return (uint64_t)wrap_int((int64_t)xa, rt);
 }
 
 // ---------------------------------------------------------------- the interpreter
@@ -356,7 +329,7 @@ __device__ __forceinline__ void load_words(const void* data, int64_t base, const
     uint32_t o = idx[k];
     asm volatile("" : "+v"(o));
     const T v = __builtin_nontemporal_load((gT_p)(p + (uint32_t)(o * (uint32_t)sizeof(T))));
-    if (FLT) B[k] = d_bits((double)v); else B[k] = (uint64_t)(int64_t)v;
+    if (FLT) B[k] = f64_bits((double)v); else B[k] = (uint64_t)(int64_t)v;
   }
 }
 // cdt: the column's dtype — the descriptor's own at run time (ahead-of-time interpreter), a literal in the run-time compiled build
@@ -397,23 +370,23 @@ __device__ __forceinline__ void convert(uint64_t (&X)[kW], int mode) {
   switch (mode) {
     case CV_S2D:
 #pragma unroll
-      EACH X[k] = d_bits((double)(int64_t)X[k]);
+      EACH X[k] = f64_bits((double)(int64_t)X[k]);
       break;
     case CV_U2D:
 #pragma unroll
-      EACH X[k] = d_bits((double)X[k]);
+      EACH X[k] = f64_bits((double)X[k]);
       break;
     case CV_S2F:
 #pragma unroll
-      EACH X[k] = d_bits((double)(float)(int64_t)X[k]);
+      EACH X[k] = f64_bits((double)(float)(int64_t)X[k]);
       break;
     case CV_U2F:
 #pragma unroll
-      EACH X[k] = d_bits((double)(float)X[k]);
+      EACH X[k] = f64_bits((double)(float)X[k]);
       break;
     case CV_D2F:
 #pragma unroll
-      EACH X[k] = d_bits((double)(float)bits_d(X[k]));
+      EACH X[k] = f64_bits((double)(float)bits_f64(X[k]));
       break;
   }
 }
@@ -431,9 +404,9 @@ __device__ __forceinline__ bool cmp_pick(int op, bool lt, bool eq, bool un) {   
 #define FLOAT_OP(EXPR)                                                        \
   {                                                                           \
     _Pragma("unroll") EACH {                                                  \
-      const double a = bits_d(A[k]), b = bits_d(B[k]); double v; (void)b;     \
+      const double a = bits_f64(A[k]), b = bits_f64(B[k]); double v; (void)b;     \
       EXPR;                                                                   \
-      A[k] = d_bits(v);                                                       \
+      A[k] = f64_bits(v);                                                       \
     }                                                                         \
   } break
 #define INT_OP(EXPR)                                                          \
@@ -551,7 +524,7 @@ __device__ __forceinline__ void interp_body(const IProgram* __restrict__ prog, u
               case DFDB_BOOL: ((uint8_t*)out)[o] = (uint8_t)(res & 1ull); break;
               case DFDB_I16: case DFDB_U16: ((uint16_t*)out)[o] = (uint16_t)res; break;
               case DFDB_I32: case DFDB_U32: ((uint32_t*)out)[o] = (uint32_t)res; break;
-              case DFDB_F32: ((float*)out)[o] = (float)bits_d(res); break;
+              case DFDB_F32: ((float*)out)[o] = (float)bits_f64(res); break;
               default: ((uint64_t*)out)[o] = res; break;
             }
             if (NUL && out_missing) out_missing[o] = (uint8_t)Am[k];

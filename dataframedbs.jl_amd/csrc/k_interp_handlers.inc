@@ -62,7 +62,7 @@
               default:      _Pragma("unroll") EACH { const TYPE a = LOADA, b = LOADB; A[k] = a >= b; } break;      \
             }                                                                                                      \
           } break
-          case H_CMP_FF: CMP_CASES(double, bits_d(A[k]), bits_d(B[k]));   // IEEE: every ordered comparison with NaN is false, != true
+          case H_CMP_FF: CMP_CASES(double, bits_f64(A[k]), bits_f64(B[k]));   // IEEE: every ordered comparison with NaN is false, != true
           case H_CMP_SS: CMP_CASES(int64_t, (int64_t)A[k], (int64_t)B[k]);
           case H_CMP_UU: CMP_CASES(uint64_t, A[k], B[k]);
           case H_CMP_US: {   // UInt64 vs a signed integer
@@ -73,7 +73,7 @@
           case H_CMP_IF: {   // integer vs float, exact (no rounding of the integer)
             const int op = in_cmp; const bool xu = (fl & F_UNS) != 0;
 #pragma unroll
-            EACH { const int c = slow_cmp_int_float((int64_t)A[k], xu, bits_d(B[k])); A[k] = cmp_pick(op, c == -1, c == 0, c == 2); }
+            EACH { const int c = slow_cmp_int_float((int64_t)A[k], xu, bits_f64(B[k])); A[k] = cmp_pick(op, c == -1, c == 0, c == 2); }
           } break;
           case H_STRCMP: case H_STRPRE: case H_STRSUF: {
             const IColDesc& c = prog->cols[in_slot];

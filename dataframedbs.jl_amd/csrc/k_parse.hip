@@ -23,6 +23,7 @@
 // is 24640 bytes per wave, 49280 per two-wave workgroup, and floor(163840 / 49280) = 3 workgroups = 6 waves per CU (one wave per workgroup would give the
 // same 6 waves).
 #include "device_utils.hpp"
+#include "value_rules.hpp"
 #include "engine.hpp"
 #include "str_tile.hpp"
 
@@ -50,7 +51,7 @@ __device__ __forceinline__ uint64_t swar_value8(uint64_t x) {    // eight ASCII 
 // [sign] + 1..19 digits that fit the target: true and the register image; anything else is the slow path's to decide
 __device__ __forceinline__ bool parse_fast(uint64_t x0, uint64_t x1, uint64_t x2, int len, int rt, uint64_t& out) {
   const uint32_t c0 = (uint32_t)x0 & 0xffu;
-  const uint32_t s = (c0 == '+' || (issigned(rt) && c0 == '-')) ? 1u : 0u;
+  const uint32_t s = (c0 == '+' || (is_signed(rt) && c0 == '-')) ? 1u : 0u;
   const bool neg = s && c0 == '-';
   const int nd = len - (int)s;
   if (nd < 1 || nd > 19) return false;
@@ -62,11 +63,7 @@ __device__ __forceinline__ bool parse_fast(uint64_t x0, uint64_t x1, uint64_t x2
   }
   if (full >= 1) { const uint64_t x = parse_get8(x0, x1, x2, o); ok = ok && swar_digits8(x); v = v * 100000000ull + swar_value8(x); o += 8; }
   if (full >= 2) { const uint64_t x = parse_get8(x0, x1, x2, o); ok = ok && swar_digits8(x); v = v * 100000000ull + swar_value8(x); }
-  uint64_t lim;                                                  // the largest magnitude of this sign (19 digits never overflow 64 bits)
-  switch (rt) {
-    case DFDB_I8: lim = 127; break; case DFDB_I16: lim = 32767; break; case DFDB_I32: lim = 2147483647ull; break; case DFDB_I64: lim = 9223372036854775807ull; break;
-    case DFDB_U8: lim = 255; break; case DFDB_U16: lim = 65535; break; case DFDB_U32: lim = 4294967295ull; break; default: lim = ~0ull; break;
-  }
+  uint64_t lim = int_hi(rt);                                     // the largest magnitude of this sign (19 digits never overflow 64 bits)
   if (neg) lim += 1;
   out = neg ? 0 - v : v;
   return ok && v <= lim;

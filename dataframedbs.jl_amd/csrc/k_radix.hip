@@ -19,6 +19,7 @@
 // are isequal images (one NaN, -0.0 apart from 0.0), a missing key and the one image that cannot be stored (all ones) are kept aside in aux[1] / aux[0]
 // exactly as k_unique_insert keeps them.  Measured history: profiles/r6_unique_radix.txt; what the instruction and store choices rest on: tools/ubench/.
 #include "device_utils.hpp"
+#include "value_rules.hpp"
 #include "kernels.hpp"
 #include "../../include/dfdb_ir.h"
 
@@ -39,22 +40,9 @@ __device__ __forceinline__ uint32_t rhash(uint64_t key) {
   return h;
 }
 
-__device__ __forceinline__ uint64_t rkey_fixed(const void* col, int dtype, int64_t row) {      // = k_unique.hip key_fixed: the isequal image
-  switch (dtype) {
-    case DFDB_I8:  return (uint64_t)(int64_t)((const int8_t*)col)[row];
-    case DFDB_I16: return (uint64_t)(int64_t)((const int16_t*)col)[row];
-    case DFDB_I32: return (uint64_t)(int64_t)((const int32_t*)col)[row];
-    case DFDB_U8: case DFDB_BOOL: return ((const uint8_t*)col)[row];
-    case DFDB_U16: return ((const uint16_t*)col)[row];
-    case DFDB_U32: return ((const uint32_t*)col)[row];
-    case DFDB_F32: { const float f = ((const float*)col)[row]; return f != f ? 0x7fc00000ull : (uint64_t)__float_as_uint(f); }
-    case DFDB_F64: { const double d = ((const double*)col)[row]; return d != d ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d); }
-    default: return ((const uint64_t*)col)[row];
-  }
-}
 struct __attribute__((packed, aligned(4))) Rec12 { uint32_t lo, hi, row; };
 struct __attribute__((packed, aligned(4))) Rec20 { uint32_t lo, hi, row, vlo, vhi; };
-enum { kKindRaw8 = 0, kKindF64 = 1, kKindAny = 2 };       // what a key load is: 8 raw bytes (Int64 / UInt64), 8 bytes + isequal's one NaN (Float64), anything narrower (rkey_fixed)
+enum { kKindRaw8 = 0, kKindF64 = 1, kKindAny = 2 };       // what a key load is: 8 raw bytes (Int64 / UInt64), 8 bytes + isequal's one NaN (Float64), anything narrower (key_image)
 __device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {     // a value every lane of the wave holds, into scalar registers
   return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32;
 }
@@ -121,7 +109,7 @@ __device__ __forceinline__ uint64_t tile_load(uint64_t (&key)[8], uint64_t (&in)
     for (int j = 0; j < 8; j++) {
       const uint32_t o = lo + (uint32_t)(j * 64);
       key[j] = 0;
-      if (__builtin_amdgcn_inverse_ballot_w64(in[j])) key[j] = rkey_fixed(col, dtype, base + (FULL || o < last ? o : last));
+      if (__builtin_amdgcn_inverse_ballot_w64(in[j])) key[j] = key_image(col, dtype, base + (FULL || o < last ? o : last));
     }
   }
   return selected_missing;                                      // (wave-uniform: nonzero = the partition pass looks for the tile's first missing row, tile_first_missing)
@@ -187,7 +175,7 @@ constexpr int part_lds_words(int block) { return 6 * 1024 + 32 + 8 * block; }   
 // the record is written (the tile's values are read in row order behind the sort and laid down in LDS where the sorted keys were), and the rows whose key cannot be
 // stored are counted and reduced
 // here, in a workgroup-wide accumulator that is flushed to gspec {count, value} once per workgroup (GOP: 0 count only, 1 wrapping integer sum, 2 double sum, 3 min, 4 max
-// of order images; vkind: how a value's image is made — k_unique.hip's order_image).
+// of order images; vkind: the value's accumulator kind — value_rules.hpp).
 struct RadixVals { const void* col; int vdt; uint64_t* gspec; int gop; int vkind; };
 // HOT KEYS.  A key that a large part of the rows hold would make one partition — one workgroup's work — of all those rows, every one an atomic on the same LDS
 // word (and through the form this replaces, 3e8 global atomics on ONE address: 3.6 s per 1e9 rows).  A workgroup of the partition pass keeps kHotSlots keys in LDS
@@ -199,27 +187,7 @@ __device__ __forceinline__ uint32_t hot_slot(uint64_t key) { return (((uint32_t)
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
   return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32;
 }
-// a value as the 64 bits the accumulators work on (= k_unique.hip's value_bits: integers widened, Float32 as the double it converts to)
-__device__ __forceinline__ uint64_t rvalue_bits(const void* col, int dtype, int64_t row) {
-  switch (dtype) {
-    case DFDB_I8:  return (uint64_t)(int64_t)((const int8_t*)col)[row];
-    case DFDB_I16: return (uint64_t)(int64_t)((const int16_t*)col)[row];
-    case DFDB_I32: return (uint64_t)(int64_t)((const int32_t*)col)[row];
-    case DFDB_U8: case DFDB_BOOL: return ((const uint8_t*)col)[row];
-    case DFDB_U16: return ((const uint16_t*)col)[row];
-    case DFDB_U32: return ((const uint32_t*)col)[row];
-    case DFDB_F32: return (uint64_t)__double_as_longlong((double)((const float*)col)[row]);
-    default: return ((const uint64_t*)col)[row];
-  }
-}
-template <bool V8> __device__ __forceinline__ uint64_t rvalue_of(const void* col, int dtype, int64_t row) { return V8 ? ((const uint64_t*)col)[row] : rvalue_bits(col, dtype, row); }
-__device__ __forceinline__ uint64_t order_image(uint64_t bits, int kind, bool is_min) {         // (= k_unique.hip's: unsigned compare; a NaN wins either reduction)
-  if (kind == 1) return bits;
-  if (kind == 0) return bits ^ (1ull << 63);
-  const double d = __longlong_as_double((long long)bits);
-  if (d != d) return is_min ? 0ull : ~0ull;
-  return (bits >> 63) ? ~bits : (bits | (1ull << 63));
-}
+template <bool V8> __device__ __forceinline__ uint64_t rvalue_of(const void* col, int dtype, int64_t row) { return V8 ? ((const uint64_t*)col)[row] : value_image(col, dtype, row); }
 __device__ __forceinline__ void acc_value(uint64_t* slot, uint64_t v, int gop, int vkind) {      // (LDS or global: one atomic)
   if (gop == 1) atomicAdd((unsigned long long*)slot, (unsigned long long)v);
   else if (gop == 2) atomicAdd((double*)slot, __longlong_as_double((long long)v));

@@ -9,6 +9,7 @@
 //   algorithmic bytes / row: sum of referenced column widths + 1/8 (bitmap) + 4/1024 (count)
 #include <type_traits>
 #include "device_utils.hpp"
+#include "value_rules.hpp"
 #include "kernels.hpp"
 #include "../../include/dfdb_ir.h"
 
@@ -483,21 +484,10 @@ __device__ __forceinline__ uint64_t term_word_affine(const ScanTerm& tm, uint32_
 }
 
 // EXTRA = 2 / 3 / 4: sum / min / max of the finally selected values (Julia: Int sums wrap, min / max of Float64 propagate NaN)
-template <typename T, int EXTRA> __device__ __forceinline__ T agg_identity() {
-  if (EXTRA == 3) return std::is_same<T, double>::value ? (T)__builtin_inf() : (std::is_same<T, int64_t>::value ? (T)INT64_MAX : (T)~0ull);
-  if (EXTRA == 4) return std::is_same<T, double>::value ? (T)-__builtin_inf() : (std::is_same<T, int64_t>::value ? (T)INT64_MIN : (T)0);
-  return (T)0;
-}
+template <typename T, int EXTRA> __device__ __forceinline__ T agg_identity() { return reduce_identity<T>(EXTRA == 3, EXTRA == 4); }
 template <typename T, int EXTRA> __device__ __forceinline__ T agg_combine(T a, T b) {
   if (EXTRA == 2) return a + b;
-  if (std::is_same<T, double>::value) {
-    if (a != a) return a;
-    if (b != b) return b;
-    if (a == b) {                       // the two zeros: -0.0 is the minimum, 0.0 the maximum, whichever came first (Base.min / Base.max; k_compact.hip red_combine_f)
-      const unsigned long long x = __double_as_longlong((double)a), y = __double_as_longlong((double)b);
-      return (T)__longlong_as_double(EXTRA == 3 ? (x | y) : (x & y));
-    }
-  }
+  if (std::is_same<T, double>::value) return (T)minmax_f64((double)a, (double)b, EXTRA == 3);      // (value_rules.hpp: NaN propagates, -0.0 < 0.0)
   if (EXTRA == 3) return b < a ? b : a;
   return b > a ? b : a;
 }
@@ -506,10 +496,8 @@ template <typename T, int EXTRA> __device__ __forceinline__ T wave_agg(T v) {
   for (int d = 32; d >= 1; d >>= 1) { const T t = __shfl_xor(v, d, 64); v = agg_combine<T, EXTRA>(v, t); }
   return v;
 }
-template <int EXTRA> __device__ __forceinline__ uint64_t agg_identity_bits(int dtype) {
-  if (dtype == DFDB_F64) { const double d = agg_identity<double, EXTRA>(); uint64_t b; __builtin_memcpy(&b, &d, 8); return b; }
-  if (dtype == DFDB_I64) return (uint64_t)agg_identity<int64_t, EXTRA>();
-  return agg_identity<uint64_t, EXTRA>();
+template <int EXTRA> __device__ __forceinline__ uint64_t agg_identity_bits(int dtype) {      // (dtype: the partials' — DFDB_F64 / DFDB_I64 / DFDB_U64)
+  return reduce_identity_bits(dtype == DFDB_F64 ? kAccFloat : (dtype == DFDB_I64 ? kAccSigned : kAccUnsigned), EXTRA == 3, EXTRA == 4);
 }
 // The LAST term of an AND of terms can do more than compare: when it is evaluated the mask of everything before it (the other
 // terms, the earlier stages) is known, so the tile's final mask falls out word by word while the term's values are still in

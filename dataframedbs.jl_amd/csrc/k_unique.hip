@@ -20,6 +20,7 @@
 // (two different strings, one key), in which case the host repeats with another salt: the result is exact, not probabilistic.
 // Integer keys of a small range take the dense form at the end of this file instead (no hashing: a presence bit per value in LDS).
 #include "device_utils.hpp"
+#include "value_rules.hpp"
 #include <algorithm>
 #include <type_traits>
 #include "kernels.hpp"
@@ -37,21 +38,6 @@ constexpr int kAuxClaims = 2, kAuxAbort = 3;
 constexpr uint64_t kNoSlot = 0xFFFFFFFFFFFFFFFFull;
 
 __device__ __forceinline__ uint64_t slot_of(uint64_t key, uint64_t mask) { return splitmix64(key) & mask; }
-
-// 64-bit image of row `row` of a fixed-width column under isequal: integers by value, floats by bits with one NaN
-__device__ __forceinline__ uint64_t key_fixed(const void* col, int dtype, int64_t row) {
-  switch (dtype) {
-    case DFDB_I8:  return (uint64_t)(int64_t)((const int8_t*)col)[row];
-    case DFDB_I16: return (uint64_t)(int64_t)((const int16_t*)col)[row];
-    case DFDB_I32: return (uint64_t)(int64_t)((const int32_t*)col)[row];
-    case DFDB_U8: case DFDB_BOOL: return ((const uint8_t*)col)[row];
-    case DFDB_U16: return ((const uint16_t*)col)[row];
-    case DFDB_U32: return ((const uint32_t*)col)[row];
-    case DFDB_F32: { const float f = ((const float*)col)[row]; return f != f ? 0x7fc00000ull : (uint64_t)__float_as_uint(f); }
-    case DFDB_F64: { const double d = ((const double*)col)[row]; return d != d ? 0x7ff8000000000000ull : (uint64_t)__double_as_longlong(d); }
-    default: return ((const uint64_t*)col)[row];
-  }
-}
 
 // -> the key's slot, bit 63 set when the key was already there (clear: this call claimed the slot), kNoSlot when the probe sequence got too long
 // (h: where the probe sequence starts — slot_of(key) for values that are their own keys, the low bits of a String's key, which is a hash already)
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_unique_insert(const uint64_t* __rest
   for (int64_t row = row0 + (int64_t)blockIdx.x * kBlock + threadIdx.x; row < row1; row += stride) {
     if (!((bitmap[row >> 6] >> (row & 63)) & 1ull)) continue;
     if (missing && ((missing[row >> 6] >> (row & 63)) & 1ull)) { if (__atomic_load_n(&aux[1], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux[1], (unsigned long long)row); continue; }
-    const uint64_t key = key_fixed(col, dtype, row);
+    const uint64_t key = key_image(col, dtype, row);
     if (key == kEmpty) { if (__atomic_load_n(&aux[0], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux[0], (unsigned long long)row); continue; }
     const uint64_t r = table_insert(ent, mask, key, (uint64_t)row, aux, slot_of(key, mask));
     if (r == kNoSlot) break;                          // the table is too full: the host grows it and repeats the chunk
@@ -163,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void k_unique_mark(uint64_t* __restrict__ b
         if (row < nrows && ((w >> lane) & 1ull)) {
           if (missing && ((missing[row >> 6] >> (row & 63)) & 1ull)) first = aux[1] == (uint64_t)row;
           else {
-            const uint64_t key = key_fixed(col, dtype, row);
+            const uint64_t key = key_image(col, dtype, row);
             first = key == kEmpty ? aux[0] == (uint64_t)row : ent[table_find(ent, mask, key, slot_of(key, mask))].row == (uint64_t)row;
           }
         }
@@ -277,6 +263,9 @@ __device__ __forceinline__ bool same_bytes(const uint8_t* a, int32_t la, const u
 
 // ---- groupreduce's accumulators (the comment at `groupreduce` below says what they are for)
 constexpr int kGroupLds = 1024;                      // groups that fit the per-workgroup accumulators
+// = value_image and value_kind of value_rules.hpp in one switch, kept HERE as a second statement, in the form the row loops below were compiled and measured with: through the header's
+// two functions the String pass and the accumulate kernels come out as other code — profiles/value_rules_refactor.txt — and NOTES/r6.md records what code that
+// is merely present in these tile loops costs.  tests/test_gpu_value_rules.py holds the two statements together on the device.
 // the value of row `row` as the accumulator sees it: 0 = int64 (wrapping sum / signed order), 1 = uint64, 2 = double
 __device__ __forceinline__ uint64_t value_bits(const void* col, int dtype, int64_t row, int& kind) {
   switch (dtype) {
@@ -292,20 +281,12 @@ __device__ __forceinline__ uint64_t value_bits(const void* col, int dtype, int64
     default:       { kind = 2; return ((const uint64_t*)col)[row]; }
   }
 }
-// order-preserving 64-bit image for min / max (unsigned compare); a NaN maps to the end that wins the reduction
-__device__ __forceinline__ uint64_t order_image(uint64_t bits, int kind, int op) {
-  if (kind == 1) return bits;
-  if (kind == 0) return bits ^ (1ull << 63);
-  const double d = __longlong_as_double((long long)bits);
-  if (d != d) return op == DFDB_AGG_MIN ? 0ull : ~0ull;
-  return (bits >> 63) ? ~bits : (bits | (1ull << 63));
-}
 __device__ __forceinline__ void group_add(uint64_t* cnt, uint64_t* val, uint64_t gid, uint64_t bits, int kind, int op, bool has_val) {
   atomicAdd((unsigned long long*)&cnt[gid], 1ull);
   if (!has_val) return;
   if (op == DFDB_AGG_SUM) { if (kind == 2) atomicAdd((double*)&val[gid], __longlong_as_double((long long)bits)); else atomicAdd((unsigned long long*)&val[gid], (unsigned long long)bits); }
-  else if (op == DFDB_AGG_MIN) atomicMin((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, op));
-  else if (op == DFDB_AGG_MAX) atomicMax((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, op));
+  else if (op == DFDB_AGG_MIN) atomicMin((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, true));
+  else if (op == DFDB_AGG_MAX) atomicMax((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, false));
 }
 // the same with the operator fixed at compile time (OPK: 0 count only, 1 wrapping integer sum, 2 double sum, 3 min, 4 max): inside the unrolled row loops of the
 // String pass the runtime form was a tree of scalar compares and branches per row (a 10 000-line kernel; SGPRs spilled to lanes)
@@ -314,8 +295,8 @@ __device__ __forceinline__ void group_add_t(uint64_t* cnt, uint64_t* val, uint64
   atomicAdd((unsigned long long*)&cnt[gid], 1ull);
   if (OPK == 1) atomicAdd((unsigned long long*)&val[gid], (unsigned long long)bits);
   if (OPK == 2) atomicAdd((double*)&val[gid], __longlong_as_double((long long)bits));
-  if (OPK == 3) atomicMin((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, DFDB_AGG_MIN));
-  if (OPK == 4) atomicMax((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, DFDB_AGG_MAX));
+  if (OPK == 3) atomicMin((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, true));
+  if (OPK == 4) atomicMax((unsigned long long*)&val[gid], (unsigned long long)order_image(bits, kind, false));
 }
 static int opk_of(int op, bool has_val, int kind) {
   if (!has_val || op == DFDB_AGG_COUNT) return 0;
@@ -383,7 +364,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
   int* collision = (int*)(A.aux + 4);
   const uint64_t gid_missing = KIND == 2 ? A.aux[1] : 0ull;
   // (properties of the value column, looked at ONCE: inside the unrolled row loops the dtype switch was a chain of scalar compares per row)
-  int vkind = 0; if (KIND == 2 && has_val) (void)value_bits(A.valcol, A.valdt, 0, vkind);
+  const int vkind = KIND == 2 && has_val ? value_kind(A.valdt) : 0;
   constexpr bool val8 = KIND == 2 && has_val && V8;
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
@@ -514,12 +495,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
   if (KIND == 0) add_claims(claimed, &claims_sh, A.aux);
   if (KIND == 2 && LDS) {
     __syncthreads();
-    int k2 = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, k2);
+    const int k2 = has_val ? value_kind(A.valdt) : 0;
     group_flush(lcnt, lval, A.cnt, A.val, A.ngroups, A.op, k2, has_val);
   }
   if (HOT) {                                                   // the hot groups' slots -> their groups
     __syncthreads();
-    int k2 = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, k2);
+    const int k2 = has_val ? value_kind(A.valdt) : 0;
     for (int sl = threadIdx.x; sl < kHotGroups; sl += kBlock) {
       const uint64_t c = lcnt[sl], g = hg_gid[sl];
       if (!c || g == kEmpty) continue;
@@ -653,7 +634,7 @@ struct AccArgs {
   uint64_t* unknown_flag;                                               // k_group_acc_dense_lds: raised by a selected row whose key has no group (an optimistic, head-only table)
 };
 // OPK: group_add_t's operator; W8: the value column AND (SRC 0 / 2) the key column are 8-byte integers or doubles, loaded as they are — the dtype switches of value_bits
-// and key_fixed, copied four times by the unrolled trip, stay in the !W8 kernels
+// and key_image, copied four times by the unrolled trip, stay in the !W8 kernels
 // NG = 0 (more groups than any LDS holds: every row's value through a global atomic) keeps kHotGroups slots in LDS for HOT groups (round 6): a group that a
 // large part of the rows belong to was 3e8 atomics on one address — 3.6 s per 1e9 rows.  A group that holds three of the 64 rows a wave looks at is given a slot
 // (if its slot is free); from the next trip on a row of a group with a slot is added THERE, and the slots are flushed with one global atomic each when the
@@ -672,7 +653,7 @@ __global__ __launch_bounds__(NG > kGroupLds ? 1024 : kBlock) void k_group_acc(co
   // one row at a time the pass ran at the latency of three dependent loads per trip (5e8 rows by dictionary codes: 5 ms)
   constexpr int U = 4;          // (eight: the same for integer keys, 1.6x slower on dictionary codes — measured)
   const int64_t stride = (int64_t)gridDim.x * nthreads;
-  int vkind = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, vkind);      // (the value kind is a property of the column)
+  const int vkind = has_val ? value_kind(A.valdt) : 0;      // (the value kind is a property of the column)
   bool unknown = false;
   for (int64_t row0 = (int64_t)blockIdx.x * nthreads + threadIdx.x; row0 < A.nrows; row0 += U * stride) {
     bool on[U], miss[U]; uint64_t key[U], gid[U], bits[U], w[U], mw[U];
@@ -687,7 +668,7 @@ __global__ __launch_bounds__(NG > kGroupLds ? 1024 : kBlock) void k_group_acc(co
       mw[k] = (SRC != 1 && inb && A.missing) ? A.missing[row >> 6] : 0ull;
       if (SRC == 1) key[k] = inb ? (uint64_t)A.codes[row] : 0ull;
       else if (W8 && A.keydt != DFDB_F64) key[k] = inb ? ((const uint64_t*)A.keycol)[row] : 0ull;
-      else key[k] = inb ? key_fixed(A.keycol, A.keydt, row) : 0ull;
+      else key[k] = inb ? key_image(A.keycol, A.keydt, row) : 0ull;
       if (W8) bits[k] = (inb && has_val) ? ((const uint64_t*)A.valcol)[row] : 0ull;
       else { int kind = 0; bits[k] = (inb && has_val) ? value_bits(A.valcol, A.valdt, row, kind) : 0ull; }
     }
@@ -736,11 +717,11 @@ __global__ __launch_bounds__(NG > kGroupLds ? 1024 : kBlock) void k_group_acc(co
   if (SRC == 0 && unknown && A.unknown_flag) __atomic_store_n(A.unknown_flag, 1ull, __ATOMIC_RELAXED);
   if (NG) {
     __syncthreads();
-    int k2 = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, k2);      // (the value kind is a property of the column)
+    const int k2 = has_val ? value_kind(A.valdt) : 0;      // (the value kind is a property of the column)
     group_flush(lcnt, lval, A.cnt, A.val, A.ngroups, A.op, k2, has_val, nthreads);
   } else {                                                     // the hot groups' slots -> their groups (group_flush, a slot's group from hg_gid)
     __syncthreads();
-    int k2 = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, k2);
+    const int k2 = has_val ? value_kind(A.valdt) : 0;
     for (int sl = threadIdx.x; sl < kHotGroups; sl += nthreads) {
       const uint64_t c = lcnt[sl], g = hg_gid[sl];
       if (!c || g == kEmpty) continue;
@@ -756,13 +737,7 @@ template <int SRC>
 static void launch_group_acc(hipStream_t s, const AccArgs& A) {
   if (A.nrows <= 0) return;
   const int64_t b256 = (A.nrows + kBlock - 1) / kBlock;
-  int vkind = 0;
-  switch (A.valdt) {                                           // (as value_bits sees the column)
-    case DFDB_I8: case DFDB_I16: case DFDB_I32: case DFDB_I64: vkind = 0; break;
-    case DFDB_U8: case DFDB_BOOL: case DFDB_U16: case DFDB_U32: case DFDB_U64: vkind = 1; break;
-    default: vkind = 2; break;
-  }
-  const int opk = opk_of(A.op, A.valcol != nullptr, vkind);
+  const int opk = opk_of(A.op, A.valcol != nullptr, value_kind(A.valdt));
   const bool v8 = opk == 0 || A.valdt == DFDB_I64 || A.valdt == DFDB_U64 || A.valdt == DFDB_F64;
   const bool k8 = SRC == 1 || A.keydt == DFDB_I64 || A.keydt == DFDB_U64 || A.keydt == DFDB_F64;
   auto go = [&](auto opk_c, auto w8_c) {
@@ -883,7 +858,7 @@ __global__ __launch_bounds__(1024) void k_group_acc_hash_lds(const AccArgs A, co
   const uint64_t g_unstorable = A.special[0], g_missing = A.special[1];       // the groups of the key that cannot be stored / of `missing` (kEmpty: there is none)
   for (int g = threadIdx.x; g < A.ngroups; g += 1024) {
     if ((uint64_t)g == g_unstorable || (uint64_t)g == g_missing) continue;     // (their first rows hold no key of the table)
-    const uint64_t key = key_fixed(gkeys, A.keydt, g);
+    const uint64_t key = key_image(gkeys, A.keydt, g);
     uint32_t h = lds_slot_of(key, slots);
     for (;;) {
       const uint64_t old = atomicCAS((unsigned long long*)&lkey[h], (unsigned long long)kEmpty, (unsigned long long)key);
@@ -894,7 +869,7 @@ __global__ __launch_bounds__(1024) void k_group_acc_hash_lds(const AccArgs A, co
   __syncthreads();
   constexpr int U = 8;
   const int64_t stride = (int64_t)gridDim.x * 1024;
-  int vkind = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, vkind);
+  const int vkind = has_val ? value_kind(A.valdt) : 0;
   const bool fkey = A.keydt == DFDB_F64;
   bool unknown = false;
   for (int64_t row0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; row0 < A.nrows; row0 += U * stride) {
@@ -913,7 +888,7 @@ __global__ __launch_bounds__(1024) void k_group_acc_hash_lds(const AccArgs A, co
       const int64_t row = row0 + k * stride;
       const bool on = (w[k] >> (row & 63)) & 1ull, miss = (mw[k] >> (row & 63)) & 1ull;
       uint64_t kk = key[k];
-      if (fkey) { const double d = __longlong_as_double((long long)kk); if (d != d) kk = 0x7ff8000000000000ull; }      // (one NaN: key_fixed)
+      if (fkey) { const double d = __longlong_as_double((long long)kk); if (d != d) kk = 0x7ff8000000000000ull; }      // (one NaN: key_image)
       uint64_t g = kEmpty;
       if (on) {
         if (miss) g = g_missing;
@@ -938,8 +913,8 @@ __global__ __launch_bounds__(1024) void k_group_acc_hash_lds(const AccArgs A, co
       atomicAdd(&lcnt[gid[k]], 1u);
       if (OPK == 1) atomicAdd((unsigned long long*)&lval[gid[k]], (unsigned long long)bits[k]);
       if (OPK == 2) atomicAdd((double*)&lval[gid[k]], __longlong_as_double((long long)bits[k]));
-      if (OPK == 3) atomicMin((unsigned long long*)&lval[gid[k]], (unsigned long long)order_image(bits[k], vkind, DFDB_AGG_MIN));
-      if (OPK == 4) atomicMax((unsigned long long*)&lval[gid[k]], (unsigned long long)order_image(bits[k], vkind, DFDB_AGG_MAX));
+      if (OPK == 3) atomicMin((unsigned long long*)&lval[gid[k]], (unsigned long long)order_image(bits[k], vkind, true));
+      if (OPK == 4) atomicMax((unsigned long long*)&lval[gid[k]], (unsigned long long)order_image(bits[k], vkind, false));
     }
   }
   if (unknown && A.unknown_flag) __atomic_store_n(A.unknown_flag, 1ull, __ATOMIC_RELAXED);
@@ -977,8 +952,7 @@ int launch_group_accumulate(hipStream_t s, const uint64_t* sel, const void* keyc
   A.sel = sel; A.keycol = keycol; A.keydt = keydt; A.missing = missing; A.valcol = valcol; A.valdt = valdt; A.op = op; A.nrows = nrows; A.ent = ent; A.mask = mask; A.special = special;
   A.cnt = cnt; A.val = val; A.ngroups = (int)ngroups; A.val_init = val_init;
   if (gkeys && nrows > 0 && ngroups > 0 && (keydt == DFDB_I64 || keydt == DFDB_U64 || keydt == DFDB_F64)) {      // (1: the form with the groups' keys in an LDS table)
-    const int vkind = valdt == DFDB_F64 ? 2 : (valdt == DFDB_U64 ? 1 : 0);
-    const int opk = opk_of(op, valcol != nullptr, vkind);
+    const int opk = opk_of(op, valcol != nullptr, value_kind(valdt));
     const bool v8 = opk == 0 || valdt == DFDB_I64 || valdt == DFDB_U64 || valdt == DFDB_F64;
     bool done = false;
     if (v8) switch (opk) {
@@ -1012,13 +986,7 @@ void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32
     int g = per_cu * cus;
     return (int)std::min<int64_t>(g, std::max<int64_t>(1, (ntiles + kWavesPerBlock - 1) / kWavesPerBlock));
   };
-  int vkind = 0;
-  switch (valdt) {                                             // (as value_bits sees the column)
-    case DFDB_I8: case DFDB_I16: case DFDB_I32: case DFDB_I64: vkind = 0; break;
-    case DFDB_U8: case DFDB_BOOL: case DFDB_U16: case DFDB_U32: case DFDB_U64: vkind = 1; break;
-    default: vkind = 2; break;
-  }
-  const int opk = opk_of(op, valcol != nullptr, vkind);
+  const int opk = opk_of(op, valcol != nullptr, value_kind(valdt));
   auto go = [&](auto ngl, auto opk_c) {
     constexpr int NGL = decltype(ngl)::value, OPK = decltype(opk_c)::value;
     if (OPK != 0 && (valdt == DFDB_I64 || valdt == DFDB_U64 || valdt == DFDB_F64)) {
@@ -1286,7 +1254,7 @@ __global__ __launch_bounds__(1024) void k_group_acc_dense_lds(const AccArgs A, u
   // where the selection bit is set costs a second dependent round trip per trip: the counters showed waves waiting 89 % of their cycles with ~37 lines in flight per CU)
   constexpr int U = 8;
   const int64_t stride = (int64_t)gridDim.x * 1024;
-  int vkind = 0; if (has_val) (void)value_bits(A.valcol, A.valdt, 0, vkind);
+  const int vkind = has_val ? value_kind(A.valdt) : 0;
   bool unknown = false;
   for (int64_t row0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; row0 < A.nrows; row0 += U * stride) {
     uint64_t w[U], mw[U], key[U], bits[U]; uint32_t gid[U];
@@ -1342,8 +1310,7 @@ int launch_group_accumulate_dense(hipStream_t s, const uint64_t* sel, const void
     AccArgs B = A;
     B.lo = lo + span_lo; B.gids = gids + span_lo;
     const uint32_t brange = (uint32_t)(span_hi - span_lo + 1);
-    int vkind = (valdt == DFDB_F64) ? 2 : (valdt == DFDB_U64 ? 1 : 0);
-    const int opk = opk_of(op, valcol != nullptr, vkind);
+    const int opk = opk_of(op, valcol != nullptr, value_kind(valdt));
     const bool v8 = opk == 0 || valdt == DFDB_I64 || valdt == DFDB_U64 || valdt == DFDB_F64;
     bool done = false;
     if (v8) switch (opk) {
@@ -1394,7 +1361,7 @@ __global__ __launch_bounds__(kBlock) void k_group_rank(const RankArgs A) {
       w[k] = inb ? A.sel[row >> 6] : 0ull;
       mw[k] = (SRC != 1 && inb && A.missing) ? A.missing[row >> 6] : 0ull;
       if (SRC == 1) key[k] = inb ? (uint64_t)A.codes[row] : 0ull;
-      else key[k] = inb ? key_fixed(A.keycol, A.keydt, row) : 0ull;
+      else key[k] = inb ? key_image(A.keycol, A.keydt, row) : 0ull;
       gp[k] = (inb && A.gprev) ? A.gprev[row] : 0u;
     }
 #pragma unroll
@@ -1474,8 +1441,8 @@ bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const int32_t* size
 // The reducers are a loop at run time (their columns, dtypes and operators are wave-uniform); the next reducer's values are loaded before the current one's are added.
 __device__ __forceinline__ void multi_add(uint64_t* v, uint64_t bits, int kind, int op) {      // one row's value into an accumulator (LDS or global)
   if (op == DFDB_AGG_SUM) { if (kind == 2) atomicAdd((double*)v, __longlong_as_double((long long)bits)); else atomicAdd((unsigned long long*)v, (unsigned long long)bits); }
-  else if (op == DFDB_AGG_MIN) atomicMin((unsigned long long*)v, (unsigned long long)order_image(bits, kind, op));
-  else if (op == DFDB_AGG_MAX) atomicMax((unsigned long long*)v, (unsigned long long)order_image(bits, kind, op));
+  else if (op == DFDB_AGG_MIN) atomicMin((unsigned long long*)v, (unsigned long long)order_image(bits, kind, true));
+  else if (op == DFDB_AGG_MAX) atomicMax((unsigned long long*)v, (unsigned long long)order_image(bits, kind, false));
 }
 __device__ __forceinline__ void multi_merge(uint64_t* v, uint64_t acc, int kind, int op) {      // an accumulator (an order image for min / max) into the global one
   if (op == DFDB_AGG_SUM) { if (kind == 2) atomicAdd((double*)v, __longlong_as_double((long long)acc)); else atomicAdd((unsigned long long*)v, (unsigned long long)acc); }

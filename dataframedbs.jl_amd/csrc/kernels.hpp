@@ -250,7 +250,7 @@ struct RankArgs {
 bool launch_group_rank(hipStream_t s, int src, const RankArgs& A);
 bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, uint64_t salt);
 // one accumulate pass for up to kMaxReducers reducers over the rows' group numbers: cnt [ngroups], val [nvals][ngroups] (min / max as order images until
-// launch_group_finish); kind: value_bits' kind of each value column; a group number >= ngroups raises *flag.  1: LDS form, 0: global form, -1: not launched
+// launch_group_finish); kind: value_kind (value_rules.hpp) of each value column; a group number >= ngroups raises *flag.  1: LDS form, 0: global form, -1: not launched
 constexpr int kMaxReducers = 16;
 struct MultiAccArgs {
   const uint64_t* sel; const uint32_t* gid; int64_t nrows; int nvals;

@@ -15,20 +15,15 @@ namespace dfdb {
 
 // ------------------------------------------------------------------ folding and the by-key merge (shared with group.cpp)
 template <class T> static T fold_t(T a, T b, int op) { return op == DFDB_AGG_MIN ? std::min(a, b) : (op == DFDB_AGG_MAX ? std::max(a, b) : (T)(a + b)); }
-double fold_f64(double x, double y, int op) {
-  if (op == DFDB_AGG_SUM) return x + y;
-  if (std::isnan(x) || std::isnan(y)) return NAN;
-  if (x == y) return op == DFDB_AGG_MIN ? (std::signbit(x) ? x : y) : (std::signbit(x) ? y : x);
-  return op == DFDB_AGG_MIN ? std::min(x, y) : std::max(x, y);
-}
 uint64_t fold_bits(uint64_t a, uint64_t b, int dt, int op) {
+  if (op == DFDB_AGG_SUM && dt != DFDB_F64) return a + b;
   if (dt == DFDB_F64) {
     double x, y; memcpy(&x, &a, 8); memcpy(&y, &b, 8);
-    const double r = fold_f64(x, y, op);
+    const double r = op == DFDB_AGG_SUM ? x + y : minmax_f64(x, y, op == DFDB_AGG_MIN);
     uint64_t o; memcpy(&o, &r, 8); return o;
   }
-  if (dt == DFDB_U64) return op == DFDB_AGG_SUM ? a + b : fold_t<uint64_t>(a, b, op);
-  return op == DFDB_AGG_SUM ? a + b : (uint64_t)fold_t<int64_t>((int64_t)a, (int64_t)b, op);
+  if (dt == DFDB_U64) return fold_t<uint64_t>(a, b, op);
+  return (uint64_t)fold_t<int64_t>((int64_t)a, (int64_t)b, op);
 }
 
 // isequal as a byte string, appended to k: the missing flag, then the value's bytes with every NaN folded onto one (isequal(NaN, -NaN); -0.0 and 0.0 stay apart)
@@ -87,7 +82,7 @@ void GroupMerger::add(GroupMerged& m, const GroupPart& p) {
     for (size_t r = 0; r < nv; r++) {
       const uint64_t a = m.vals[r][s], b = p.vals[r][(size_t)j];
       if (m.ops[r] == DFDB_AGG_COUNT) m.vals[r][s] = a + b;
-      else m.vals[r][s] = fold_bits(a, b, m.kinds[r] == 2 ? DFDB_F64 : (m.kinds[r] == 1 ? DFDB_U64 : DFDB_I64), m.ops[r]);   // wrapping Int sums, Float64 sums of the parts' sums, NaN-propagating min / max
+      else m.vals[r][s] = fold_bits(a, b, kind_dtype(m.kinds[r]), m.ops[r]);   // wrapping Int sums, Float64 sums of the parts' sums, NaN-propagating min / max
     }
   }
 }
@@ -405,8 +400,7 @@ void ooc_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double*
   TempQuery tq(q, !o.narrowed);
   if (o.narrowed) narrowed_view(q, tq);
   tq.project(q->proj[(size_t)i]);
-  const int b = dt_base(e.dtype);
-  const int adt = dt_isfloat(b) ? DFDB_F64 : (b == DFDB_U64 ? DFDB_U64 : DFDB_I64);    // the accumulator query_aggregate_device reduces in
+  const int adt = agg_dtype(e.dtype);                     // the accumulator query_aggregate_device reduces in
   uint64_t acc = 0; bool have = false; int64_t rows = 0;
   {
     StreamPass pass(q, &tq.q);
@@ -426,7 +420,7 @@ void ooc_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double*
     if (op != DFDB_AGG_SUM) fail(DFDB_ERR_ARGUMENT, "ArgumentError: reducing over an empty collection is not allowed");
     acc = 0;                                             // (0 and 0.0 share a bit pattern)
   }
-  group_values_out(&acc, 1, adt == DFDB_F64 ? 2 : (adt == DFDB_U64 ? 1 : 0), out_i, out_f);
+  group_values_out(&acc, 1, value_kind(adt), out_i, out_f);
 }
 
 // ------------------------------------------------------------------ unique / groupreduce
@@ -517,14 +511,10 @@ int ooc_aggregate_bits(dfdb_query* q, int32_t op, int32_t i, uint64_t out[2]) {
   if (i < 0 || (size_t)i >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", i);
   const Node& e = *q->proj[(size_t)i].expr;
   if (!dt_isnum(e.dtype) || dt_nullable(e.dtype)) fail(DFDB_ERR_UNSUPPORTED, "aggregate over %s is not supported", dt_name(e.dtype).c_str());
-  const int b = dt_base(e.dtype);
-  const int adt = dt_isfloat(b) ? DFDB_F64 : (b == DFDB_U64 ? DFDB_U64 : DFDB_I64);
+  const int adt = agg_dtype(e.dtype);
   const int64_t n = ooc_count(q);
   if (n == 0) {
-    uint64_t id = 0;
-    if (op == DFDB_AGG_MIN) { if (adt == DFDB_F64) { const double d = INFINITY; memcpy(&id, &d, 8); } else id = adt == DFDB_U64 ? ~0ull : (uint64_t)INT64_MAX; }
-    if (op == DFDB_AGG_MAX) { if (adt == DFDB_F64) { const double d = -INFINITY; memcpy(&id, &d, 8); } else id = adt == DFDB_U64 ? 0ull : (uint64_t)INT64_MIN; }
-    out[0] = id; out[1] = 0;
+    out[0] = reduce_identity_bits(value_kind(adt), op == DFDB_AGG_MIN, op == DFDB_AGG_MAX); out[1] = 0;
     return adt;
   }
   int64_t vi = 0; double vf = 0;

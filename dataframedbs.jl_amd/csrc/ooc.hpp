@@ -12,7 +12,6 @@
 namespace dfdb {
 
 // Julia's min / max over Float64: NaN propagates, and -0.0 orders below 0.0 (Base.min / Base.max); integer sums wrap like Julia's
-double fold_f64(double x, double y, int op);
 uint64_t fold_bits(uint64_t a, uint64_t b, int dt /* DFDB_I64 / DFDB_U64 / DFDB_F64 */, int op);
 
 // the groups of ONE part of a table (a shard of a multi-GPU group, a chunk of a block stream), in order of first appearance inside the part: one key block per

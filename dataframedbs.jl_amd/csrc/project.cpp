@@ -374,7 +374,7 @@ int query_aggregate_device(dfdb_query* q, int32_t op, int32_t i) {
       stream_wait(ctx);
       q->agg_ones_tiles = nt;
     }
-    dt = q->left.agg_dtype == DFDB_F64 ? DFDB_F64 : (q->left.agg_dtype == DFDB_U64 ? DFDB_U64 : DFDB_I64);
+    dt = agg_dtype(q->left.agg_dtype);
     { LaunchTimer lt(ctx, "reduce_partials"); launch_reduce(s, q->agg_ones.as<uint64_t>(), q->agg_partials.p, dt, op, nt, q->red_scratch.p, q->red_result.p); }
     // the count slot of the partial reduce counts TILES: the selected rows are the scan total
     HIP_CHECK(hipMemcpyAsync((uint64_t*)q->red_result.p + 1, q->prefix.as<uint64_t>() + nt, 8, hipMemcpyDeviceToDevice, s));
@@ -393,7 +393,7 @@ int query_aggregate_device(dfdb_query* q, int32_t op, int32_t i) {
     stream_wait(q->t->ctx);
     { LaunchTimer lt(ctx, "reduce"); launch_reduce(s, ones.as<uint64_t>(), full.p, dt, op, cnt, q->red_scratch.p, q->red_result.p); }
   }
-  return dt_isfloat(dt) ? DFDB_F64 : (dt == DFDB_U64 ? DFDB_U64 : DFDB_I64);
+  return agg_dtype(dt);
 }
 
 void query_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double* out_f) {

@@ -655,8 +655,7 @@ std::vector<int> groupreduce_check(const dfdb_query* q, const int32_t* key_cols,
     if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
     const Node& ve = *q->proj[(size_t)p].expr;
     if (ve.op != DFIR_COL || !dt_isnum(ve.dtype) || dt_nullable(ve.dtype)) fail(DFDB_ERR_UNSUPPORTED, "groupreduce over %s: a plain numeric column is needed", dt_name(ve.dtype).c_str());
-    const int b = dt_base(ve.dtype);
-    kinds[(size_t)m] = dt_isfloat(b) ? 2 : (dt_issigned(b) ? 0 : 1);
+    kinds[(size_t)m] = value_kind(dt_base(ve.dtype));
   }
   return kinds;
 }

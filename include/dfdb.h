@@ -113,6 +113,12 @@ int32_t dfdb_jit_cache_dir(char* buf, size_t cap);
  *   "rccl_bracket": the ncclGroupStart / ncclGroupEnd bracket of every RCCL exchange (csrc/group.cpp) driven by a stub collective table: three all-reduces of
  *   which number `arg` fails (0 = none, -1 = ncclGroupStart itself, -2 = ncclGroupEnd), then a second exchange on the same communicator state.
  *   out[0..5] = GroupStart calls, GroupEnd calls, collectives issued, status of the first exchange, status of the second, communicator marked dead.
+ *   "value_rules": the host side of csrc/value_rules.hpp, the one definition of value images, accumulator kinds, order images, Float64 min / max and the
+ *   integer limits, which host and kernels compile from the same text.  arg = function | parameter << 8 | is_min << 16; the nout operands are bit patterns
+ *   in out (a narrow column value in its low bytes) and every result replaces its operand.  Functions: 0 key_image and 1 value_image (parameter: dtype),
+ *   2 order_image (parameter: accumulator kind, 0 signed / 1 unsigned / 2 float), 3 minmax_f64 over the pairs out[2i], out[2i + 1] (the result in out[2i]),
+ *   4 int_lo, 5 int_hi and 6 wrap_int (parameter: dtype; 4 and 5 ignore the operand), 7 value_kind (dtype), 8 kind_dtype (kind), 9 the reduction identity of
+ *   the DFDB_AGG_* operator in the operand (parameter: kind).
  * An unknown name is ArgumentError. */
 int32_t dfdb_selftest(const char* name, int64_t arg, int64_t* out, int32_t nout);
 int32_t dfdb_device_count(int32_t* n);   /* visible HIP devices (0 without a GPU: no error); the Julia shim forms a group when n > 1 */

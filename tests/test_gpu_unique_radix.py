@@ -98,7 +98,7 @@ def test_radix_unique_is_first_appearance(dfdb_mod, ctx, kind):
 
 @pytest.mark.parametrize("dt", ["int8", "int16", "int32", "uint8", "uint16", "uint32", "float32", "uint64"])
 def test_radix_unique_narrow_and_unsigned_keys(dfdb_mod, ctx, dt):
-    """the keys that are not eight raw bytes (k_radix.hip kKindAny: rkey_fixed makes the image) and UInt64, over a table whose last tile is partial"""
+    """the keys that are not eight raw bytes (k_radix.hip kKindAny: key_image makes the image) and UInt64, over a table whose last tile is partial"""
     rng = np.random.default_rng(11)
     n = 1_300_007
     if dt == "float32":
