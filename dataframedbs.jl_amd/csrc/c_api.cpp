@@ -511,6 +511,9 @@ int32_t dfdb_select_indices(dfdb_query* q, int64_t* out, int64_t cap, int32_t me
 int32_t dfdb_result_string_bytes(dfdb_query* q, int32_t i, int64_t* nbytes) { return guard([&] { NEEDQT(q); NEED(nbytes); *nbytes = query_out_of_core(q) ? ooc_string_bytes(q, i) : query_string_bytes(q, i); }); }
 int32_t dfdb_materialize(dfdb_query* q, dfdb_outcol* outs, int32_t ncols) { return guard([&] { NEEDQT(q); if (ncols > 0) NEED(outs); if (query_out_of_core(q)) { ooc_materialize(q, outs, ncols); return; } query_materialize(q, outs, ncols); }); }
 int32_t dfdb_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double* out_f) { return guard([&] { NEEDQT(q); if (query_out_of_core(q)) { ooc_aggregate(q, op, i, out_i, out_f); return; } query_aggregate(q, op, i, out_i, out_f); }); }
+int32_t dfdb_order_statistics(dfdb_query* q, int32_t proj_col, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts) {
+  return guard([&] { NEEDQT(q); if (nranks > 0) NEED(ranks); query_order_statistics(q, proj_col, ranks, nranks, out_i, out_f, counts); });
+}
 
 
 /* ---- only what the view needs, resident only if it fits (view.jl:183-190, blocksiterator.jl:20-33) ---- */

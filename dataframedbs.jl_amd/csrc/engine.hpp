@@ -219,6 +219,7 @@ void query_select_indices(dfdb_query* q, int64_t* out, int64_t cap, int32_t memk
 int64_t query_string_bytes(dfdb_query* q, int i);
 void query_materialize(dfdb_query* q, dfdb_outcol* outs, int32_t ncols);
 void query_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double* out_f);
+void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts);   // project.cpp over k_select.hip
 void query_unique(dfdb_query* q, int32_t p);
 void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes);
 void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f);

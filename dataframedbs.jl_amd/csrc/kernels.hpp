@@ -174,6 +174,18 @@ void launch_reduce(hipStream_t s, const uint64_t* bitmap, const void* col, int32
                    void* result /* 16 bytes: i64/u64 or f64 result + count */);
 size_t reduce_scratch_bytes();
 
+// ---- K11: order statistics by radix select (k_select.hip) -------------------------------------------
+// One pass: per group g < ngroups, the histogram of key bits [shift, shift + 8) over the selected, non-missing rows whose key bits above them equal
+// prefix[g] (distinct prefixes), added to hist[g * 256 + digit]; first: also the counts {not missing, missing, NaN} of the selected rows, added to
+// counts[0 .. 3).  Both are 64-bit counters the caller zeroes; ngroups = 0 with first counts only.  missing: the column's bitmap or null.
+// full: the key is the 64-bit order image (select_key_bits = 64) instead of the same order in the column's own width.
+constexpr int kSelectMaxRanks = 16;
+struct SelectPass { uint64_t prefix[kSelectMaxRanks]; int32_t ngroups; int32_t shift; int32_t first; };
+void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const uint64_t* missing, const void* col, int32_t dtype, bool full,
+                        int64_t nrows, const SelectPass& P, uint64_t* hist /* [kSelectMaxRanks * 256] */, uint64_t* counts /* [3] */);
+int select_key_bits(int dtype, bool full);
+uint64_t select_key_value(int dtype, bool full, uint64_t key);      // a finished key -> the value's 64 accumulator bits (integers widened, floats as Float64)
+
 // ---- unique(col) as a selection of first occurrences (k_unique.hip: hash table of {key, smallest row}; k_unique_dense.hip: integer keys of a small range)
 struct UniqueEntry { uint64_t key, row; };
 void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t row0, int64_t row1,

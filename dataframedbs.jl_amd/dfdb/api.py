@@ -800,6 +800,24 @@ class _Query:
         # Base.sum widens unsigned element types to UInt64 (Base.add_sum), minimum / maximum keep them: the 64 bits are an unsigned number
         return oi.value & 0xFFFFFFFFFFFFFFFF if dt in (ir.U8, ir.U16, ir.U32, ir.U64) else oi.value
 
+    def order_statistics(self, ranks, col: int = 0):
+        """dfdb_order_statistics: the values at the 1-based `ranks` (any number: 16 per call) among the selected non-missing values of projection column
+        `col` in isless order, and the counts (not missing, missing, NaN) of the selected rows"""
+        ranks = np.ascontiguousarray(ranks, np.int64).reshape(-1)
+        dt = self.coltype(col) & ir.DTYPE_MASK
+        isf = dt in (ir.F32, ir.F64)
+        out = np.zeros(len(ranks), np.float64 if isf else np.int64)
+        cnt = np.zeros(3, np.int64)
+        for lo in range(0, max(len(ranks), 1), 16):
+            r, o = ranks[lo:lo + 16], out[lo:lo + 16]
+            N.check(N.load().dfdb_order_statistics(self._h, col, r.ctypes.data if len(r) else None, len(r), None if isf else o.ctypes.data,
+                                                   o.ctypes.data if isf else None, cnt.ctypes.data))
+        if dt in (ir.U8, ir.U16, ir.U32, ir.U64):
+            out = out.view(np.uint64)
+        elif dt == ir.BOOL:
+            out = out != 0
+        return out, (int(cnt[0]), int(cnt[1]), int(cnt[2]))
+
 
 class _ChunkQuery(_Query):
     """One chunk of a streamed view: the engine owns the handle (valid until the stream advances)."""
@@ -1095,6 +1113,67 @@ class DFColumn:
         s, n = self._aggregate(N.AGG_SUM, with_count=True)      # one evaluation of the selection gives both
         return float("nan") if n == 0 else s / n
 
+    # -- order statistics: Statistics.median / quantile, which the reference answers by collecting Base.iterate(::DFColumn) (column.jl:102-126) and sorting;
+    # here the device selects the one or two values a result is made of (dfdb_order_statistics, csrc/k_select.hip)
+    def order_statistics(self, ranks):
+        """(values, (n, missing, nan)): the values at the 1-based `ranks` among the n non-missing selected values in isless order (integers by value,
+        floats -Inf .. -0.0 < 0.0 .. Inf < NaN; Float32 widened to Float64), and how many selected rows are not missing, missing, NaN"""
+        return self.view._query().order_statistics(ranks)
+
+    def _ordered_counts(self, q):
+        """(n, missing) before any rank is known: the selection's own count when nothing can be missing, else one counting pass"""
+        if self.eltype & ir.NULLABLE:
+            n, nmiss, _ = q.order_statistics([])[1]
+            return n, nmiss
+        return q.count(), 0
+
+    def median(self):
+        """Statistics.median(col): None (missing) if a selected row is missing, NaN if one is NaN, else middle(v[mid]) for odd n and
+        middle(v[mid], v[mid + 1]) = v[mid] / 2 + v[mid + 1] / 2 for even n, mid = (1 + n) ÷ 2; Float32 for a Float32 column, else Float64"""
+        q = self.view._query()
+        n, nmiss = self._ordered_counts(q)
+        if nmiss:
+            return None
+        if n == 0:
+            raise ValueError("ArgumentError: median of an empty array is undefined")
+        mid = (1 + n) // 2
+        v, (_, _, nnan) = q.order_statistics([mid] if n % 2 else [mid, mid + 1])
+        F = np.float32 if (self.eltype & ir.DTYPE_MASK) == ir.F32 else np.float64
+        if nnan:
+            return F("nan")
+        with np.errstate(all="ignore"):
+            x = [F(int(e)) if v.dtype.kind in "iub" else F(e) for e in v]
+            return x[0] if n % 2 else x[0] / F(2) + x[1] / F(2)
+
+    def quantile(self, p):
+        """Statistics.quantile(col, p) with the default parameters (alpha = beta = 1): aleph = n p + (1 - p), j = clamp(floor(aleph), 1, n - 1),
+        gamma = clamp(aleph - j, 0, 1), a = v[j], b = v[j + 1]: a + gamma (b - a) when both are finite, else (1 - gamma) a + gamma b; Float64.
+        A vector of p gives a vector."""
+        ps = np.atleast_1d(np.asarray(p, np.float64))
+        if not np.all((ps >= 0) & (ps <= 1)):
+            raise ValueError("ArgumentError: input probability out of [0,1] range")
+        q = self.view._query()
+        n, nmiss = self._ordered_counts(q)
+        if nmiss:
+            raise ValueError("ArgumentError: quantiles are undefined in presence of missing values")
+        if n == 0:
+            raise ValueError("ArgumentError: empty data vector")
+        js = [1 if n == 1 else min(max(int(np.floor(n * x + (1 - x))), 1), n - 1) for x in ps]
+        v, (_, _, nnan) = q.order_statistics([r for j in js for r in ((j,) if n == 1 else (j, j + 1))])
+        if nnan:
+            raise ValueError("ArgumentError: quantiles are undefined in presence of NaNs")
+        v = [float(int(e)) if v.dtype.kind in "iub" else float(e) for e in v]
+        out = np.empty(len(ps), np.float64)
+        with np.errstate(all="ignore"):
+            for k, (x, j) in enumerate(zip(ps, js)):
+                if n == 1:
+                    out[k] = v[k]
+                    continue
+                a, b = np.float64(v[2 * k]), np.float64(v[2 * k + 1])
+                g = min(max(n * x + (1 - x) - j, 0.0), 1.0)
+                out[k] = a + g * (b - a) if np.isfinite(a) and np.isfinite(b) else (1 - g) * a + g * b
+        return float(out[0]) if np.ndim(p) == 0 else out
+
     # -- broadcasting (columnbroadcast.jl:19-62): every DFColumn argument must share (table, selection)
     def _bc(self, op: int, other, swap: bool = False) -> "DFColumn":
         if isinstance(other, DFColumn):
@@ -1137,6 +1216,10 @@ class DFColumn:
     def __bool__(self): raise TypeError("a DFColumn has no truth value: use & | ~ and split chained comparisons")
 
     def __repr__(self): return f"DFColumn{{{ir.dtype_name(self.eltype)}}}"
+
+
+def median(c: DFColumn): return c.median()                # Statistics.median(col)
+def quantile(c: DFColumn, p): return c.quantile(p)        # Statistics.quantile(col, p)
 
 
 def col_equal(a: DFColumn, b: DFColumn) -> bool:

@@ -624,6 +624,72 @@ gpu_mean(c::DFColumn) = ((s, n) = gpu_aggregate(c, 1); s / n)
 gpu_sum_count(c::DFColumn) = gpu_aggregate(c, 1)
 
 """
+The values at the 1-based `ranks` (at most 16) among the n selected, non-missing values of a DFColumn in `isless` order, as Float64 (integers and Bool
+converted, Float32 widened), and the counts (n, missing, NaN) of the selected rows: dfdb_order_statistics, a radix select on the device.  What
+Statistics.median / quantile need of a column, which the reference collects through Base.iterate(::DFColumn) (column.jl:102-126) and sorts.  The sharded
+form, a view that stays on disk and a compressed-only column are `Unsupported` (the stock path answers).
+"""
+function gpu_order_statistics(c::DFColumn{T}, ranks::Vector{Int64}) where {T}
+    S = Base.nonmissingtype(T)
+    S <: Union{Int8,Int16,Int32,Int64,UInt8,UInt16,UInt32,UInt64,Bool,Float32,Float64} || throw(Unsupported("order statistics over $(T)"))
+    sharded() && throw(Unsupported("order statistics over a sharded table"))
+    nr = length(ranks)
+    vi = zeros(Int64, max(nr, 1)); vf = zeros(Float64, max(nr, 1)); cnt = zeros(Int64, 3)
+    with_query(c.view) do q
+        check(ccall((:dfdb_order_statistics, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int64}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                    q, 0, ranks, nr, vi, vf, cnt))
+    end
+    vals = S <: AbstractFloat ? vf[1:nr] : (S <: Unsigned ? Float64.(reinterpret(UInt64, vi[1:nr])) : Float64.(vi[1:nr]))
+    return (vals, cnt[1], cnt[2], cnt[3])
+end
+"the counts alone before any rank is known: the selection's own count when nothing can be missing, else one counting pass"
+ordered_counts(c::DFColumn{T}) where {T} = Missing <: T ? gpu_order_statistics(c, Int64[])[2:3] : (gpu_nrow(c.view), 0)
+
+"""
+Statistics.median(col): `missing` if a selected row is missing, NaN if one is NaN, else middle(v[mid]) for odd n and middle(v[mid], v[mid+1]) =
+v[mid]/2 + v[mid+1]/2 for even n with mid = (1 + n) ÷ 2; Float32 arithmetic for a Float32 column, else Float64 (integers and Bool convert).
+The formulas are Statistics.jl's as restated in INTEGRATION.md; they are pinned by the repository's tests, not against a running Julia.
+"""
+function gpu_median(c::DFColumn{T}) where {T}
+    F = Base.nonmissingtype(T) === Float32 ? Float32 : Float64
+    n, nmiss = ordered_counts(c)
+    nmiss > 0 && return missing
+    n == 0 && throw(ArgumentError("median of an empty array is undefined"))
+    mid = (1 + n) ÷ 2
+    v, _, _, nnan = gpu_order_statistics(c, isodd(n) ? Int64[mid] : Int64[mid, mid + 1])
+    nnan > 0 && return F(NaN)
+    return isodd(n) ? F(v[1]) : F(v[1]) / 2 + F(v[2]) / 2
+end
+
+"Statistics.quantile(col, p) with the default parameters (alpha = beta = 1), a number or a vector of p; Float64"
+function gpu_quantile(c::DFColumn, p::Union{Real,AbstractVector{<:Real}})
+    ps = p isa Real ? Float64[p] : Float64.(p)
+    all(x -> 0 <= x <= 1, ps) || throw(ArgumentError("input probability out of [0,1] range"))
+    n, nmiss = ordered_counts(c)
+    nmiss > 0 && throw(ArgumentError("quantiles are undefined in presence of missing values"))
+    n == 0 && throw(ArgumentError("empty data vector"))
+    js = Int64[n == 1 ? 1 : clamp(floor(Int64, n * x + (1 - x)), 1, n - 1) for x in ps]
+    ranks = n == 1 ? js : Int64[r for j in js for r in (j, j + 1)]
+    v = Float64[]; nnan = 0
+    for lo in 1:16:length(ranks)                        # 16 ranks per call
+        part, _, _, nn = gpu_order_statistics(c, ranks[lo:min(lo + 15, length(ranks))])
+        append!(v, part); nnan = nn
+    end
+    nnan > 0 && throw(ArgumentError("quantiles are undefined in presence of NaNs"))
+    out = Vector{Float64}(undef, length(ps))
+    for (k, x) in enumerate(ps)
+        if n == 1
+            out[k] = v[k]
+            continue
+        end
+        a = v[2k - 1]; b = v[2k]
+        g = clamp(n * x + (1 - x) - js[k], 0.0, 1.0)
+        out[k] = (isfinite(a) && isfinite(b)) ? a + g * (b - a) : (1 - g) * a + g * b
+    end
+    return p isa Real ? out[1] : out
+end
+
+"""
 groupreduce(view, (:by,); out = :col => Stat()) on the device (src/tables/aggregate.jl:1-36: exported by the reference, unfinished there — it numbers the
 groups in order of first appearance and stops).  Returns a DataFrame with one row per distinct value of `by` in order of first appearance, the group's
 row count and `stat(col)`, stat in (:count, :sum, :minimum, :maximum, :mean).  Sharded like everything else when a group is active.
@@ -790,7 +856,7 @@ end
 """
 Route the hot-path consumers of DataFrameDBs through the MI355X engine, falling back to the stock path when an expression is outside the IR:
 `materialize(::DFView)`, `nrow(::DFView)` (and with it `size` / `length(::DFColumn)`), `materialize(::DFColumn)`, `copyto!(dest, ::DFColumn)`,
-`copyto!(dest, ::Broadcasted{DFColumnStyle})` (`dest .= col_expr`), and `sum` / `minimum` / `maximum` / `Statistics.mean` / `unique` of a DFColumn
+`copyto!(dest, ::Broadcasted{DFColumnStyle})` (`dest .= col_expr`), and `sum` / `minimum` / `maximum` / `Statistics.mean` / `Statistics.median` / `Statistics.quantile` / `unique` of a DFColumn
 (which otherwise pull one element at a time through `Base.iterate(::DFColumn)`, column.jl:102-126).
 """
 function enable!()
@@ -822,6 +888,8 @@ function enable!()
         Base.maximum(c::DFColumn) = with_fallback(() -> gpu_maximum(c), Base.maximum, c)
         Statistics.mean(c::DFColumn) = with_fallback(() -> gpu_mean(c), Statistics.mean, c)
         Base.unique(c::DFColumn) = with_fallback(() -> gpu_unique(c), Base.unique, c)
+        Statistics.median(c::DFColumn) = with_fallback(() -> gpu_median(c), Statistics.median, c)
+        Statistics.quantile(c::DFColumn, p) = with_fallback(() -> gpu_quantile(c, p), Statistics.quantile, c, p)
     end
     ENABLED[] = true
     nothing

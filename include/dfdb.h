@@ -389,6 +389,24 @@ int32_t dfdb_materialize(dfdb_query* q, dfdb_outcol* outs, int32_t ncols);
 /* sum/min/max/count of projection column i over the selected rows; Float64 sums are pairwise
  * (tolerance documented in DESIGN.md), integer results exact */
 int32_t dfdb_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double* out_f);
+/* k-th smallest values of projection column proj_col over the selected rows: what Statistics.median / quantile need of a column
+ * (they collect Base.iterate(::DFColumn), column.jl:102-126, and sort), by radix select on the device (csrc/k_select.hip) — exact, and
+ * independent of grid size and launch order.
+ *   column   a plain numeric column: Int8..Int64, UInt8..UInt64, Float32, Float64, Bool, nullable or not.  A String column is
+ *            DFDB_ERR_ARGUMENT; a computed column is DFDB_ERR_UNSUPPORTED (materialise it as a column first: dfdb_table_add_from_query).
+ *   counts   [3], filled by every call that succeeds: the selected rows that are not missing (n), the selected rows that are missing, the
+ *            selected non-missing rows that are NaN (0 for integers).  Bytes under a set missing bit are garbage (quirk Q11): they are neither
+ *            ranked nor counted as NaN.  May be NULL.
+ *   ranks    nranks (0 to 16, else DFDB_ERR_ARGUMENT) 1-based positions among the n non-missing selected values in the order of isless:
+ *            integers by value, floats -Inf .. -0.0 < 0.0 .. Inf, every NaN last.  Any order, repeats allowed.  A rank outside 1..n is
+ *            DFDB_ERR_BOUNDS (any rank when n = 0); nranks = 0 returns the counts only.
+ *   results  as dfdb_aggregate returns them: out_i[k] for integer and Bool columns (the value widened to 64 bits, unsigned ones as their bits),
+ *            out_f[k] for floats (Float32 widened exactly; every NaN comes back as the canonical quiet NaN).  The other pointer may be NULL.
+ * The column must be resident decoded.  Three forms are refused with DFDB_ERR_UNSUPPORTED and a message that names the form — a view that is
+ * out of core (required columns not resident), a compressed-only column (ctx option "keep_compressed" = 2) — or have no entry point yet — the
+ * sharded form over a dfdb_group; all three are follow-ups.  The query's selection is left as it was found;
+ * dfdb_query_reset / _execute mean what they meant. */
+int32_t dfdb_order_statistics(dfdb_query* q, int32_t proj_col, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts);
 
 /* ---- out of core behind the ordinary entry points (round 6) ----
  * The reference never holds more than one block per column (src/io/blocksiterator.jl:98-121, src/io/BlockStreams.jl:9-15; "memory use is O(block)",
