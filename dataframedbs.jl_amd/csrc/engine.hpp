@@ -63,7 +63,10 @@ struct Column {
   size_t data_off = 0;  // first block inside the file
   std::shared_ptr<BlockIndex> bix;   // block locations of `file`, as far as a stream or table_column_stats has walked them
 };
-inline StrSide str_side(const Column& c) { return StrSide{c.data.as<int32_t>(), (const int64_t*)c.tile_off.p, c.bytes.as<uint8_t>()}; }   // a resident String column, as the kernels take it
+// a resident column as the launchers take it (kernels.hpp): a flat String column, a fixed-width column (null: no column — the count-only reducer)
+inline StrSide str_side(const Column& c) { return StrSide{c.data.as<int32_t>(), (const int64_t*)c.tile_off.p, c.bytes.as<uint8_t>()}; }
+inline ColRef col_ref(const Column& c) { return ColRef{c.data.p, dt_base(c.dtype), dt_nullable(c.dtype) ? c.missing.as<uint64_t>() : nullptr}; }
+inline ColRef col_ref(const Column* c) { return c ? col_ref(*c) : ColRef{}; }
 
 enum StageKind { ST_RANGE = 0, ST_INTEGER = 1, ST_INDICES = 2, ST_PRED = 3 };
 

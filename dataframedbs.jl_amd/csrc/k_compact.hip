@@ -16,6 +16,7 @@
 #include "device_utils.hpp"
 #include "value_rules.hpp"
 #include "kernels.hpp"
+#include "launch_dispatch.hpp"
 #include "../../include/dfdb_ir.h"
 
 namespace dfdb {
@@ -295,13 +296,10 @@ void launch_gather_transform(hipStream_t s, const uint64_t* bitmap, const uint64
   const int64_t nct = (nrows + kCTile - 1) / kCTile;
   if (nct == 0) return;
   const dim3 g(grid_for_ctiles(nct)), b(kBlock);
-#define DFDB_GT(T) hipLaunchKernelGGL((k_gather_transform<T>), g, b, 0, s, bitmap, prefix, (const T*)src, (uint64_t*)dst, nct, out_cap, (int)tf.pre, tf.pre_magic, (int)tf.pre_shift, tf.pre_d)
-  switch (src_dtype) {
-    case DFDB_I8: DFDB_GT(int8_t); break; case DFDB_I16: DFDB_GT(int16_t); break; case DFDB_I32: DFDB_GT(int32_t); break; case DFDB_I64: DFDB_GT(int64_t); break;
-    case DFDB_U8: DFDB_GT(uint8_t); break; case DFDB_U16: DFDB_GT(uint16_t); break; case DFDB_U32: DFDB_GT(uint32_t); break; case DFDB_U64: DFDB_GT(uint64_t); break;
-    case DFDB_F32: DFDB_GT(float); break; default: DFDB_GT(double); break;
-  }
-#undef DFDB_GT
+  with_dtype<DtNumbers>(src_dtype, [&](auto c) {
+    using T = typename decltype(c)::type;
+    hipLaunchKernelGGL((k_gather_transform<T>), g, b, 0, s, bitmap, prefix, (const T*)src, (uint64_t*)dst, nct, out_cap, (int)tf.pre, tf.pre_magic, (int)tf.pre_shift, tf.pre_d);
+  });
 }
 
 // projection of a predicate column whose selected values the scan already wrote per tile (k_scan_cmp / k_scan_terms CAP):
@@ -483,18 +481,7 @@ static void launch_reduce_t(hipStream_t s, const uint64_t* bitmap, const void* c
 }
 
 void launch_reduce(hipStream_t s, const uint64_t* bitmap, const void* col, int32_t dtype, int op, int64_t nrows, void* partials, void* result) {
-  switch (dtype) {
-    case DFDB_I8:  launch_reduce_t<int8_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_I16: launch_reduce_t<int16_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_I32: launch_reduce_t<int32_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_I64: launch_reduce_t<int64_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_U8: case DFDB_BOOL: launch_reduce_t<uint8_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_U16: launch_reduce_t<uint16_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_U32: launch_reduce_t<uint32_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_U64: launch_reduce_t<uint64_t>(s, bitmap, col, op, nrows, partials, result); break;
-    case DFDB_F32: launch_reduce_t<float>(s, bitmap, col, op, nrows, partials, result); break;
-    default:       launch_reduce_t<double>(s, bitmap, col, op, nrows, partials, result); break;
-  }
+  with_dtype<DtValues>(dtype, [&](auto c) { launch_reduce_t<typename decltype(c)::type>(s, bitmap, col, op, nrows, partials, result); });
 }
 
 }  // namespace dfdb

@@ -83,11 +83,10 @@ __global__ __launch_bounds__(kBlock) void k_dict_encode(const int32_t* __restric
     }
   }
 }
-void launch_dict_encode(hipStream_t s, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const DictSlot* slots, uint32_t nslots,
-                        const uint8_t* dict_bytes, uint16_t* codes, int64_t nrows, const DictMiss& miss) {
+void launch_dict_encode(hipStream_t s, const StrSide& a, const DictSlot* slots, uint32_t nslots, const uint8_t* dict_bytes, uint16_t* codes, int64_t nrows, const DictMiss& miss) {
   const int64_t nt = (nrows + kTile - 1) / kTile;
   if (nt == 0) return;
-  hipLaunchKernelGGL(k_dict_encode, dim3(grid_for(nt, 2048)), dim3(kBlock), 0, s, sizes, tile_off, bytes, slots, nslots - 1, dict_bytes, codes, nrows, nt, miss);
+  hipLaunchKernelGGL(k_dict_encode, dim3(grid_for(nt, 2048)), dim3(kBlock), 0, s, a.sizes, a.tile_off, a.bytes, slots, nslots - 1, dict_bytes, codes, nrows, nt, miss);
 }
 
 // codes -> bitmap + tile counts: lane l of a wave takes 8 consecutive rows (one 16-byte load), looks each code up in the bit table (LDS) and writes
@@ -191,14 +190,13 @@ __global__ __launch_bounds__(kBlock) void k_dict_pair(const uint16_t* __restrict
     if (lane == 0) tile_counts[tile] = cnt;
   }
 }
-void launch_dict_pair(hipStream_t s, const uint16_t* codes_a, const uint16_t* codes_b, const uint32_t* rank_a, int32_t n_a, const uint32_t* rank_b, int32_t n_b, int op,
-                      uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing) {
+void launch_dict_pair(hipStream_t s, const DictSide& a, const DictSide& b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing) {
   const int64_t nt = (nrows + kTile - 1) / kTile;
   if (nt == 0) return;
-  const int use_lds = n_a + n_b <= kDictPairLds ? 1 : 0;
-  const size_t lds = use_lds ? (size_t)(n_a + n_b) * 4 : 0;
-  if (and_existing) hipLaunchKernelGGL(k_dict_pair<true>, dim3(grid_for(nt, 2048)), dim3(kBlock), lds, s, codes_a, codes_b, rank_a, n_a, rank_b, n_b, op, use_lds, bitmap, tile_counts, nrows, nt);
-  else hipLaunchKernelGGL(k_dict_pair<false>, dim3(grid_for(nt, 2048)), dim3(kBlock), lds, s, codes_a, codes_b, rank_a, n_a, rank_b, n_b, op, use_lds, bitmap, tile_counts, nrows, nt);
+  const int use_lds = a.n + b.n <= kDictPairLds ? 1 : 0;
+  const size_t lds = use_lds ? (size_t)(a.n + b.n) * 4 : 0;
+  if (and_existing) hipLaunchKernelGGL(k_dict_pair<true>, dim3(grid_for(nt, 2048)), dim3(kBlock), lds, s, a.codes, b.codes, a.rank, a.n, b.rank, b.n, op, use_lds, bitmap, tile_counts, nrows, nt);
+  else hipLaunchKernelGGL(k_dict_pair<false>, dim3(grid_for(nt, 2048)), dim3(kBlock), lds, s, a.codes, b.codes, a.rank, a.n, b.rank, b.n, op, use_lds, bitmap, tile_counts, nrows, nt);
 }
 
 // Projection of a dictionary column.  K3 first compacts the selected rows' CODES (a 2-byte gather); what is left is flat work over the selected rows in

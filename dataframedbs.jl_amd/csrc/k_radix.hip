@@ -21,6 +21,7 @@
 #include "device_utils.hpp"
 #include "value_rules.hpp"
 #include "kernels.hpp"
+#include "launch_dispatch.hpp"      // (kKindRaw8 / kKindF64 / kKindAny: what a key load is)
 #include "../../include/dfdb_ir.h"
 
 namespace dfdb {
@@ -42,7 +43,6 @@ __device__ __forceinline__ uint32_t rhash(uint64_t key) {
 
 struct __attribute__((packed, aligned(4))) Rec12 { uint32_t lo, hi, row; };
 struct __attribute__((packed, aligned(4))) Rec20 { uint32_t lo, hi, row, vlo, vhi; };
-enum { kKindRaw8 = 0, kKindF64 = 1, kKindAny = 2 };       // what a key load is: 8 raw bytes (Int64 / UInt64), 8 bytes + isequal's one NaN (Float64), anything narrower (key_image)
 __device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {     // a value every lane of the wave holds, into scalar registers
   return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32;
 }
@@ -753,7 +753,6 @@ int64_t radix_rows_per_chunk(int64_t nrows, int chunks) {
   return (per + kRTile - 1) / kRTile * kRTile;              // whole tiles of the partition pass (and whole bitmap words)
 }
 static size_t radix_partition_lds_bytes(int block) { return (size_t)part_lds_words(block) * 4 + (size_t)block * 8 * 8; }
-static int radix_kind(int dtype) { return dtype == DFDB_F64 ? kKindF64 : (dtype == DFDB_I64 || dtype == DFDB_U64 ? kKindRaw8 : kKindAny); }
 int radix_share() { return kRShare; }
 // the record pool for `cnt` selected rows in 2^kbits partitions: every stream (partition, share) ends in a page that is not full, one page is nobody's
 // (where a stream that gave up puts its records); a stream may take `maxv` pages: 16 times its even share — the sample already turned skewed columns away
@@ -763,45 +762,37 @@ int radix_group_slots() { return kGSlots; }
 int radix_hot_slots() { return kHotSlots; }
 uint32_t radix_pool_maxv(int64_t cnt, int kbits) { const int64_t even = ((cnt + kRPage - 1) / kRPage + ((int64_t)kRShare << kbits) - 1) / ((int64_t)kRShare << kbits); return (uint32_t)(16 * even + 16); }
 
-bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int kbits, int chunks, int step,
-                         uint32_t* counts) {
+bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, int step, uint32_t* counts) {
+  const int kbits = grid.kbits;
   if (kbits < 6 || kbits > 10 || nrows < 1 || step < 1) return false;
-  const int64_t rpc = radix_rows_per_chunk(nrows, chunks);
+  const int64_t rpc = radix_rows_per_chunk(nrows, grid.chunks);
   const size_t lds = ((size_t)1 << kbits) * 4;
-  switch (radix_kind(dtype)) {
-    case kKindRaw8: hipLaunchKernelGGL(k_radix_hist<kKindRaw8>, dim3(chunks), dim3(kRBlock), lds, s, sel, col, dtype, missing, nrows, rpc, kbits, counts, step); break;
-    case kKindF64: hipLaunchKernelGGL(k_radix_hist<kKindF64>, dim3(chunks), dim3(kRBlock), lds, s, sel, col, dtype, missing, nrows, rpc, kbits, counts, step); break;
-    default: hipLaunchKernelGGL(k_radix_hist<kKindAny>, dim3(chunks), dim3(kRBlock), lds, s, sel, col, dtype, missing, nrows, rpc, kbits, counts, step); break;
-  }
+  with_radix_kind(key.dtype, [&](auto kind) {
+    hipLaunchKernelGGL(k_radix_hist<decltype(kind)::value>, dim3(grid.chunks), dim3(kRBlock), lds, s, sel, key.data, (int)key.dtype, key.missing, nrows, rpc, kbits, counts, step);
+  });
   return true;
 }
-template <int KIND, bool HASVAL, bool V8, bool HOT>
-static bool radix_partition_go(hipStream_t s, const uint64_t* sel, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int kbits, int chunks,
-                               const RadixPool& pool, uint32_t* recs_out, uint64_t* aux, const RadixVals& vals) {
-  if (!allow_dynamic_lds((const void*)k_radix_partition<KIND, kRBlock, HASVAL, V8, HOT>, radix_partition_lds_bytes(kRBlock))) return false;      // (+ the static arrays: under 160 KB)
-  hipLaunchKernelGGL((k_radix_partition<KIND, kRBlock, HASVAL, V8, HOT>), dim3(chunks), dim3(kRBlock), radix_partition_lds_bytes(kRBlock), s, sel, col, dtype, missing, nrows,
-                     radix_rows_per_chunk(nrows, chunks), kbits, pool, recs_out, aux, vals);
-  return hipGetLastError() == hipSuccess;
-}
 // (512-thread workgroups sorting 4096 rows, two per CU, instead of one of 1024 sorting 8192: 5.36-5.43 ms against 5.32-5.33 — the pass waits for its stores either way)
-// group = nullptr: 12-byte records for unique; otherwise 20-byte records {key, row, value} for groupreduce (group->valcol may be null: count only)
-bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int kbits, int chunks,
-                            const RadixPool& pool, uint32_t* recs_out, uint64_t* aux, const RadixGroup* group, bool hot) {
+// group = nullptr: 12-byte records for unique; otherwise 20-byte records {key, row, value} for groupreduce (group->val may be no column: count only)
+bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, const RadixPool& pool, uint32_t* recs_out, uint64_t* aux,
+                            const RadixGroup* group, bool hot) {
+  const int kbits = grid.kbits, chunks = grid.chunks;
   if (kbits < 6 || kbits > 10 || nrows < 1 || chunks % kRShare) return false;
   RadixVals v{};
-  if (group) { v.col = group->valcol; v.vdt = group->valdt; v.gspec = group->gspec; v.gop = group->gop; v.vkind = group->vkind; }
-  const bool v8 = !group || !group->valcol || group->valdt == DFDB_I64 || group->valdt == DFDB_U64 || group->valdt == DFDB_F64;
-#define DFDB_RP(K) (group ? (!v8 ? radix_partition_go<K, true, false, true>(s, sel, col, dtype, missing, nrows, kbits, chunks, pool, recs_out, aux, v) \
-                                 : hot ? radix_partition_go<K, true, true, true>(s, sel, col, dtype, missing, nrows, kbits, chunks, pool, recs_out, aux, v) \
-                                       : radix_partition_go<K, true, true, false>(s, sel, col, dtype, missing, nrows, kbits, chunks, pool, recs_out, aux, v)) \
-                          : (hot ? radix_partition_go<K, false, true, true>(s, sel, col, dtype, missing, nrows, kbits, chunks, pool, recs_out, aux, v) \
-                                 : radix_partition_go<K, false, true, false>(s, sel, col, dtype, missing, nrows, kbits, chunks, pool, recs_out, aux, v)))
-  switch (radix_kind(dtype)) {
-    case kKindRaw8: return DFDB_RP(kKindRaw8);
-    case kKindF64: return DFDB_RP(kKindF64);
-    default: return DFDB_RP(kKindAny);
-  }
-#undef DFDB_RP
+  if (group) { v.col = group->val.data; v.vdt = group->val.dtype; v.gspec = group->gspec; v.gop = group->gop; v.vkind = group->vkind; }
+  const bool v8 = !group || !group->val.data || dt_is_w8(group->val.dtype);
+  return with_radix_kind(key.dtype, [&](auto kind) {
+    auto go = [&](auto hasval, auto v8_c, auto hot_c) {
+      const auto kernel = k_radix_partition<decltype(kind)::value, kRBlock, decltype(hasval)::value, decltype(v8_c)::value, decltype(hot_c)::value>;
+      if (!allow_dynamic_lds((const void*)kernel, radix_partition_lds_bytes(kRBlock))) return false;      // (+ the static arrays: under 160 KB)
+      hipLaunchKernelGGL(kernel, dim3(chunks), dim3(kRBlock), radix_partition_lds_bytes(kRBlock), s, sel, key.data, (int)key.dtype, key.missing, nrows,
+                         radix_rows_per_chunk(nrows, chunks), kbits, pool, recs_out, aux, v);
+      return hipGetLastError() == hipSuccess;
+    };
+    const std::true_type yes{}; const std::false_type no{};
+    if (group) return !v8 ? go(yes, no, yes) : (hot ? go(yes, yes, yes) : go(yes, yes, no));
+    return hot ? go(no, yes, yes) : go(no, yes, no);
+  });
 }
 bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux,
                         const RadixGroup& group, int cus) {

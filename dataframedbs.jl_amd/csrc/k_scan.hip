@@ -11,6 +11,7 @@
 #include "device_utils.hpp"
 #include "value_rules.hpp"
 #include "kernels.hpp"
+#include "launch_dispatch.hpp"
 #include "../../include/dfdb_ir.h"
 
 namespace dfdb {
@@ -304,20 +305,10 @@ static void launch_cmp_op(hipStream_t s, const void* col, int op, uint64_t cbits
   }
 }
 
-void launch_scan_cmp(hipStream_t s, const void* col, int32_t dtype, int op, uint64_t cbits, uint64_t* bitmap, uint32_t* tile_counts,
-                     int64_t nrows, bool and_existing, bool nt, void* cap, int wt_store) {
-  switch (dtype) {
-    case DFDB_I8:  launch_cmp_op<int8_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_I16: launch_cmp_op<int16_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_I32: launch_cmp_op<int32_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_I64: launch_cmp_op<int64_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_U8: case DFDB_BOOL: launch_cmp_op<uint8_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_U16: launch_cmp_op<uint16_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_U32: launch_cmp_op<uint32_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_U64: launch_cmp_op<uint64_t>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    case DFDB_F32: launch_cmp_op<float>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-    default:       launch_cmp_op<double>(s, col, op, cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store); break;
-  }
+void launch_scan_cmp(hipStream_t s, const ScanTerm& term, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing, bool nt, void* cap, int wt_store) {
+  with_dtype<DtValues>(term.dtype, [&](auto c) {
+    launch_cmp_op<typename decltype(c)::type>(s, term.col, term.op, term.cbits, bitmap, tile_counts, nrows, and_existing, nt, cap, wt_store);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include "device_utils.hpp"
 #include "value_rules.hpp"
 #include "kernels.hpp"
+#include "launch_dispatch.hpp"
 #include "../../include/dfdb_ir.h"
 
 namespace dfdb {
@@ -154,34 +155,20 @@ __global__ __launch_bounds__(kBlock) void k_select_hist(const uint64_t* __restri
   if (P.first && threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&gcounts[threadIdx.x], cnt[threadIdx.x]);
 }
 
-template <int DT>
-static void launch_select_dt(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const uint64_t* missing, const void* col, bool full,
-                             int64_t nrows, const SelectPass& P, uint64_t* hist, uint64_t* counts) {
-  using T = typename SelT<DT>::type;
+void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const ColRef& col, bool full, int64_t nrows, const SelectPass& P, uint64_t* hist,
+                        uint64_t* counts) {
   const int64_t nwords = (nrows + 63) / 64, ntiles = (nwords + 15) / 16;
   int grid = (int)((ntiles + kWavesPerBlock - 1) / kWavesPerBlock);
   if (grid > kSelBlocks) grid = kSelBlocks;
   if (grid < 1) grid = 1;
-  if (full) hipLaunchKernelGGL((k_select_hist<DT, true>), dim3(grid), dim3(kBlock), 0, s, bitmap, tile_counts, missing, (const T*)col, nwords, P,
-                               (unsigned long long*)hist, (unsigned long long*)counts);
-  else hipLaunchKernelGGL((k_select_hist<DT, false>), dim3(grid), dim3(kBlock), 0, s, bitmap, tile_counts, missing, (const T*)col, nwords, P,
-                          (unsigned long long*)hist, (unsigned long long*)counts);
-}
-
-void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const uint64_t* missing, const void* col, int32_t dtype, bool full,
-                        int64_t nrows, const SelectPass& P, uint64_t* hist, uint64_t* counts) {
-  switch (dtype) {
-    case DFDB_I8:  launch_select_dt<DFDB_I8>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_I16: launch_select_dt<DFDB_I16>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_I32: launch_select_dt<DFDB_I32>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_I64: launch_select_dt<DFDB_I64>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_U8: case DFDB_BOOL: launch_select_dt<DFDB_U8>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_U16: launch_select_dt<DFDB_U16>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_U32: launch_select_dt<DFDB_U32>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_U64: launch_select_dt<DFDB_U64>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    case DFDB_F32: launch_select_dt<DFDB_F32>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-    default:       launch_select_dt<DFDB_F64>(s, bitmap, tile_counts, missing, col, full, nrows, P, hist, counts); break;
-  }
+  with_dtype<DtValues>(col.dtype, [&](auto c) {      // (the kernels are instantiated by the enumerator: Bool as DFDB_U8, anything that is no number as DFDB_F64)
+    constexpr int DT = decltype(c)::dtype;
+    using T = typename SelT<DT>::type;
+    if (full) hipLaunchKernelGGL((k_select_hist<DT, true>), dim3(grid), dim3(kBlock), 0, s, bitmap, tile_counts, col.missing, (const T*)col.data, nwords, P,
+                                 (unsigned long long*)hist, (unsigned long long*)counts);
+    else hipLaunchKernelGGL((k_select_hist<DT, false>), dim3(grid), dim3(kBlock), 0, s, bitmap, tile_counts, col.missing, (const T*)col.data, nwords, P,
+                            (unsigned long long*)hist, (unsigned long long*)counts);
+  });
 }
 
 }  // namespace dfdb

@@ -261,13 +261,14 @@ static void launch_short(hipStream_t s, int grid, bool ae, const int32_t* sizes,
   }
 }
 
-void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const uint8_t* pat_host,
-                      const uint8_t* pat_dev, int32_t patlen, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
-                      bool and_existing, const StrCapture* cap, uint32_t max_tile_bytes) {
+void launch_str_match(hipStream_t s, const StrSide& a, const StrPattern& p, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing,
+                      const StrCapture* cap, uint32_t max_tile_bytes) {
   const int64_t ntiles = (nrows + kTile - 1) / kTile;
   if (ntiles == 0) return;
+  const int32_t* sizes = a.sizes; const int64_t* tile_off = a.tile_off; const uint8_t* bytes = a.bytes;
+  const uint8_t* pat_dev = p.dev; const int32_t patlen = p.len;
   Pattern pat; memset(&pat, 0, sizeof pat); pat.len = patlen;
-  if (patlen > 0 && patlen <= 64) memcpy(pat.w, pat_host, (size_t)patlen);   // short patterns ride in the kernel arguments
+  if (patlen > 0 && patlen <= 64) memcpy(pat.w, p.host, (size_t)patlen);   // short patterns ride in the kernel arguments
   const int grid = grid_for(ntiles, 2048);
   const StrMatchForm form = str_match_form(patlen, max_tile_bytes);
   if (form != STR_MATCH_LONG) {

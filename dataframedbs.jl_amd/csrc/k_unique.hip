@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "kernels.hpp"
+#include "launch_dispatch.hpp"
 #include "../../include/dfdb_ir.h"
 
 namespace dfdb {
@@ -566,16 +567,14 @@ static int grid_str_pass(int64_t nt) {
   return (int)b;
 }
 
-void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t row0, int64_t row1,
-                          UniqueEntry* ent, uint64_t mask, uint64_t* aux) {
+void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, UniqueEntry* ent, uint64_t mask, uint64_t* aux) {
   if (row1 <= row0) return;
-  hipLaunchKernelGGL(k_unique_insert, dim3(grid_rows(row1 - row0)), dim3(kBlock), 0, s, bitmap, col, dtype, missing, row0, row1, ent, mask, aux);
+  hipLaunchKernelGGL(k_unique_insert, dim3(grid_rows(row1 - row0)), dim3(kBlock), 0, s, bitmap, key.data, (int)key.dtype, key.missing, row0, row1, ent, mask, aux);
 }
-void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const void* col, int dtype, const uint64_t* missing, int64_t nrows,
-                        const UniqueEntry* ent, uint64_t mask, const uint64_t* aux) {
+void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const ColRef& key, int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* aux) {
   if (nrows <= 0) return;
   const int64_t ntiles = (nrows + kTile - 1) / kTile;
-  hipLaunchKernelGGL(k_unique_mark, dim3(grid_tiles(ntiles)), dim3(kBlock), 0, s, bitmap, tile_counts, col, dtype, missing, nrows, ntiles, ent, mask, aux);
+  hipLaunchKernelGGL(k_unique_mark, dim3(grid_tiles(ntiles)), dim3(kBlock), 0, s, bitmap, tile_counts, key.data, (int)key.dtype, key.missing, nrows, ntiles, ent, mask, aux);
 }
 void launch_unique_migrate(hipStream_t s, const UniqueEntry* from, const uint64_t* from_off, const uint32_t* from_len, uint64_t from_cap, UniqueEntry* ent,
                            uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, uint64_t* aux) {
@@ -584,16 +583,22 @@ void launch_unique_migrate(hipStream_t s, const UniqueEntry* from, const uint64_
 void launch_unique_scatter(hipStream_t s, const UniqueEntry* ent, uint64_t cap, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts) {
   hipLaunchKernelGGL(k_unique_scatter, dim3(grid_rows((int64_t)cap + 2)), dim3(kBlock), 0, s, ent, cap, aux, bitmap, tile_counts);
 }
-void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile_counts, const int32_t* sizes, const int64_t* tile_off,
-                       const uint8_t* bytes, int64_t nrows, int64_t tile0, int64_t tile1, UniqueEntry* ent, uint64_t* rep_off, uint32_t* rep_len, uint64_t mask,
-                       uint64_t* aux, uint64_t salt) {
+// the String passes' arguments: the key column and its table
+static StrPassArgs str_pass_args(const uint64_t* sel, const StrSide& key, int64_t nrows, int64_t tile0, int64_t tile1, const StrTable& tab) {
+  StrPassArgs A{};
+  A.sel = sel; A.sizes = key.sizes; A.tile_off = key.tile_off; A.bytes = key.bytes; A.nrows = nrows; A.tile0 = tile0; A.tile1 = tile1;
+  A.ent = tab.ent; A.rep_off = tab.rep_off; A.rep_len = tab.rep_len; A.mask = tab.mask; A.aux = tab.aux; A.salt = tab.salt;
+  return A;
+}
+void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile_counts, const StrSide& key, int64_t nrows, int64_t tile0, int64_t tile1, const StrTable& tab) {
   if (tile1 <= tile0) return;
   const dim3 b(kBlock);
-  if (pass == 2) { hipLaunchKernelGGL(k_unique_str_mark, dim3(grid_tiles(tile1 - tile0)), b, 0, s, bitmap, tile_counts, sizes, tile_off, bytes, nrows, tile1, ent, mask, aux, salt); return; }
+  if (pass == 2) {
+    hipLaunchKernelGGL(k_unique_str_mark, dim3(grid_tiles(tile1 - tile0)), b, 0, s, bitmap, tile_counts, key.sizes, key.tile_off, key.bytes, nrows, tile1, tab.ent, tab.mask, tab.aux, tab.salt);
+    return;
+  }
   const dim3 g(grid_str_pass(tile1 - tile0));
-  StrPassArgs A{};
-  A.sel = bitmap; A.sizes = sizes; A.tile_off = tile_off; A.bytes = bytes; A.nrows = nrows; A.tile0 = tile0; A.tile1 = tile1;
-  A.ent = ent; A.rep_off = rep_off; A.rep_len = rep_len; A.mask = mask; A.aux = aux; A.salt = salt;
+  StrPassArgs A = str_pass_args(bitmap, key, nrows, tile0, tile1, tab);
   A.maybe = pass == 3 ? 1 : 0;
   if (pass == 0) hipLaunchKernelGGL((k_str_pass<0, 0, 0, false>), g, b, 0, s, A);
   else hipLaunchKernelGGL((k_str_pass<1, 0, 0, false>), g, b, 0, s, A);
@@ -625,14 +630,6 @@ __global__ __launch_bounds__(kBlock) void k_group_ids(UniqueEntry* __restrict__ 
 // dictionary codes' rank table, 2: out of the dense form's table.  NG = how many groups the workgroup's own accumulators hold: 1024 (16 KB of LDS, 256 threads, several
 // workgroups per CU), 9216 (144 KB, one 1024-thread workgroup per CU: round 4 — 1e9 rows in 5 000 groups were 2e9 global atomics, 85 ms), 0 = global atomics
 constexpr int kGroupLdsBig = 9216;
-struct AccArgs {
-  const uint64_t* sel; const void* keycol; int keydt; const uint64_t* missing; const void* valcol; int valdt, op; int64_t nrows;
-  const UniqueEntry* ent; uint64_t mask; const uint64_t* special;       // SRC 0 (special: aux — the groups of the unstorable key and of missing)
-  const uint16_t* codes; const uint32_t* rank_of_code;                  // SRC 1
-  uint64_t lo; const uint64_t* gids;                                    // SRC 2 (special[1]: the group of missing)
-  uint64_t* cnt; uint64_t* val; int ngroups; uint64_t val_init;
-  uint64_t* unknown_flag;                                               // k_group_acc_dense_lds: raised by a selected row whose key has no group (an optimistic, head-only table)
-};
 // OPK: group_add_t's operator; W8: the value column AND (SRC 0 / 2) the key column are 8-byte integers or doubles, loaded as they are — the dtype switches of value_bits
 // and key_image, copied four times by the unrolled trip, stay in the !W8 kernels
 // NG = 0 (more groups than any LDS holds: every row's value through a global atomic) keeps kHotGroups slots in LDS for HOT groups (round 6): a group that a
@@ -733,28 +730,21 @@ __global__ __launch_bounds__(NG > kGroupLds ? 1024 : kBlock) void k_group_acc(co
     }
   }
 }
+static int acc_opk(const AccArgs& A) { return opk_of(A.op, A.valcol != nullptr, value_kind(A.valdt)); }
 template <int SRC>
 static void launch_group_acc(hipStream_t s, const AccArgs& A) {
   if (A.nrows <= 0) return;
   const int64_t b256 = (A.nrows + kBlock - 1) / kBlock;
-  const int opk = opk_of(A.op, A.valcol != nullptr, value_kind(A.valdt));
-  const bool v8 = opk == 0 || A.valdt == DFDB_I64 || A.valdt == DFDB_U64 || A.valdt == DFDB_F64;
-  const bool k8 = SRC == 1 || A.keydt == DFDB_I64 || A.keydt == DFDB_U64 || A.keydt == DFDB_F64;
+  const int opk = acc_opk(A);
+  const bool k8 = SRC == 1 || dt_is_w8(A.keydt);
   auto go = [&](auto opk_c, auto w8_c) {
     constexpr int OPK = decltype(opk_c)::value; constexpr bool W8 = decltype(w8_c)::value;
     if (A.ngroups <= kGroupLds) hipLaunchKernelGGL((k_group_acc<kGroupLds, SRC, OPK, W8>), dim3((unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, b256))), dim3(kBlock), 0, s, A);
     else if (A.ngroups <= kGroupLdsBig) hipLaunchKernelGGL((k_group_acc<kGroupLdsBig, SRC, OPK, W8>), dim3((unsigned)std::min<int64_t>(256, std::max<int64_t>(1, (A.nrows + 1023) / 1024))), dim3(1024), 0, s, A);
     else hipLaunchKernelGGL((k_group_acc<0, SRC, OPK, W8>), dim3((unsigned)std::min<int64_t>(8192, std::max<int64_t>(1, b256))), dim3(kBlock), 0, s, A);
   };
-  auto by_w = [&](auto opk_c) { go(opk_c, std::true_type{}); };
-  if (!(v8 && k8)) { go(std::integral_constant<int, -1>{}, std::false_type{}); return; }      // narrow keys or values: one kernel per (NG, SRC), operator at run time
-  switch (opk) {
-    case 0: by_w(std::integral_constant<int, 0>{}); break;
-    case 1: by_w(std::integral_constant<int, 1>{}); break;
-    case 2: by_w(std::integral_constant<int, 2>{}); break;
-    case 3: by_w(std::integral_constant<int, 3>{}); break;
-    default: by_w(std::integral_constant<int, 4>{}); break;
-  }
+  if (!(value_is_w8(opk, A.valdt) && k8)) { go(std::integral_constant<int, -1>{}, std::false_type{}); return; }      // narrow keys or values: one kernel per (NG, SRC), operator at run time
+  with_opk(opk, [&](auto opk_c) { go(opk_c, std::true_type{}); });
 }
 
 void launch_group_ids(hipStream_t s, UniqueEntry* ent, uint64_t cap, uint64_t* special, const uint64_t* ubits, const uint64_t* uprefix) {
@@ -829,12 +819,6 @@ __global__ void k_set_rows(const uint64_t* __restrict__ rows, int n, uint64_t* _
 }
 void launch_set_rows(hipStream_t s, const uint64_t* rows, int n, uint64_t* bitmap, uint32_t* tile_counts) {
   if (n > 0) hipLaunchKernelGGL(k_set_rows, dim3((n + 255) / 256), dim3(256), 0, s, rows, n, bitmap, tile_counts);
-}
-void launch_group_accumulate_codes(hipStream_t s, const uint64_t* sel, const uint16_t* codes, const uint32_t* rank_of_code, const void* valcol, int valdt, int op,
-                                   int64_t nrows, uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init) {
-  AccArgs A{};
-  A.sel = sel; A.codes = codes; A.rank_of_code = rank_of_code; A.valcol = valcol; A.valdt = valdt; A.op = op; A.nrows = nrows; A.cnt = cnt; A.val = val; A.ngroups = (int)ngroups; A.val_init = val_init;
-  launch_group_acc<1>(s, A);
 }
 
 // Keys that take the hash table (Float64, wide integers), a few thousand groups: the accumulate pass probed the GLOBAL table per row — a 64-bit mix, a 16-byte read
@@ -944,39 +928,13 @@ static bool try_hash_lds(hipStream_t s, const AccArgs& A, const void* gkeys) {
   hipLaunchKernelGGL((k_group_acc_hash_lds<OPK>), dim3(g), dim3(1024), lds, s, A, gkeys, (uint32_t)slots, ngp);
   return hipGetLastError() == hipSuccess;
 }
-int launch_group_accumulate(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
-                             int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* special, uint64_t* cnt, uint64_t* val,
-                             int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag, const void* gkeys) {
-  AccArgs A{};
-  A.unknown_flag = unknown_flag;                               // the table was filled from a prefix of the rows: a key without a slot raises this word
-  A.sel = sel; A.keycol = keycol; A.keydt = keydt; A.missing = missing; A.valcol = valcol; A.valdt = valdt; A.op = op; A.nrows = nrows; A.ent = ent; A.mask = mask; A.special = special;
-  A.cnt = cnt; A.val = val; A.ngroups = (int)ngroups; A.val_init = val_init;
-  if (gkeys && nrows > 0 && ngroups > 0 && (keydt == DFDB_I64 || keydt == DFDB_U64 || keydt == DFDB_F64)) {      // (1: the form with the groups' keys in an LDS table)
-    const int opk = opk_of(op, valcol != nullptr, value_kind(valdt));
-    const bool v8 = opk == 0 || valdt == DFDB_I64 || valdt == DFDB_U64 || valdt == DFDB_F64;
-    bool done = false;
-    if (v8) switch (opk) {
-      case 0: done = try_hash_lds<0>(s, A, gkeys); break;
-      case 1: done = try_hash_lds<1>(s, A, gkeys); break;
-      case 2: done = try_hash_lds<2>(s, A, gkeys); break;
-      case 3: done = try_hash_lds<3>(s, A, gkeys); break;
-      default: done = try_hash_lds<4>(s, A, gkeys); break;
-    }
-    if (done) return 1;
-  }
-  launch_group_acc<0>(s, A);
-  return 0;
-}
 // String keys: k_str_pass, KIND 2
-void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const void* valcol, int valdt,
-                                 int op, int64_t nrows, const UniqueEntry* ent, const uint64_t* rep_off, const uint32_t* rep_len, uint64_t mask, uint64_t* special, uint64_t salt,
-                                 uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init) {
-  if (nrows <= 0) return;
-  const int64_t ntiles = (nrows + kTile - 1) / kTile;
-  StrPassArgs A{};
-  A.sel = sel; A.sizes = sizes; A.tile_off = tile_off; A.bytes = bytes; A.nrows = nrows; A.tile0 = 0; A.tile1 = ntiles;
-  A.ent = const_cast<UniqueEntry*>(ent); A.rep_off = const_cast<uint64_t*>(rep_off); A.rep_len = const_cast<uint32_t*>(rep_len); A.mask = mask; A.aux = special; A.salt = salt;
-  A.valcol = valcol; A.valdt = valdt; A.op = op; A.cnt = cnt; A.val = val; A.ngroups = (int)ngroups; A.val_init = val_init;
+void launch_group_accumulate_str(hipStream_t s, const AccArgs& G, const StrSide& key, const StrTable& tab) {
+  if (G.nrows <= 0) return;
+  const int64_t ntiles = (G.nrows + kTile - 1) / kTile;
+  StrPassArgs A = str_pass_args(G.sel, key, G.nrows, 0, ntiles, tab);
+  A.valcol = G.valcol; A.valdt = G.valdt; A.op = G.op; A.cnt = G.cnt; A.val = G.val; A.ngroups = G.ngroups; A.val_init = G.val_init;
+  const int ngroups = G.ngroups, valdt = G.valdt;
   // the LDS forms run ONE round of workgroups: as many as are resident at once (a workgroup's met caches warm up on its first tiles and its accumulators are
   // flushed once, and 2048 workgroups over 768 resident places left a third of the chip idle in the last round)
   auto one_round = [&](const void* fn) {
@@ -986,10 +944,10 @@ void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32
     int g = per_cu * cus;
     return (int)std::min<int64_t>(g, std::max<int64_t>(1, (ntiles + kWavesPerBlock - 1) / kWavesPerBlock));
   };
-  const int opk = opk_of(op, valcol != nullptr, value_kind(valdt));
+  const int opk = acc_opk(G);
   auto go = [&](auto ngl, auto opk_c) {
     constexpr int NGL = decltype(ngl)::value, OPK = decltype(opk_c)::value;
-    if (OPK != 0 && (valdt == DFDB_I64 || valdt == DFDB_U64 || valdt == DFDB_F64)) {
+    if (OPK != 0 && dt_is_w8(valdt)) {
       const int g = NGL ? one_round((const void*)k_str_pass<2, NGL, OPK, true>) : grid_str_pass(ntiles);
       hipLaunchKernelGGL((k_str_pass<2, NGL, OPK, true>), dim3(g), dim3(kBlock), 0, s, A);
     } else {
@@ -997,15 +955,7 @@ void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32
       hipLaunchKernelGGL((k_str_pass<2, NGL, OPK, false>), dim3(g), dim3(kBlock), 0, s, A);
     }
   };
-  auto by_op = [&](auto ngl) {
-    switch (opk) {
-      case 0: go(ngl, std::integral_constant<int, 0>{}); break;
-      case 1: go(ngl, std::integral_constant<int, 1>{}); break;
-      case 2: go(ngl, std::integral_constant<int, 2>{}); break;
-      case 3: go(ngl, std::integral_constant<int, 3>{}); break;
-      default: go(ngl, std::integral_constant<int, 4>{}); break;
-    }
-  };
+  auto by_op = [&](auto ngl) { with_opk(opk, [&](auto opk_c) { go(ngl, opk_c); }); };
   if (ngroups <= 64) by_op(std::integral_constant<int, 64>{});
   else if (ngroups <= kGroupLds) by_op(std::integral_constant<int, kGroupLds>{});
   else by_op(std::integral_constant<int, 0>{});
@@ -1196,40 +1146,37 @@ __global__ __launch_bounds__(kBlock) void k_dense_group_ids(uint64_t* __restrict
   else if (i == range && aux[kAuxMissing] != kEmpty) aux[kAuxMissing] = rank_of_row(ubits, uprefix, aux[kAuxMissing]);
 }
 
-#define DENSE_BY_DTYPE(CALL)                                                       \
-  switch (dtype) {                                                                 \
-    case DFDB_I8:  { using T = int8_t;   CALL; } break;                            \
-    case DFDB_I16: { using T = int16_t;  CALL; } break;                            \
-    case DFDB_I32: { using T = int32_t;  CALL; } break;                            \
-    case DFDB_I64: { using T = int64_t;  CALL; } break;                            \
-    case DFDB_U8: case DFDB_BOOL: { using T = uint8_t; CALL; } break;              \
-    case DFDB_U16: { using T = uint16_t; CALL; } break;                            \
-    case DFDB_U32: { using T = uint32_t; CALL; } break;                            \
-    default:       { using T = uint64_t; CALL; } break;                            \
-  }
-void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int64_t tile_step, uint64_t* aux) {
+void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, int64_t tile_step, uint64_t* aux) {
   if (nrows <= 0) return;
   const int64_t ntiles = (nrows + kTile - 1) / kTile, visited = (ntiles + tile_step - 1) / tile_step;
   const dim3 g(grid_tiles(visited) > 2048 ? 2048 : grid_tiles(visited)), b(kBlock);
-  DENSE_BY_DTYPE(hipLaunchKernelGGL((k_dense_minmax<T>), g, b, 0, s, bitmap, (const T*)col, missing, nrows, ntiles, tile_step, aux))
+  with_dtype<DtDenseKeys>(key.dtype, [&](auto c) {
+    using T = typename decltype(c)::type;
+    hipLaunchKernelGGL((k_dense_minmax<T>), g, b, 0, s, bitmap, (const T*)key.data, key.missing, nrows, ntiles, tile_step, aux);
+  });
 }
-void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t nrows, uint64_t lo, uint32_t range,
-                           uint32_t* present, uint64_t* aux) {
+void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, uint64_t lo, uint32_t range, uint32_t* present, uint64_t* aux) {
   if (nrows <= 0) return;
   const int64_t ntiles = (nrows + kTile - 1) / kTile;
   int64_t nb = (ntiles + kDenseBlock / 64 - 1) / (kDenseBlock / 64); if (nb > 256) nb = 256;      // one workgroup per CU: its LDS is the whole CU's
   const dim3 g((unsigned)nb), b(kDenseBlock);
-  DENSE_BY_DTYPE(hipLaunchKernelGGL((k_dense_presence<T>), g, b, 0, s, bitmap, (const T*)col, missing, nrows, ntiles, lo, range, present, aux))
+  with_dtype<DtDenseKeys>(key.dtype, [&](auto c) {
+    using T = typename decltype(c)::type;
+    hipLaunchKernelGGL((k_dense_presence<T>), g, b, 0, s, bitmap, (const T*)key.data, key.missing, nrows, ntiles, lo, range, present, aux);
+  });
   const int words = (int)((range + 31u) >> 5);
   hipLaunchKernelGGL(k_dense_count, dim3((words + kBlock - 1) / kBlock > 64 ? 64 : (words + kBlock - 1) / kBlock), dim3(kBlock), 0, s, present, words, aux);
 }
-void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t row0, int64_t row1, uint64_t lo,
-                        uint32_t range, uint64_t distinct, uint64_t* first, uint64_t* aux) {
+void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, uint64_t lo, uint32_t range, uint64_t distinct,
+                        uint64_t* first, uint64_t* aux) {
   if (row1 <= row0) return;
   const int64_t tile0 = row0 / kTile, tile1 = (row1 + kTile - 1) / kTile;
   const dim3 g(grid_tiles(tile1 - tile0) > 2048 ? 2048 : grid_tiles(tile1 - tile0)), b(kBlock);
   hipLaunchKernelGGL(k_dense_snap, dim3(1), dim3(1), 0, s, aux);      // what the launches before this one have found: the only count this launch may stop on
-  DENSE_BY_DTYPE(hipLaunchKernelGGL((k_dense_first<T>), g, b, 0, s, bitmap, (const T*)col, missing, row1, tile0, tile1, lo, range, distinct, first, aux))
+  with_dtype<DtDenseKeys>(key.dtype, [&](auto c) {
+    using T = typename decltype(c)::type;
+    hipLaunchKernelGGL((k_dense_first<T>), g, b, 0, s, bitmap, (const T*)key.data, key.missing, row1, tile0, tile1, lo, range, distinct, first, aux);
+  });
 }
 void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts) {
   hipLaunchKernelGGL(k_dense_scatter, dim3((range + 1 + kBlock) / kBlock), dim3(kBlock), 0, s, first, range, aux, bitmap, tile_counts);
@@ -1296,33 +1243,25 @@ static bool try_dense_lds(hipStream_t s, const AccArgs& A, uint32_t range) {
   hipLaunchKernelGGL((k_group_acc_dense_lds<OPK>), dim3(g), dim3(1024), lds, s, A, range, ngp);
   return hipGetLastError() == hipSuccess;
 }
-int launch_group_accumulate_dense(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
-                                   int64_t nrows, uint64_t lo, uint32_t range, uint64_t span_lo, uint64_t span_hi, const uint64_t* gids, const uint64_t* aux, uint64_t* cnt, uint64_t* val,
-                                   int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag) {
-  // unknown_flag != nullptr: the table was made from the head of the column only — the pass must be the LDS form, which reports a key without a group; returns -1,
-  // nothing launched, when that form cannot take the job (the caller then makes the table from every row)
-  AccArgs A{};
-  A.unknown_flag = unknown_flag;
-  A.sel = sel; A.keycol = keycol; A.keydt = keydt; A.missing = missing; A.valcol = valcol; A.valdt = valdt; A.op = op; A.nrows = nrows; A.lo = lo; A.gids = gids; A.special = aux;
-  A.cnt = cnt; A.val = val; A.ngroups = (int)ngroups; A.val_init = val_init;
-  if (nrows > 0 && (ngroups > kGroupLds || unknown_flag) && (keydt == DFDB_I64 || keydt == DFDB_U64) && span_lo <= span_hi && span_hi < range) {   // (few groups: the 256-thread kernels, several workgroups per CU)
+// the single-reducer accumulate pass (kernels.hpp): the form with the groups' table in LDS where it can take the job, else k_group_acc
+int launch_group_accumulate(hipStream_t s, GroupSrc src, const AccArgs& A, const GroupAccExtra& X) {
+  const int opk = acc_opk(A);
+  if (src == GROUP_SRC_CODES) { launch_group_acc<1>(s, A); return 0; }
+  if (src == GROUP_SRC_HASH) {
+    if (X.gkeys && A.nrows > 0 && A.ngroups > 0 && dt_is_w8(A.keydt) && value_is_w8(opk, A.valdt) &&      // (1: the form with the groups' keys in an LDS table)
+        with_opk(opk, [&](auto opk_c) { return try_hash_lds<decltype(opk_c)::value>(s, A, X.gkeys); })) return 1;
+    launch_group_acc<0>(s, A);
+    return 0;
+  }
+  // the dense table.  A.unknown_flag: the table was made from the head of the column only — the pass must be the LDS form, which reports a key without a group
+  if (A.nrows > 0 && (A.ngroups > kGroupLds || A.unknown_flag) && (A.keydt == DFDB_I64 || A.keydt == DFDB_U64) && X.span_lo <= X.span_hi && X.span_hi < X.range) {   // (few groups: the 256-thread kernels, several workgroups per CU)
     // the table is laid out for the widest span the form can hold; the keys that are there cover [span_lo, span_hi] of it (k_dense_count) and only that goes to LDS
     AccArgs B = A;
-    B.lo = lo + span_lo; B.gids = gids + span_lo;
-    const uint32_t brange = (uint32_t)(span_hi - span_lo + 1);
-    const int opk = opk_of(op, valcol != nullptr, value_kind(valdt));
-    const bool v8 = opk == 0 || valdt == DFDB_I64 || valdt == DFDB_U64 || valdt == DFDB_F64;
-    bool done = false;
-    if (v8) switch (opk) {
-      case 0: done = try_dense_lds<0>(s, B, brange); break;
-      case 1: done = try_dense_lds<1>(s, B, brange); break;
-      case 2: done = try_dense_lds<2>(s, B, brange); break;
-      case 3: done = try_dense_lds<3>(s, B, brange); break;
-      default: done = try_dense_lds<4>(s, B, brange); break;
-    }
-    if (done) return 1;                                        // (1: the form with the group table in LDS)
+    B.lo = A.lo + X.span_lo; B.gids = A.gids + X.span_lo;
+    const uint32_t brange = (uint32_t)(X.span_hi - X.span_lo + 1);
+    if (value_is_w8(opk, A.valdt) && with_opk(opk, [&](auto opk_c) { return try_dense_lds<decltype(opk_c)::value>(s, B, brange); })) return 1;
   }
-  if (unknown_flag) return -1;
+  if (A.unknown_flag) return -1;
   launch_group_acc<2>(s, A);
   return 0;
 }
@@ -1426,11 +1365,11 @@ bool launch_group_rank(hipStream_t s, int src, const RankArgs& A) {
   else hipLaunchKernelGGL(k_group_rank<0>, g, b, 0, s, A);
   return hipGetLastError() == hipSuccess;
 }
-bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, uint64_t salt) {
+bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const StrSide& key, uint64_t salt) {
   if (A.nrows <= 0) return true;
   (void)hipGetLastError();
   const int64_t nt = (A.nrows + kTile - 1) / kTile;
-  hipLaunchKernelGGL(k_group_rank_str, dim3(grid_tiles(nt)), dim3(kBlock), 0, s, A, sizes, tile_off, bytes, salt, nt);
+  hipLaunchKernelGGL(k_group_rank_str, dim3(grid_tiles(nt)), dim3(kBlock), 0, s, A, key.sizes, key.tile_off, key.bytes, salt, nt);
   return hipGetLastError() == hipSuccess;
 }
 

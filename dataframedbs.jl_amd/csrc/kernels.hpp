@@ -17,6 +17,11 @@ inline bool allow_dynamic_lds(const void* kernel, size_t bytes) {
   return false;
 }
 
+// ---- how a column reaches a launcher.  A fixed-width column is a ColRef (engine.hpp: col_ref), a flat String column a StrSide (below; engine.hpp: str_side);
+// what a kernel family needs beyond the columns travels in that family's argument record (AccArgs, RankArgs, MultiAccArgs, StrTable, RadixGroup ...), filled by
+// the caller with named fields.  A value-initialised ColRef is "no column": the count-only reducer
+struct ColRef { const void* data; int32_t dtype; const uint64_t* missing; };   // dtype: the base dtype; missing: the column's missing bitmap, null = not nullable
+
 enum CmpOp : int { CMP_EQ = 0, CMP_NE = 1, CMP_LT = 2, CMP_LE = 3, CMP_GT = 4, CMP_GE = 5 };
 
 // one simple term `col OP const` of a conjunction/disjunction (K1 multi-column form).  op2 >= 0: the term is the INTERVAL
@@ -44,9 +49,8 @@ struct ScanTerms {
 };
 
 // ---- K1: predicate scan -> bitmap (+ per-1024-row tile counts) ----------------------------------
-// single column `x OP c`; and_existing: bitmap &= result (a predicate stage after a range stage)
-void launch_scan_cmp(hipStream_t s, const void* col, int32_t dtype, int op, uint64_t cbits, uint64_t* bitmap,
-                     uint32_t* tile_counts, int64_t nrows, bool and_existing, bool nt = true, void* cap = nullptr,
+// single column `x OP c` (term: its col, dtype, op and cbits; no second comparison, no transform); and_existing: bitmap &= result (a predicate stage after a range stage)
+void launch_scan_cmp(hipStream_t s, const ScanTerm& term, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing, bool nt = true, void* cap = nullptr,
                      int wt_store = 3 /* bit 0: the bitmap leaves with write-through stores (ctx option "scan_wt_store"); bits 1-2: ctx option "scan_narrow" — which
                                          narrow columns take k_scan_cmp_narrow (16 bytes per lane): 1 = 1-byte (default), 2 = 1-, 2- and 4-byte, 0 = none */);
 // K1's read stream alone (k_read_probe): an 8-byte column of nrows rows, nothing written (sink: one device word that is never stored to)
@@ -117,7 +121,7 @@ struct StrSide { const int32_t* sizes; const int64_t* tile_off; const uint8_t* b
 // per-1024-row byte totals of max(size,0)  (first half of unsafe_remake_offsets!)
 void launch_str_tile_bytes(hipStream_t s, const int32_t* sizes, uint32_t* tile_bytes, int64_t nrows, uint32_t* max_tile_bytes = nullptr);   // (max: one zeroed device word)
 // K5: s OP "const" (EQ / NE / STARTSWITH / ENDSWITH) -> bitmap + counts.  mode: 0 EQ, 1 NE, 2 STARTSWITH, 3 ENDSWITH
-// pat_host: the pattern in host memory (<= 64 bytes travel as kernel arguments); pat_dev: device copy for longer ones
+// StrPattern: host — the pattern in host memory (<= 64 bytes travel as kernel arguments); dev — device copy for longer ones
 struct StrCapture { int32_t* sizes; uint8_t* bytes; uint32_t* tile_bytes; };   // K5 CAP outputs (see k_str_match_short)
 // the form launch_str_match takes: patterns above 64 bytes run k_str_match; shorter ones k_str_match_short, staged through LDS when every tile of the column
 // fits the 8 KB a wave stages (+ 15 bytes below the tile's first, + 16 behind its last), with direct probes otherwise (and for the empty pattern, which reads nothing)
@@ -127,9 +131,9 @@ inline StrMatchForm str_match_form(int32_t patlen, uint32_t max_tile_bytes) {
   if (patlen > 64) return STR_MATCH_LONG;
   return patlen > 0 && max_tile_bytes > 0 && max_tile_bytes + 48u <= kStrStageBytes ? STR_MATCH_STAGED : STR_MATCH_DIRECT;
 }
-void launch_str_match(hipStream_t s, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const uint8_t* pat_host,
-                      const uint8_t* pat_dev, int32_t patlen, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
-                      bool and_existing, const StrCapture* cap = nullptr, uint32_t max_tile_bytes = 0);   // max_tile_bytes: Column::max_tile_bytes (0 = not known: probes straight from memory)
+struct StrPattern { const uint8_t* host; const uint8_t* dev; int32_t len; };
+void launch_str_match(hipStream_t s, const StrSide& a, const StrPattern& pat, int mode, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing,
+                      const StrCapture* cap = nullptr, uint32_t max_tile_bytes = 0);   // max_tile_bytes: Column::max_tile_bytes (0 = not known: probes straight from memory)
 // K5b: s1 OP s2 (CmpOp) over two String columns -> bitmap + counts; a row with a missing side (size -1) selects nothing
 void launch_str_pair(hipStream_t s, const StrSide& a, const StrSide& b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
 void launch_str_compact_captured(hipStream_t s, const StrCapture& cap, const uint64_t* prefix, const int64_t* tile_off, const uint64_t* out_tile_off,
@@ -155,14 +159,13 @@ struct DictMiss {                                                     // rows wh
   int64_t max_records, bytes_cap; int32_t max_len;
 };
 uint64_t dict_hash_host(uint64_t key8, uint32_t len);
-void launch_dict_encode(hipStream_t s, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const DictSlot* slots, uint32_t nslots,
-                        const uint8_t* dict_bytes, uint16_t* codes, int64_t nrows, const DictMiss& miss);
+void launch_dict_encode(hipStream_t s, const StrSide& a, const DictSlot* slots, uint32_t nslots, const uint8_t* dict_bytes, uint16_t* codes, int64_t nrows, const DictMiss& miss);
 // lut: one bit per code, 1 = the row is selected; lut_words = ceil(entries / 32) <= 2048
 void launch_dict_scan(hipStream_t s, const uint16_t* codes, const uint32_t* lut, int32_t lut_words, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows,
                       bool and_existing);
-// two dictionary columns compared: rank_a / rank_b give every code its rank in the bytewise sorted union of the two dictionaries (equal strings, equal rank)
-void launch_dict_pair(hipStream_t s, const uint16_t* codes_a, const uint16_t* codes_b, const uint32_t* rank_a, int32_t n_a, const uint32_t* rank_b, int32_t n_b, int op,
-                      uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
+// two dictionary columns compared: each side's rank gives every one of its n codes its rank in the bytewise sorted union of the two dictionaries (equal strings, equal rank)
+struct DictSide { const uint16_t* codes; const uint32_t* rank; int32_t n; };
+void launch_dict_pair(hipStream_t s, const DictSide& a, const DictSide& b, int op, uint64_t* bitmap, uint32_t* tile_counts, int64_t nrows, bool and_existing);
 // the projection of a dictionary column over n selected rows whose codes K3 has compacted: sizes + per-1024-output-row byte totals, then the bytes
 void launch_dict_expand_sizes(hipStream_t s, const uint16_t* codes, int64_t n, const int32_t* dict_len, int32_t* out_sizes, uint32_t* out_tile_bytes);
 void launch_dict_expand_bytes(hipStream_t s, const uint16_t* codes, int64_t n, const int32_t* dict_len, const uint32_t* dict_off, const uint8_t* dict_bytes,
@@ -177,28 +180,26 @@ size_t reduce_scratch_bytes();
 // ---- K11: order statistics by radix select (k_select.hip) -------------------------------------------
 // One pass: per group g < ngroups, the histogram of key bits [shift, shift + 8) over the selected, non-missing rows whose key bits above them equal
 // prefix[g] (distinct prefixes), added to hist[g * 256 + digit]; first: also the counts {not missing, missing, NaN} of the selected rows, added to
-// counts[0 .. 3).  Both are 64-bit counters the caller zeroes; ngroups = 0 with first counts only.  missing: the column's bitmap or null.
+// counts[0 .. 3).  Both are 64-bit counters the caller zeroes; ngroups = 0 with first counts only.
 // full: the key is the 64-bit order image (select_key_bits = 64) instead of the same order in the column's own width.
 constexpr int kSelectMaxRanks = 16;
 struct SelectPass { uint64_t prefix[kSelectMaxRanks]; int32_t ngroups; int32_t shift; int32_t first; };
-void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const uint64_t* missing, const void* col, int32_t dtype, bool full,
+void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const ColRef& col, bool full,
                         int64_t nrows, const SelectPass& P, uint64_t* hist /* [kSelectMaxRanks * 256] */, uint64_t* counts /* [3] */);
 int select_key_bits(int dtype, bool full);
 uint64_t select_key_value(int dtype, bool full, uint64_t key);      // a finished key -> the value's 64 accumulator bits (integers widened, floats as Float64)
 
 // ---- unique(col) as a selection of first occurrences (k_unique.hip: hash table of {key, smallest row}; k_unique_dense.hip: integer keys of a small range)
 struct UniqueEntry { uint64_t key, row; };
-void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t row0, int64_t row1,
-                          UniqueEntry* ent, uint64_t mask, uint64_t* aux);
-void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const void* col, int dtype, const uint64_t* missing, int64_t nrows,
-                        const UniqueEntry* ent, uint64_t mask, const uint64_t* aux);
+void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, UniqueEntry* ent, uint64_t mask, uint64_t* aux);
+void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const ColRef& key, int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* aux);
 void launch_unique_migrate(hipStream_t s, const UniqueEntry* from, const uint64_t* from_off, const uint32_t* from_len, uint64_t from_cap, UniqueEntry* ent,
                            uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, uint64_t* aux);
 void launch_unique_scatter(hipStream_t s, const UniqueEntry* ent, uint64_t cap, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts);
-// pass 0: insert the tiles [tile0, tile1), 1: verify, 2: mark
-void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile_counts, const int32_t* sizes, const int64_t* tile_off,
-                       const uint8_t* bytes, int64_t nrows, int64_t tile0, int64_t tile1, UniqueEntry* ent, uint64_t* rep_off, uint32_t* rep_len, uint64_t mask,
-                       uint64_t* aux, uint64_t salt);
+// the hash table of a flat String key: a slot's key is the salted hash of the string, rep_off / rep_len say where one holder's bytes lie (the representative)
+struct StrTable { UniqueEntry* ent; uint64_t* rep_off; uint32_t* rep_len; uint64_t mask; uint64_t* aux; uint64_t salt; };
+// pass 0: insert the tiles [tile0, tile1), 1: verify (3: the table may not hold every string), 2: mark
+void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile_counts, const StrSide& key, int64_t nrows, int64_t tile0, int64_t tile1, const StrTable& tab);
 // dense form.  aux words: 1 = smallest missing row, 5 = a key outside [lo, lo + range) was met, 6 = distinct keys, 7 = keys whose first row is known, 8 / 9 = min / max image
 // radix-partitioned form of the hash-table unique (k_radix.hip): partition into a pool of pages -> one LDS table per partition.  false: the launch is
 // not possible or refused (LDS attribute refused, too many partition bits, a launch error): the caller stays with the hash table.  The pool: `front` [2^kbits x radix_share()] running
@@ -206,21 +207,20 @@ void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile
 // counter (zero), `dump_page` the page nobody owns (radix_pool_pages() - 1); the records' buffer holds radix_pool_record_bytes().
 struct RadixPool { uint32_t* front; uint32_t* pt; uint32_t* next_page; uint32_t maxv; uint32_t dump_page;
                    uint64_t* hot /* [hot_cap x 3]: the hot keys' list {key, value, rows << 32 | first row}: chunks x radix_hot_slots() entries */; uint32_t* hot_n /* zero before */; uint32_t hot_cap; };
+struct RadixGrid { int kbits; int chunks; };      // 2^kbits partitions; `chunks` workgroups share the rows (a multiple of radix_share())
 int64_t radix_rows_per_chunk(int64_t nrows, int chunks);
 int radix_share();
 int64_t radix_pool_pages(int64_t cnt, int kbits);
 int64_t radix_pool_record_bytes(int64_t cnt, int kbits, bool with_values);
 int radix_group_slots();
 uint32_t radix_pool_maxv(int64_t cnt, int kbits);
-bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int kbits, int chunks, int step,
-                         uint32_t* counts /* [2^kbits], zero before */);
-// groupreduce by radix: the records carry the row's 8-byte value (valcol; null: count only); gop 0 count only, 1 wrapping integer sum, 2 double sum, 3 min, 4 max
+bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, int step, uint32_t* counts /* [2^kbits], zero before */);
+// groupreduce by radix: the records carry the row's 8-byte value (val; no column: count only); gop 0 count only, 1 wrapping integer sum, 2 double sum, 3 min, 4 max
 // (of order images: vkind 0 signed, 1 unsigned, 2 double); results [<= groups] {first row, rows, value} + their count nres; gspec {rows, value} of the unstorable key
 // and of the missing key (their first rows: aux[0], aux[1])
-struct RadixGroup { const void* valcol; int valdt; int gop; int vkind; void* results; uint32_t* nres; uint64_t* gspec /* [4]: the unstorable key's, the missing key's */; };
+struct RadixGroup { ColRef val; int gop; int vkind; void* results; uint32_t* nres; uint64_t* gspec /* [4]: the unstorable key's, the missing key's */; };
 int radix_hot_slots();
-bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int kbits, int chunks,
-                            const RadixPool& pool, uint32_t* recs_out /* 12 bytes per record: key image, row; with a group: 20, + the value */, uint64_t* aux,
+bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, const RadixPool& pool, uint32_t* recs_out /* 12 bytes per record: key image, row; with a group: 20, + the value */, uint64_t* aux,
                             const RadixGroup* group = nullptr, bool hot = false /* the kernels that keep hot keys out of the records (values narrower than 8 bytes: always) */);
 bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux,
                         const RadixGroup& group, int cus);
@@ -228,27 +228,38 @@ void launch_radix_group_finish(hipStream_t s, const RadixGroup& group, const uin
 bool launch_radix_unique(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux, int cus);
 int64_t unique_dense_max_range();
 bool unique_dense_dtype(int dtype);
-void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t nrows, int64_t tile_step, uint64_t* aux);
-void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t nrows, uint64_t lo, uint32_t range,
+void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, int64_t tile_step, uint64_t* aux);
+void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, uint64_t lo, uint32_t range,
                            uint32_t* present, uint64_t* aux);
-void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const void* col, int dtype, const uint64_t* missing, int64_t row0, int64_t row1, uint64_t lo,
+void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, uint64_t lo,
                         uint32_t range, uint64_t distinct, uint64_t* first, uint64_t* aux);
 void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts);
 void launch_dense_group_ids(hipStream_t s, uint64_t* first, uint32_t range, uint64_t* aux, const uint64_t* ubits, const uint64_t* uprefix);
-int launch_group_accumulate_dense(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
-                                   int64_t nrows, uint64_t lo, uint32_t range, uint64_t span_lo, uint64_t span_hi, const uint64_t* gids, const uint64_t* aux, uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag = nullptr);
 // K9 (dictionary codes) and groupreduce's group numbers, accumulate passes and finish (k_unique.hip)
 void launch_dict_first_rows(hipStream_t s, const uint64_t* sel, const uint16_t* codes, int64_t nrows, uint64_t* first, int dict_n, int64_t tile0, int64_t tile1);
 void launch_set_rows(hipStream_t s, const uint64_t* rows, int n, uint64_t* bitmap, uint32_t* tile_counts);
-void launch_group_accumulate_codes(hipStream_t s, const uint64_t* sel, const uint16_t* codes, const uint32_t* rank_of_code, const void* valcol, int valdt, int op,
-                                   int64_t nrows, uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
 void launch_group_ids(hipStream_t s, UniqueEntry* ent, uint64_t cap, uint64_t* special, const uint64_t* ubits, const uint64_t* uprefix);
-int launch_group_accumulate(hipStream_t s, const uint64_t* sel, const void* keycol, int keydt, const uint64_t* missing, const void* valcol, int valdt, int op,
-                            int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* special, uint64_t* cnt, uint64_t* val,
-                            int64_t ngroups, uint64_t val_init, uint64_t* unknown_flag = nullptr, const void* gkeys = nullptr);
-void launch_group_accumulate_str(hipStream_t s, const uint64_t* sel, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, const void* valcol, int valdt,
-                                 int op, int64_t nrows, const UniqueEntry* ent, const uint64_t* rep_off, const uint32_t* rep_len, uint64_t mask, uint64_t* special, uint64_t salt,
-                                 uint64_t* cnt, uint64_t* val, int64_t ngroups, uint64_t val_init);
+// groupreduce's single-reducer accumulate pass: every selected row's value to the accumulators of its key's group.  AccArgs is the kernels' argument (its
+// layout is theirs); `src` says which table numbers the groups and which fields beside the common ones are read
+struct AccArgs {
+  const uint64_t* sel; const void* keycol; int keydt; const uint64_t* missing; const void* valcol; int valdt, op; int64_t nrows;
+  const UniqueEntry* ent; uint64_t mask; const uint64_t* special;       // SRC 0 (special: aux — the groups of the unstorable key and of missing)
+  const uint16_t* codes; const uint32_t* rank_of_code;                  // SRC 1
+  uint64_t lo; const uint64_t* gids;                                    // SRC 2 (special[1]: the group of missing)
+  uint64_t* cnt; uint64_t* val; int ngroups; uint64_t val_init;
+  uint64_t* unknown_flag;                                               // the LDS forms: raised by a selected row whose key has no group (an optimistic / head-only table)
+  void key(const ColRef& k) { keycol = k.data; keydt = k.dtype; missing = k.missing; }
+  void value(const ColRef& v) { valcol = v.data; valdt = v.dtype; }
+};
+enum GroupSrc : int { GROUP_SRC_HASH = 0, GROUP_SRC_CODES = 1, GROUP_SRC_DENSE = 2 };
+// what the LDS forms need beside AccArgs.  hash table: gkeys, the groups' 8-byte keys in group order (null: the plain form).  dense table: it spans `range`
+// values from A.lo, of which the keys cover [span_lo, span_hi]
+struct GroupAccExtra { const void* gkeys; uint32_t range; uint64_t span_lo, span_hi; };
+// 1: the form with the groups' table in LDS ran, 0: the plain form, -1: nothing was launched (dense table with A.unknown_flag set — the table was made from
+// the head of the column, only the LDS form reports a key without a group, and it cannot take the job: the caller makes the table from every row)
+int launch_group_accumulate(hipStream_t s, GroupSrc src, const AccArgs& A, const GroupAccExtra& X);
+// flat String keys (k_str_pass): of A the selection, nrows, the value column, op and the outputs are read; the key side is `key` and `tab`
+void launch_group_accumulate_str(hipStream_t s, const AccArgs& A, const StrSide& key, const StrTable& tab);
 void launch_group_finish(hipStream_t s, uint64_t* val, int64_t ng, int kind, int op);
 // groupreduce by a tuple of keys (dfdb_query_groupreduce_n): per selected row of `sel`, the rank of its key out of one of the tables above -> g_out (gprev null)
 // or image = gprev[row] * n + rank -> img_out; a rank >= n raises *flag.  src 0: hash table (special = unique's aux), 1: dictionary codes, 2: the dense form (its table in LDS when the range is small)
@@ -260,7 +271,7 @@ struct RankArgs {
   const uint32_t* gprev; uint64_t n; uint32_t* g_out; uint64_t* img_out; uint64_t* flag;
 };
 bool launch_group_rank(hipStream_t s, int src, const RankArgs& A);
-bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const int32_t* sizes, const int64_t* tile_off, const uint8_t* bytes, uint64_t salt);
+bool launch_group_rank_str(hipStream_t s, const RankArgs& A, const StrSide& key, uint64_t salt);
 // one accumulate pass for up to kMaxReducers reducers over the rows' group numbers: cnt [ngroups], val [nvals][ngroups] (min / max as order images until
 // launch_group_finish); kind: value_kind (value_rules.hpp) of each value column; a group number >= ngroups raises *flag.  1: LDS form, 0: global form, -1: not launched
 constexpr int kMaxReducers = 16;

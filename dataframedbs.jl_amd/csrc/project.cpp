@@ -448,7 +448,7 @@ void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int3
       const size_t used = P.first ? h.size() : (size_t)P.ngroups * 256;
       HIP_CHECK(hipMemsetAsync(hist, 0, used * 8, s));
       { LaunchTimer lt(ctx, "select_hist");
-        launch_select_hist(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), nullable ? col.missing.as<uint64_t>() : nullptr, col.data.p, dt, full, t->nrows, P, hist, dcnt); }
+        launch_select_hist(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col_ref(col), full, t->nrows, P, hist, dcnt); }
       HIP_CHECK(hipMemcpyAsync(h.data(), hist, used * 8, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));            // (`h` is pageable host memory)
       if (P.first) {

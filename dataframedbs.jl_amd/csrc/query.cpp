@@ -286,7 +286,7 @@ static void run_dict_pair(dfdb_query* q, const Column& ca, const Column& cb, int
   HIP_CHECK(hipMemcpyAsync(rb.p, rank.data(), rank.size() * 4, hipMemcpyHostToDevice, s));
   stream_wait(ctx);                                      // `rank` is pageable host memory
   LaunchTimer lt(ctx, "dict_pair");
-  launch_dict_pair(s, ca.dict_codes.as<uint16_t>(), cb.dict_codes.as<uint16_t>(), rb.as<uint32_t>(), (int32_t)na, rb.as<uint32_t>() + na, (int32_t)nb, op,
+  launch_dict_pair(s, DictSide{ca.dict_codes.as<uint16_t>(), rb.as<uint32_t>(), (int32_t)na}, DictSide{cb.dict_codes.as<uint16_t>(), rb.as<uint32_t>() + na, (int32_t)nb}, op,
                    q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), q->t->nrows, have);
 }
 
@@ -533,9 +533,8 @@ static void run_str_step(dfdb_query* q, const StrStep& st, bool have, bool do_ca
     const StrMatchForm form = str_match_form((int32_t)pat.size(), col.max_tile_bytes);
     prof_note(ctx, form == STR_MATCH_STAGED ? "str_match.staged" : form == STR_MATCH_DIRECT ? "str_match.direct" : "str_match.long");
   }
-  launch_str_match(s, col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(), (const uint8_t*)pat.data(),
-                   pb.as<uint8_t>(), (int32_t)pat.size(), st.mode, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), nrows, have,
-                   do_cap ? &capture : nullptr, col.max_tile_bytes);
+  launch_str_match(s, str_side(col), StrPattern{(const uint8_t*)pat.data(), pb.as<uint8_t>(), (int32_t)pat.size()}, st.mode, q->bitmap.as<uint64_t>(),
+                   q->tile_counts.as<uint32_t>(), nrows, have, do_cap ? &capture : nullptr, col.max_tile_bytes);
   if (do_cap) q->left.cap_str_col = st.ord;
 }
 // (after the generic conjuncts like every other string scan: those see every row that reached the stage; a pair launch pins no constant and captures nothing)
@@ -575,7 +574,7 @@ static void place_first_batch(dfdb_query* q, PredPlan& plan) {
   place_mask(q, ord0, [&](uint64_t* bm, int64_t rows, const void* colp) {
     ScanTerms tbx = tb0;                                          // the calibration may be trying another allocation of the first term's column
     for (int k = 0; k < tbx.n; k++) if (tbx.t[k].col == col_before) tbx.t[k].col = colp;
-    if (tbx.n == 1 && tbx.t[0].op2 < 0 && tbx.t[0].pre == 0) launch_scan_cmp(s, tbx.t[0].col, tbx.t[0].dtype, tbx.t[0].op, tbx.t[0].cbits, bm, q->tile_counts.as<uint32_t>(), rows, false, nt, nullptr, wt0);
+    if (tbx.n == 1 && tbx.t[0].op2 < 0 && tbx.t[0].pre == 0) launch_scan_cmp(s, tbx.t[0], bm, q->tile_counts.as<uint32_t>(), rows, false, nt, nullptr, wt0);
     else launch_scan_terms(s, tbx, bm, q->tile_counts.as<uint32_t>(), rows, false, EX_NONE, nullptr, (int)ctx_option(ctx, "scan_pair", 1));
   });
   const void* const col_after = t->cols[(size_t)ord0].data.p;
@@ -623,7 +622,7 @@ static void run_term_batch(dfdb_query* q, const TermBatch& b, int ex, bool have,
   if (one_plain && (ex == EX_NONE || (ex == EX_CAPTURE && !have))) {      // (k_scan_cmp captures over a fresh mask only)
     LaunchTimer lt(ctx, "scan_cmp");
     prof_note(ctx, ctx_option(ctx, "scan_wt_store", 1) ? "scan_cmp.wt_store" : "scan_cmp.plain_store");
-    launch_scan_cmp(s, tb.t[0].col, tb.t[0].dtype, tb.t[0].op, tb.t[0].cbits, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have,
+    launch_scan_cmp(s, tb.t[0], q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have,
                     true, ex == EX_CAPTURE ? q->cap_buf.p : nullptr,
                     (ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0) | (int)((ctx_option(ctx, "scan_narrow", 1) & 3) << 1));
     return;

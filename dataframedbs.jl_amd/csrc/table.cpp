@@ -752,7 +752,7 @@ int64_t table_build_dictionary(dfdb_table* t, int32_t ordinal, int64_t max_entri
     HIP_CHECK(hipStreamSynchronize(s));                               // hs / hb are pageable host memory
     DictMiss miss{(unsigned long long*)mcount.p, (unsigned long long*)mcount.p + 1, moff.as<uint32_t>(), mlen.as<int32_t>(), marena.as<uint8_t>(), kMaxRecords, kArena, kMaxLen};
     { LaunchTimer lt(ctx, "dict_encode");
-      launch_dict_encode(s, c.data.as<int32_t>(), (const int64_t*)c.tile_off.p, c.bytes.as<uint8_t>(), slots.as<DictSlot>(), nslots, dbytes.as<uint8_t>(), codes.as<uint16_t>(), c.nrows, miss); }
+      launch_dict_encode(s, str_side(c), slots.as<DictSlot>(), nslots, dbytes.as<uint8_t>(), codes.as<uint16_t>(), c.nrows, miss); }
     unsigned long long cnt[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(cnt, mcount.p, 16, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));

@@ -32,6 +32,7 @@ struct UniqueTables {
   bool group_probe = false; int64_t group_estimate = 0;
   bool allow_radix = true;       // in: the radix form of unique may take the job (it leaves no table to look keys up in: groupreduce_n's rank pass says no)
 };
+static StrTable str_table(const UniqueTables& T) { return StrTable{T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt}; }
 // K9: unique over a String column that has a dictionary — the first selected row of every code, no hash table.  Leaves what unique_impl leaves (the
 // bitmap holds exactly the first occurrences, prefix scanned); rank_of_code (optional) maps a code to its group number in order of first appearance.
 static int64_t dict_unique(dfdb_query* q, const Column& col, DevBuf* rank_of_code) {
@@ -106,7 +107,7 @@ static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const int dt = dt_base(col.dtype);
   const int64_t limit = std::min<int64_t>(unique_dense_max_range(), ctx_option(ctx, "unique_dense_range", unique_dense_max_range()));
-  const uint64_t* miss = dt_nullable(col.dtype) ? col.missing.as<uint64_t>() : nullptr;
+  const ColRef key = col_ref(col);
   const uint64_t flip = dt_issigned(dt) ? (1ull << 63) : 0ull;
   uint64_t* aux = nullptr;
   uint64_t distinct = 0;
@@ -115,7 +116,7 @@ static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
   auto prows = [&]() -> int64_t { return T.head_only ? head_tiles * kTileRows : t->nrows; };      // the rows the presence pass and the first-row launches walk
   auto minmax = [&](int64_t tile_step, uint64_t* mm) {                 // order-preserving images of the smallest / largest selected key (of every tile_step-th tile)
     unique_reset_aux(ctx, T.aux);
-    { LaunchTimer lt(ctx, "unique_minmax"); launch_dense_minmax(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t->nrows, tile_step, T.aux.as<uint64_t>()); }
+    { LaunchTimer lt(ctx, "unique_minmax"); launch_dense_minmax(s, q->bitmap.as<uint64_t>(), key, t->nrows, tile_step, T.aux.as<uint64_t>()); }
     HIP_CHECK(hipMemcpyAsync(mm, (char*)T.aux.p + 64, 16, hipMemcpyDeviceToHost, s));
     stream_wait(ctx);
   };
@@ -128,7 +129,7 @@ static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
     unique_reset_aux(ctx, T.aux);
     aux = T.aux.as<uint64_t>();
     { LaunchTimer lt(ctx, "unique_presence");
-      launch_dense_presence(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, prows(), T.lo, T.range, T.present.as<uint32_t>(), aux); }
+      launch_dense_presence(s, q->bitmap.as<uint64_t>(), key, prows(), T.lo, T.range, T.present.as<uint32_t>(), aux); }
     uint64_t od[8] = {0, 0, 0, 0, 0, 0, 0, 0};                          // [0] a key outside?  [1] distinct values ... [6], [7] the span of the present values
     HIP_CHECK(hipMemcpyAsync(od, (char*)T.aux.p + 40, 64, hipMemcpyDeviceToHost, s));
     stream_wait(ctx);
@@ -177,7 +178,7 @@ static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
     const int64_t nt_walk = T.head_only ? head_tiles : nt;
     int64_t t0 = 0;
     auto walk = [&](int64_t a, int64_t b) {
-      launch_dense_first(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, a * kTileRows, std::min(prows(), b * kTileRows), T.lo, T.range, distinct, T.first.as<uint64_t>(), aux);
+      launch_dense_first(s, q->bitmap.as<uint64_t>(), key, a * kTileRows, std::min(prows(), b * kTileRows), T.lo, T.range, distinct, T.first.as<uint64_t>(), aux);
     };
     // FEW values: the first 1 M rows in three steps of 16, 112 and 896 tiles — rows that run side by side all see "no first row yet" and all send their atomicMin,
     // and with seven values those are a million atomics on seven words (2.1 ms: `tools/r5_fewgroups.py`); after sixteen tiles every value has its row and the
@@ -244,10 +245,11 @@ struct RadixRun {
   }
   // unique: does some partition hold a large part of all the rows (a value that a third of the column has)?  Every 16th tile is counted (all of them in a small
   // table: 0.1 ms per 1e9 rows) and the counts come back.  1 = skewed, 0 = not, -1 = the sample could not be launched
-  int skewed(const uint64_t* sel, const void* col, int dt, const uint64_t* miss, int64_t nrows, int times) {      // times: "large" = more than this many average partitions
+  RadixGrid grid() const { return RadixGrid{kbits, C}; }
+  int skewed(const uint64_t* sel, const ColRef& key, int64_t nrows, int times) {      // times: "large" = more than this many average partitions
     const int step = radix_rows_per_chunk(nrows, C) / 8192 >= 32 ? 16 : 1;
     { LaunchTimer lt(ctx, "radix_sample");
-      if (!launch_radix_sample(ctx->stream, sel, col, dt, miss, nrows, kbits, C, step, ctl.as<uint32_t>())) return -1; }
+      if (!launch_radix_sample(ctx->stream, sel, key, nrows, grid(), step, ctl.as<uint32_t>())) return -1; }
     std::vector<uint32_t> cn((size_t)P);
     HIP_CHECK(hipMemcpyAsync(cn.data(), ctl.p, (size_t)P * 4, hipMemcpyDeviceToHost, ctx->stream));
     stream_wait(ctx);
@@ -279,24 +281,23 @@ static bool unique_radix(dfdb_query* q, const Column& col, int64_t cnt, UniqueTa
   int kbits = 8;
   while (kbits < 10 && D / (double)(1 << kbits) > 2500.0) kbits++;       // (fewer partitions = longer runs per tile of the partition pass; more = emptier tables in the unique pass: 1e6 values -> 512)
   if (mode < 2 && D / (double)(1 << kbits) > 5500.0) return false;       // the partitions' tables (8192 slots) would overflow
-  const int dt = dt_base(col.dtype);
-  const uint64_t* miss = dt_nullable(col.dtype) ? col.missing.as<uint64_t>() : nullptr;
+  const ColRef key = col_ref(col);
   const int64_t nt = ceil_div(t->nrows, kTileRows);
   const size_t nw = padded_words(t->nrows);
   PooledScratch keep_sel(ctx), keep_tc(ctx);                             // the selection, set aside
   DevBuf &sel_keep = keep_sel.buf, &tc_keep = keep_tc.buf;
   RadixRun run(ctx, kbits);
   if (!run.prepare(cnt, false, 0) || !try_ensure(sel_keep, nw * 8) || !try_ensure(tc_keep, (size_t)nt * 4 + 64)) return false;
-  const RadixPool& pool = run.pool; const int C = run.C;
+  const RadixPool& pool = run.pool;
   DevBuf& recs = ctx->radix_recs;
   // SKEW: one workgroup reduces one partition, so a value that a large part of the rows hold would be one CU's work while 255 wait.  The sample says whether some
   // partition holds more than eight average ones; then the partition kernels that keep hot keys out of the records run (k_radix.hip, hot keys: 1.1 ms slower where
   // nothing is hot, which is why they are not the only ones)
-  const int sk = run.skewed(q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t->nrows, 8);
+  const int sk = run.skewed(q->bitmap.as<uint64_t>(), key, t->nrows, 8);
   if (sk < 0) return false;
   if (sk) prof_note(ctx, "unique_radix.skewed");
   { LaunchTimer lt(ctx, "radix_partition");
-    if (!launch_radix_partition(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t->nrows, kbits, C, pool, recs.as<uint32_t>(), T.aux.as<uint64_t>(), nullptr, sk != 0)) return false; }
+    if (!launch_radix_partition(s, q->bitmap.as<uint64_t>(), key, t->nrows, run.grid(), pool, recs.as<uint32_t>(), T.aux.as<uint64_t>(), nullptr, sk != 0)) return false; }
   // the selection is set aside (a partition that outgrows its table means: back to the hash table, over the same selection)
   HIP_CHECK(hipMemcpyAsync(sel_keep.p, q->bitmap.p, nw * 8, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(tc_keep.p, q->tile_counts.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
@@ -324,8 +325,7 @@ static bool unique_radix(dfdb_query* q, const Column& col, int64_t cnt, UniqueTa
 static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueTables& T) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const bool is_str = T.is_str;
-  const int dt = dt_base(col.dtype);
-  const uint64_t* miss = (!is_str && dt_nullable(col.dtype)) ? col.missing.as<uint64_t>() : nullptr;
+  const ColRef key = is_str ? ColRef{} : col_ref(col);                 // (a flat String key travels as str_side(col) + str_table(T))
   const int64_t nt = ceil_div(t->nrows, kTileRows);
   const uint64_t capmax = pow2_at_least((uint64_t)cnt * 2);
   const uint64_t cap0 = std::min(capmax, pow2_at_least(1ull << std::min<int64_t>(40, std::max<int64_t>(10, ctx_option(ctx, "unique_cap0_log2", 21)))));
@@ -339,9 +339,8 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
   };
   auto insert = [&](int64_t t0, int64_t t1) {
     LaunchTimer lt(ctx, "unique_insert");
-    if (is_str) launch_unique_str(s, 0, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                                  t->nrows, t0, t1, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt);
-    else launch_unique_insert(s, q->bitmap.as<uint64_t>(), col.data.p, dt, miss, t0 * kTileRows, std::min(t->nrows, t1 * kTileRows), T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
+    if (is_str) launch_unique_str(s, 0, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), str_side(col), t->nrows, t0, t1, str_table(T));
+    else launch_unique_insert(s, q->bitmap.as<uint64_t>(), key, t0 * kTileRows, std::min(t->nrows, t1 * kTileRows), T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
   };
   uint64_t st[2] = {0, 0};                                             // claimed slots, abort flag
   auto read_state = [&](uint64_t* selected_before, int64_t tile) {
@@ -407,8 +406,7 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
     // the pass that compares every selected row with its slot's representative.  After an optimistic insert it also meets the rows that were never inserted: a string
     // the table does not hold raises the abort word and everything runs again with every row inserted (as groupreduce's accumulate pass does it)
     if (T.optimistic) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));
-    launch_unique_str(s, T.optimistic ? 3 : 1, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                      t->nrows, 0, nt, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt);
+    launch_unique_str(s, T.optimistic ? 3 : 1, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), str_side(col), t->nrows, 0, nt, str_table(T));
     int hit = 0; uint64_t unknown = 0;
     HIP_CHECK(hipMemcpyAsync(&hit, (char*)T.aux.p + 32, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
@@ -423,10 +421,9 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
     HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)nt * 4, s));
     launch_unique_scatter(s, T.ent.as<UniqueEntry>(), T.cap, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>());
   } else if (is_str) {
-    launch_unique_str(s, 2, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.as<int32_t>(), (const int64_t*)col.tile_off.p, col.bytes.as<uint8_t>(),
-                      t->nrows, 0, nt, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt);
+    launch_unique_str(s, 2, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), str_side(col), t->nrows, 0, nt, str_table(T));
   } else {
-    launch_unique_mark(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col.data.p, dt, miss, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
+    launch_unique_mark(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), key, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
   }
 }
 
@@ -479,12 +476,12 @@ static void restore_group_selection(dfdb_query* q) {
 // for the tables, a skewed column, no room — the caller's accumulate pass (global atomics) runs.  85-135 ms -> see profiles/r6_groupreduce_radix.txt.
 // mark: q's bitmap does NOT hold every group's first row yet (unique looked at the head of the column only): the table pass marks them itself — the bitmap is
 // cleared first, scanned afterwards, and *ng_io becomes the number of groups; on false the bitmap is whatever the pass left (the caller restores the selection).
-// (keys: the key column's values, their base dtype and missing bits — or a dictionary's 16-bit codes)
-static bool group_radix(dfdb_query* q, const void* keys, int dt, const uint64_t* kmiss, const Column* vc, int op, int64_t nsel, int64_t* ng_io, const uint64_t* sel, bool mark) {
+// (key: the key column — or a dictionary's 16-bit codes as a UInt16 column)
+static bool group_radix(dfdb_query* q, const ColRef& key, const Column* vc, int op, int64_t nsel, int64_t* ng_io, const uint64_t* sel, bool mark) {
   int64_t ng = mark ? *ng_io + *ng_io / 4 + 1024 : *ng_io;                // (marking: an estimate from the head — the tables are sized with room to spare)
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const int64_t mode = ctx_option(ctx, "unique_radix", 1);
-  if (mode == 0 || t->nrows >= (1ll << 32) - 8192 || dt == DFDB_STRING) return false;
+  if (mode == 0 || t->nrows >= (1ll << 32) - 8192 || key.dtype == DFDB_STRING) return false;
   int kbits = 9;                                                         // (512 partitions at least: one workgroup reduces one partition, and there are 256 CUs)
   while (kbits < 10 && ng / (1ll << kbits) > 1200) kbits++;              // (a 4096-slot table at 30 % load)
   if ((mark ? *ng_io : ng) / (1ll << kbits) > 2400) return false;        // (59 % load: the claims stop a table at 7/8, and that raises the abort word)
@@ -492,11 +489,11 @@ static bool group_radix(dfdb_query* q, const void* keys, int dt, const uint64_t*
   PooledScratch res(ctx);
   RadixRun run(ctx, kbits);
   if (!run.prepare(nsel, true, 128) || !try_ensure(res.buf, (size_t)(mark ? (int64_t)P * radix_group_slots() : ng) * 16 + 256)) return false;
-  const RadixPool& pool = run.pool; const int C = run.C;
+  const RadixPool& pool = run.pool;
   DevBuf& recs = ctx->radix_recs;
   uint64_t* aux = (uint64_t*)run.extra();                                // [0] the unstorable key's first row, [1] the missing key's, [3] abort; [4..7] gspec; [8] nres
   RadixGroup g{};
-  g.valcol = vc ? vc->data.p : nullptr; g.valdt = vc ? dt_base(vc->dtype) : 0;
+  g.val = col_ref(vc);
   const int kind = q->gr_kinds_n[0];
   g.gop = op == DFDB_AGG_SUM ? (kind == 2 ? 2 : 1) : (op == DFDB_AGG_MIN ? 3 : (op == DFDB_AGG_MAX ? 4 : 0));
   if (!vc) g.gop = 0;
@@ -506,11 +503,11 @@ static bool group_radix(dfdb_query* q, const void* keys, int dt, const uint64_t*
   // a key that a large part of the rows hold is reduced by the partition pass itself (k_radix.hip, hot keys: the form this replaces sent every one of its rows
   // through a global atomic on ONE address — 3.6 s per 1e9 rows with a key that 30 % of them hold); the kernels that do so are 0.8-1.1 ms slower where nothing is
   // hot, so the sample picks: some partition above THREE average ones, and they run
-  const int sk = run.skewed(sel, keys, dt, kmiss, t->nrows, 3);
+  const int sk = run.skewed(sel, key, t->nrows, 3);
   if (sk < 0) return false;
   if (sk) prof_note(ctx, "group_radix.skewed");
   { LaunchTimer lt(ctx, "radix_partition");
-    if (!launch_radix_partition(s, sel, keys, dt, kmiss, t->nrows, kbits, C, pool, recs.as<uint32_t>(), aux, &g, sk != 0)) return false; }
+    if (!launch_radix_partition(s, sel, key, t->nrows, run.grid(), pool, recs.as<uint32_t>(), aux, &g, sk != 0)) return false; }
   if (mark) {
     HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
     HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
@@ -533,6 +530,14 @@ static bool group_radix(dfdb_query* q, const void* keys, int dt, const uint64_t*
   launch_radix_group_finish(s, g, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), aux, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>());
   prof_note(ctx, "group_radix.taken");
   return true;                                                           // (the temporaries' destructor drains the stream)
+}
+
+// what every form of the single-reducer accumulate pass reads: the full selection (gr_sel), the value column (null: count only) and the outputs
+static AccArgs group_acc_args(dfdb_query* q, const Column* vc, int op, int64_t ng, uint64_t init) {
+  AccArgs A{};
+  A.sel = q->gr_sel.as<uint64_t>(); A.nrows = q->t->nrows; A.value(col_ref(vc)); A.op = op;
+  A.cnt = q->gr_cnt.as<uint64_t>(); A.val = q->gr_val.as<uint64_t>(); A.ngroups = (int)ng; A.val_init = init;
+  return A;
 }
 
 // groupreduce by the key column's values: unique's table (hash or dense; `T` holds it when this returns) + group numbers + an accumulate pass, or the radix
@@ -558,7 +563,7 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
     unique_impl(q, key_p, &T);
     if (T.group_estimate > 0) {                                  // the first chunk of rows promises more groups than any accumulate pass's LDS holds: by radix, first rows and all
       ng = T.group_estimate;
-      if (group_radix(q, kc.data.p, dt_base(kc.dtype), dt_nullable(kc.dtype) ? kc.missing.as<uint64_t>() : nullptr, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), true)) break;
+      if (group_radix(q, col_ref(kc), vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), true)) break;
       radix_failed = true;                                       // (skewed, too many groups, no room: the bitmap may have been cleared — everything again, the old way)
       restore_group_selection(q);
       continue;
@@ -575,7 +580,7 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
     // from the head of the column / a prefix of the rows is made again from all of them first
     if (!radix_failed && !T.is_str && ng > kGroupsInLds && ctx_option(ctx, "unique_radix", 1) != 0 && ng <= 2400 * 1024) {
       const bool partial = head_table || T.optimistic;          // unique looked at the head of the column / a prefix of the rows: not every group's first row is marked
-      if (group_radix(q, kc.data.p, dt_base(kc.dtype), dt_nullable(kc.dtype) ? kc.missing.as<uint64_t>() : nullptr, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), partial)) break;
+      if (group_radix(q, col_ref(kc), vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), partial)) break;
       radix_failed = true;
       if (partial) {                                             // not taken, and the bitmap may have been cleared: everything again, every row looked at
         whole_dense = true; pessimistic = true;
@@ -585,15 +590,14 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
     }
     int dense_lds = 0;
     { LaunchTimer lt(ctx, "group_accumulate");
-      const uint64_t* kmiss = dt_nullable(kc.dtype) ? kc.missing.as<uint64_t>() : nullptr;
-      if (T.dense)
-        dense_lds = launch_group_accumulate_dense(s, q->gr_sel.as<uint64_t>(), kc.data.p, dt_base(kc.dtype), kmiss, vc ? vc->data.p : nullptr, vc ? dt_base(vc->dtype) : 0, op, t->nrows, T.lo,
-                                      T.range, T.span_lo, T.span_hi, T.first.as<uint64_t>(), special, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init,
-                                      head_table ? T.aux.as<uint64_t>() + 3 : nullptr);
-      else if (T.is_str)
-        launch_group_accumulate_str(s, q->gr_sel.as<uint64_t>(), kc.data.as<int32_t>(), (const int64_t*)kc.tile_off.p, kc.bytes.as<uint8_t>(), vc ? vc->data.p : nullptr,
-                                    vc ? dt_base(vc->dtype) : 0, op, t->nrows, T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, special, T.salt,
-                                    q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init);
+      AccArgs A = group_acc_args(q, vc, op, ng, init);
+      A.special = special;
+      if (T.dense) {
+        A.key(col_ref(kc)); A.lo = T.lo; A.gids = T.first.as<uint64_t>();
+        A.unknown_flag = head_table ? T.aux.as<uint64_t>() + 3 : nullptr;
+        dense_lds = launch_group_accumulate(s, GROUP_SRC_DENSE, A, GroupAccExtra{nullptr, T.range, T.span_lo, T.span_hi});
+      } else if (T.is_str)
+        launch_group_accumulate_str(s, A, str_side(kc), str_table(T));
       else {
         // few groups of an 8-byte key: their keys (the key column at the first rows q's bitmap now holds, i.e. in group order) for the accumulate pass's LDS table
         const void* gkeys = nullptr;
@@ -602,10 +606,9 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
           launch_gather(s, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), kc.data.p, q->gr_keys.p, 8, t->nrows, ng);
           gkeys = q->gr_keys.p;
         }
-        if (launch_group_accumulate(s, q->gr_sel.as<uint64_t>(), kc.data.p, dt_base(kc.dtype), kmiss, vc ? vc->data.p : nullptr,
-                                    vc ? dt_base(vc->dtype) : 0, op, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, special,
-                                    q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init, T.optimistic ? T.aux.as<uint64_t>() + 3 : nullptr, gkeys) > 0)
-          prof_note(ctx, "group_accumulate.hash_lds");
+        A.key(col_ref(kc)); A.ent = T.ent.as<UniqueEntry>(); A.mask = T.cap - 1;
+        A.unknown_flag = T.optimistic ? T.aux.as<uint64_t>() + 3 : nullptr;      // the table was filled from a prefix of the rows: a key without a slot raises this word
+        if (launch_group_accumulate(s, GROUP_SRC_HASH, A, GroupAccExtra{gkeys, 0, 0, 0}) > 0) prof_note(ctx, "group_accumulate.hash_lds");
       } }
     if (dense_lds > 0) prof_note(ctx, "group_accumulate.dense_lds");
     if (head_table) {
@@ -693,11 +696,12 @@ void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, 
     DevBuf& rank = q->du_rank;
     ng = dict_unique(q, kc, &rank);
     // more codes in use than LDS accumulators hold: the codes are the keys of the radix form (the first occurrences are in the bitmap already)
-    if (!(ng > kGroupsInLds && group_radix(q, kc.dict_codes.p, DFDB_U16, nullptr, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), false))) {
+    if (!(ng > kGroupsInLds && group_radix(q, ColRef{kc.dict_codes.p, DFDB_U16, nullptr}, vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), false))) {
       reset_group_outputs(q, ng, op);
       LaunchTimer lt(ctx, "group_accumulate");
-      launch_group_accumulate_codes(s, q->gr_sel.as<uint64_t>(), kc.dict_codes.as<uint16_t>(), rank.as<uint32_t>(), vc ? vc->data.p : nullptr, vc ? dt_base(vc->dtype) : 0, op,
-                                    t->nrows, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>(), ng, init);
+      AccArgs A = group_acc_args(q, vc, op, ng, init);
+      A.codes = kc.dict_codes.as<uint16_t>(); A.rank_of_code = rank.as<uint32_t>();
+      launch_group_accumulate(s, GROUP_SRC_CODES, A, GroupAccExtra{});
     }
   } else ng = groupreduce_hashed(q, key_p, kc, vc, op, nsel, init, T);
   launch_group_finish(s, q->gr_val.as<uint64_t>(), ng, kinds[0], op);
@@ -708,20 +712,26 @@ void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, 
   if (key_bytes && dt_base(kc.dtype) == DFDB_STRING) *key_bytes = query_string_bytes(q, key_p);
 }
 
+// the counts of `ng` groups and the accumulators of `nvals` reducers (reducer-major) off the device; the counts to the caller's buffer as well
+static void fetch_group_results(dfdb_query* q, int64_t ng, int nvals, std::vector<uint64_t>& c, std::vector<uint64_t>& v, int64_t* counts) {
+  dfdb_ctx* ctx = q->t->ctx; hipStream_t s = ctx->stream;
+  c.resize((size_t)ng); v.resize((size_t)ng * (size_t)nvals);
+  HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
+  if (nvals) HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, v.size() * 8, hipMemcpyDeviceToHost, s));
+  stream_wait(ctx);
+  if (counts) memcpy(counts, c.data(), (size_t)ng * 8);
+}
 // the groups' keys (gathered over the first occurrences, i.e. in order of first appearance), counts and values -> caller buffers (host);
 // restores the query's full selection afterwards
 void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  dfdb_table* t = q->t;
   if (q->gr_state == 0 || q->gr_multi == 2) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce has not been called (or the query was executed, reset or changed since)");
   if (q->bitmap_rows != t->nrows) { q->gr_state = 0; fail(DFDB_ERR_ARGUMENT, "ArgumentError: the table changed between dfdb_query_groupreduce and its fetch"); }
   const int64_t ng = q->gr_n;
   if (ng > 0) {
     if (keys) { keys->memkind = keys->memkind == DFDB_MEM_DEVICE ? DFDB_MEM_DEVICE : DFDB_MEM_HOST; materialize_col(q, q->gr_keys_n[0], *keys, ng); }
-    std::vector<uint64_t> c((size_t)ng), v((size_t)ng);
-    HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    if (counts) memcpy(counts, c.data(), (size_t)ng * 8);
+    std::vector<uint64_t> c, v;
+    fetch_group_results(q, ng, 1, c, v, counts);
     group_values_out(v.data(), ng, q->gr_kinds_n.empty() ? 0 : q->gr_kinds_n[0], vals_i, vals_f);   // (no kind: an _n call without a reducer that was handed over)
   } else if (keys) { keys->count = 0; keys->nbytes = 0; }
   if (q->gr_state == 2) restore_group_selection(q);      // back to the full selection: bitmap + tile counts + prefix
@@ -768,7 +778,8 @@ static int64_t group_rank_key(dfdb_query* q, const Column& kc, const uint32_t* g
     unique_impl_col(q, kc, &T);
     n = query_count(q, -1);
     A.n = (uint64_t)n; A.special = T.aux.as<uint64_t>();
-    A.keycol = kc.data.p; A.keydt = dt_base(kc.dtype); A.missing = dt_nullable(kc.dtype) && !T.is_str ? kc.missing.as<uint64_t>() : nullptr;
+    const ColRef key = col_ref(kc);
+    A.keycol = key.data; A.keydt = key.dtype; A.missing = T.is_str ? nullptr : key.missing;
     LaunchTimer lt(ctx, "group_rank");
     if (T.dense) {
       launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
@@ -780,7 +791,7 @@ static int64_t group_rank_key(dfdb_query* q, const Column& kc, const uint32_t* g
     } else {
       launch_group_ids(s, T.ent.as<UniqueEntry>(), T.cap, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
       A.ent = T.ent.as<UniqueEntry>(); A.mask = T.cap - 1;
-      if (T.is_str) ok = launch_group_rank_str(s, A, kc.data.as<int32_t>(), (const int64_t*)kc.tile_off.p, kc.bytes.as<uint8_t>(), T.salt);
+      if (T.is_str) ok = launch_group_rank_str(s, A, str_side(kc), T.salt);
       else ok = launch_group_rank(s, 0, A);
     }
     stream_wait(ctx);                                          // the tables die here
@@ -835,7 +846,7 @@ void query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, 
   for (int m = 0; m < nvals; m++) HIP_CHECK(hipMemsetAsync(q->gr_val.as<uint64_t>() + (size_t)m * ng, stats[m] == DFDB_AGG_MIN ? 0xFF : 0, (size_t)ng * 8, s));
   MultiAccArgs A{};
   A.sel = q->gr_sel.as<uint64_t>(); A.gid = G; A.nrows = t->nrows; A.nvals = nvals;
-  for (int m = 0; m < nvals; m++) { A.valcol[m] = vcs[(size_t)m] ? vcs[(size_t)m]->data.p : nullptr; A.valdt[m] = vcs[(size_t)m] ? dt_base(vcs[(size_t)m]->dtype) : 0; A.op[m] = stats[m]; A.kind[m] = kinds[(size_t)m]; }
+  for (int m = 0; m < nvals; m++) { const ColRef v = col_ref(vcs[(size_t)m]); A.valcol[m] = v.data; A.valdt[m] = v.dtype; A.op[m] = stats[m]; A.kind[m] = kinds[(size_t)m]; }
   A.cnt = q->gr_cnt.as<uint64_t>(); A.val = q->gr_val.as<uint64_t>(); A.ngroups = ng; A.flag = flag.buf.as<uint64_t>();
   HIP_CHECK(hipMemsetAsync(flag.buf.p, 0, 8, s));
   int form;
@@ -853,7 +864,7 @@ void query_groupreduce_n(dfdb_query* q, const int32_t* key_cols, int32_t nkeys, 
 // the groups' keys (one dfdb_outcol per key column, gathered over the first rows), counts and values (reducer-major; a count reducer's values are the counts)
 // -> caller buffers (host); restores the query's full selection afterwards
 void query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  dfdb_table* t = q->t;
   if (q->gr_state == 0 || q->gr_multi == 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: dfdb_query_groupreduce_n has not been called (or the query was executed, reset or changed since)");
   const int nvals = (int)q->gr_ops_n.size();
   if (q->gr_multi == 1) {                                      // handed to dfdb_query_groupreduce: its fetch, and a count reducer's values from the counts
@@ -871,11 +882,8 @@ void query_groupreduce_n_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts
   const int nkeys = (int)q->gr_keys_n.size();
   if (ng > 0) {
     if (keys) for (int k = 0; k < nkeys; k++) { keys[k].memkind = keys[k].memkind == DFDB_MEM_DEVICE ? DFDB_MEM_DEVICE : DFDB_MEM_HOST; materialize_col(q, q->gr_keys_n[(size_t)k], keys[k], ng); }
-    std::vector<uint64_t> c((size_t)ng), v((size_t)ng * (size_t)nvals);
-    HIP_CHECK(hipMemcpyAsync(c.data(), q->gr_cnt.p, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-    if (nvals) HIP_CHECK(hipMemcpyAsync(v.data(), q->gr_val.p, v.size() * 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    if (counts) memcpy(counts, c.data(), (size_t)ng * 8);
+    std::vector<uint64_t> c, v;
+    fetch_group_results(q, ng, nvals, c, v, counts);
     for (int m = 0; m < nvals; m++) {
       const bool cnt_red = q->gr_ops_n[(size_t)m] == DFDB_AGG_COUNT;
       const size_t m0 = (size_t)m * (size_t)ng;
