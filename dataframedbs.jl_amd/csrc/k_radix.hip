@@ -16,7 +16,7 @@
 // A key that a large part of the rows hold (one partition = one workgroup's work) is kept out of the records: the partition pass gives it one of a workgroup's
 // 256 LDS slots (HOT KEYS, below) and the table pass gets one list entry per workgroup and key instead.
 // A partition that holds more distinct keys than its table takes raises a flag and the host runs the hash-table form instead (unique.cpp: unique_hashed); keys
-// are isequal images (one NaN, -0.0 apart from 0.0), a missing key and the one image that cannot be stored (all ones) are kept aside in aux[1] / aux[0]
+// are isequal images (one NaN, -0.0 apart from 0.0), a missing key and the one image that cannot be stored (all ones) are kept aside in KeyAux::special_row
 // exactly as k_unique_insert keeps them.  Measured history: profiles/r6_unique_radix.txt; what the instruction and store choices rest on: tools/ubench/.
 #include "device_utils.hpp"
 #include "value_rules.hpp"
@@ -58,7 +58,7 @@ __device__ __forceinline__ void aux_min(uint64_t* a, uint64_t row) {
 // instructions per 64 rows: at 2.5-4.3 cycles per wave-instruction (tools/ubench/valu_rate.hip) that, not HBM, was what both passes waited for.
 // FULL = every row of the tile exists (base + 8192 <= nrows); the one partial tile of a table clamps its word and row numbers instead.
 // A row takes part when it is selected, not missing and its image can be stored; the special rows go to aux in the partition pass: a missing key's
-// smallest row to aux[1] here, the unstorable image's (all ones) to aux[0] where the keys are looked at.
+// smallest row to special_row[SPECIAL_MISSING] here, the unstorable image's (all ones) to special_row[SPECIAL_UNSTORABLE] where the keys are looked at.
 template <int KIND, bool FULL>
 __device__ __forceinline__ uint64_t tile_load(uint64_t (&key)[8], uint64_t (&in)[8], const uint64_t* __restrict__ sel, const void* __restrict__ col, int dtype,
                                               const uint64_t* __restrict__ missing, int64_t base, int64_t nrows, int wv, int lane) {
@@ -114,15 +114,15 @@ __device__ __forceinline__ uint64_t tile_load(uint64_t (&key)[8], uint64_t (&in)
   }
   return selected_missing;                                      // (wave-uniform: nonzero = the partition pass looks for the tile's first missing row, tile_first_missing)
 }
-// the rare side of the partition pass: the smallest selected row of the wave's 512 whose key is missing, to aux[1]
-__device__ __forceinline__ void tile_first_missing(const uint64_t* __restrict__ sel, const uint64_t* __restrict__ missing, int64_t base, int64_t nrows, int wv, int lane, uint64_t* aux) {
+// the rare side of the partition pass: the smallest selected row of the wave's 512 whose key is missing, to special_row[SPECIAL_MISSING]
+__device__ __forceinline__ void tile_first_missing(const uint64_t* __restrict__ sel, const uint64_t* __restrict__ missing, int64_t base, int64_t nrows, int wv, int lane, KeyAux* aux) {
   const int64_t w0 = (base >> 6) + wv * 8, wl = (nrows - 1) >> 6;
   for (int j = 0; j < 8; j++) {
     const int64_t w = w0 + j;
     if (w > wl) break;
     uint64_t m = wave_uniform(sel[w] & missing[w]);
     if (w == wl && (nrows & 63)) m &= (1ull << (nrows & 63)) - 1ull;
-    if (m) { if (lane == 0) aux_min(&aux[1], (uint64_t)(w * 64 + __builtin_ctzll(m))); break; }
+    if (m) { if (lane == 0) aux_min(&aux->special_row[SPECIAL_MISSING], (uint64_t)(w * 64 + __builtin_ctzll(m))); break; }
   }
 }
 // the lanes of the wave whose key can be stored, as a mask (all ones is the table's "empty"); Float64 keys become their isequal image first: one NaN — and all
@@ -199,7 +199,7 @@ __device__ __forceinline__ void acc_value(uint64_t* slot, uint64_t v, int gop, i
 template <int KIND, int BLOCK, bool HASVAL, bool V8, bool HOT>
 __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __restrict__ sel, const void* __restrict__ col, int dtype, const uint64_t* __restrict__ missing,
                                                              int64_t nrows, int64_t rows_per_chunk, int kbits, RadixPool pool,
-                                                             uint32_t* __restrict__ recs_out, uint64_t* aux, RadixVals vals) {
+                                                             uint32_t* __restrict__ recs_out, KeyAux* aux, RadixVals vals) {
   __shared__ uint64_t spec_sh[4];                               // HASVAL: {rows, reduced value} of the rows whose key is the unstorable image, then of the rows whose key is missing: this workgroup's
   __shared__ uint64_t hc_key[HOT ? kHotSlots : 1], hc_val[HOT && HASVAL ? kHotSlots : 1];      // the hot keys' slots: key, (HASVAL) reduced value, ...
   __shared__ uint32_t hc_cnt[HOT ? kHotSlots : 1], hc_row[HOT ? kHotSlots : 1], hc_any;         // ... rows, smallest row; whether any slot is taken
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
 #pragma unroll
     for (int j = 0; j < 8; j++)
       if (__builtin_amdgcn_inverse_ballot_w64(take[j])) { const uint32_t p = rhash(key[j]) >> sh; pr[j] = p << 13 | atomicAdd(&hist2[p], 1u); }
-    if (nmiss) {                                                // (rare: the two keys kept aside — a missing key's first row, aux[1] — and, HASVAL, its rows and their values; ...
+    if (nmiss) {                                                // (rare: the two keys kept aside — a missing key's first row — and, HASVAL, its rows and their values; ...
       tile_first_missing(sel, missing, base, nrows, wv, lane, aux);
       if (HASVAL) {
         const int64_t w0 = (base >> 6) + wv * 8, wl = (nrows - 1) >> 6;
@@ -285,12 +285,12 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
         }
       }
     }
-    if (unstorable) {                                           // ... the unstorable image's, aux[0]: -1 in an Int64 column is that image; one lane of the wave reports)
+    if (unstorable) {                                           // ... the unstorable image's first row: -1 in an Int64 column is that image; one lane of the wave reports)
       bool first = true;
       for (int j = 0; j < 8; j++) {
         const uint64_t bad = nin[j] & ~keys_storable<KIND>(key[j]);
         if (!bad) continue;
-        if (first && lane == 0) aux_min(&aux[0], (uint64_t)(base + wv * 512 + j * 64 + __builtin_ctzll(bad)));
+        if (first && lane == 0) aux_min(&aux->special_row[SPECIAL_UNSTORABLE], (uint64_t)(base + wv * 512 + j * 64 + __builtin_ctzll(bad)));
         first = false;
         if (!HASVAL) break;
         if (lane == 0) atomicAdd((unsigned long long*)&spec_sh[0], (unsigned long long)__builtin_popcountll(bad));
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
       uint32_t* e0 = pool.pt + (size_t)fx * pool.maxv + k0;
       uint32_t b0 = pool.dump_page, b1 = pool.dump_page;
       const bool over = k1 >= pool.maxv;
-      if (over) __atomic_store_n(&aux[3], 1ull, __ATOMIC_RELAXED);             // aux[kAuxAbort]: this column needs the hash-table form (the records go to the spare page)
+      if (over) __atomic_store_n(&aux->abort, 1ull, __ATOMIC_RELAXED);             // this column needs the hash-table form (the records go to the spare page)
       // first the taking ...  (publishing and reading the page table are read-modify-write atomics — exchanged, OR-ed with zero —: they are performed where the
       // other XCDs' are; an acquiring LOAD per thread and tile invalidated the CU's caches 512 times a tile and the pass took 19 ms)
       if (!over && k1 != k0) { b1 = atomicAdd(pool.next_page, 1u); atomicExch(e0 + 1, b1); }
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
           uint32_t spins = 0;                                                   // (bounded: a page that never comes — it cannot — would end in the abort flag, not in a hang)
           while ((b0 = atomicOr(e0, 0u)) == 0xFFFFFFFFu) {
             __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1u << 22)) { __atomic_store_n(&aux[3], 1ull, __ATOMIC_RELAXED); b0 = pool.dump_page; break; }
+            if (++spins > (1u << 22)) { __atomic_store_n(&aux->abort, 1ull, __ATOMIC_RELAXED); b0 = pool.dump_page; break; }
           }
         }
       }
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(BLOCK) void k_radix_partition(const uint64_t* __res
   if (HOT && tid < kHotSlots && hc_key[tid] != kREmpty && hc_cnt[tid]) {     // the hot keys' slots -> the launch's list
     const uint32_t i = atomicAdd(pool.hot_n, 1u);
     if (i < pool.hot_cap) { pool.hot[3 * (size_t)i] = hc_key[tid]; pool.hot[3 * (size_t)i + 1] = HASVAL ? hc_val[tid] : 0ull; pool.hot[3 * (size_t)i + 2] = (uint64_t)hc_cnt[tid] << 32 | hc_row[tid]; }
-    else __atomic_store_n(&aux[3], 1ull, __ATOMIC_RELAXED);                // (cannot happen: the list holds every workgroup's every slot)
+    else __atomic_store_n(&aux->abort, 1ull, __ATOMIC_RELAXED);                // (cannot happen: the list holds every workgroup's every slot)
   }
   if (HASVAL) {                                                 // the workgroup's rows of the unstorable key / the missing key -> the launch's
     if (tid < 2 && spec_sh[2 * tid]) {
@@ -468,7 +468,7 @@ __device__ __forceinline__ void recs_load(uint64_t (&kk)[4], uint32_t (&rw)[4], 
   }
 }
 __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __restrict__ recs, RadixPool pool,
-                                                          int P, uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, uint64_t* aux, int kbits) {
+                                                          int P, uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, KeyAux* aux, int kbits) {
   extern __shared__ uint64_t tab_sh[];
   uint64_t* tkey = tab_sh;                                    // [kRSlots]
   uint32_t* trow = (uint32_t*)(tkey + kRSlots);               // [kRSlots]
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __rest
   for (int p = (int)blockIdx.x; p < P; p += (int)gridDim.x) {
     uint32_t qn = 0;                                          // (wave-uniform)
     for (int i = tid; i < kRSlots; i += kRBlock) { tkey[i] = kREmpty; trow[i] = 0xFFFFFFFFu; }
-    if (tid == 0) { claims_sh = 0; abort_sh = __atomic_load_n(&aux[3], __ATOMIC_RELAXED) != 0; }
+    if (tid == 0) { claims_sh = 0; abort_sh = __atomic_load_n(&aux->abort, __ATOMIC_RELAXED) != 0; }
     __syncthreads();
     if (abort_sh) return;                                     // (the partition pass gave up on a stream: the hash table answers)
     // the partition's records: its kRShare streams one after the other, a stream page by page, a page in two blocks of 4096 records (all wave-uniform).
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __rest
         if ((int)(rhash(key) >> (32 - kbits)) == p) table_claim(tkey, trow, key, (uint32_t)pool.hot[3 * (size_t)i + 2], &claims_sh, &abort_sh);
       } }
     __syncthreads();
-    if (abort_sh) { if (tid == 0) __atomic_store_n(&aux[3], 1ull, __ATOMIC_RELAXED); return; }      // aux[kAuxAbort]: this column needs the hash-table form
+    if (abort_sh) { if (tid == 0) __atomic_store_n(&aux->abort, 1ull, __ATOMIC_RELAXED); return; }      // this column needs the hash-table form
     for (int i = tid; i < kRSlots; i += kRBlock) {
       if (tkey[i] == kREmpty) continue;
       const uint64_t r = trow[i];
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_unique(const uint32_t* __rest
       atomicAdd(&tile_counts[r >> 10], 1u);
     }
     if (p == 0 && tid < 2) {                                  // the two keys kept aside: the unstorable image, missing
-      const uint64_t r = aux[tid];
+      const uint64_t r = aux->special_row[tid];
       if (r != kREmpty) { atomicOr((unsigned long long*)&bitmap[r >> 6], 1ull << (r & 63)); atomicAdd(&tile_counts[r >> 10], 1u); }
     }
     __syncthreads();
@@ -628,7 +628,7 @@ __device__ __forceinline__ void recs20_load(uint64_t (&kk)[4], uint32_t (&rw)[4]
   }
 }
 __global__ __launch_bounds__(kRBlock) void k_radix_group(const uint32_t* __restrict__ recs, RadixPool pool, int P, int mark, uint64_t* __restrict__ bitmap,
-                                                         uint32_t* __restrict__ tile_counts, uint64_t* aux, uint4* __restrict__ results, uint32_t* __restrict__ nres,
+                                                         uint32_t* __restrict__ tile_counts, KeyAux* aux, uint4* __restrict__ results, uint32_t* __restrict__ nres,
                                                          int gop, int vkind, int kbits) {
   extern __shared__ uint64_t tab_sh[];
   uint64_t* tkey = tab_sh;                                    // [kGSlots]
@@ -645,7 +645,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_group(const uint32_t* __restr
   for (int p = (int)blockIdx.x; p < P; p += (int)gridDim.x) {
     uint32_t qn = 0;
     for (int i = tid; i < kGSlots; i += kRBlock) { tkey[i] = kREmpty; trow[i] = 0xFFFFFFFFu; tcnt[i] = 0; tval[i] = vinit; }
-    if (tid == 0) { claims_sh = 0; abort_sh = __atomic_load_n(&aux[3], __ATOMIC_RELAXED) != 0; }
+    if (tid == 0) { claims_sh = 0; abort_sh = __atomic_load_n(&aux->abort, __ATOMIC_RELAXED) != 0; }
     __syncthreads();
     if (abort_sh) return;
     const uint32_t vfront = pool.front[p * kRShare + (lane & (kRShare - 1))];
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_group(const uint32_t* __restr
       gtable_merge(tkey, trow, tcnt, tval, key, (uint32_t)cr, (uint32_t)(cr >> 32), hot[3 * (size_t)i + 1], gop, &claims_sh, &abort_sh);
     }
     __syncthreads();
-    if (abort_sh) { if (tid == 0) __atomic_store_n(&aux[3], 1ull, __ATOMIC_RELAXED); return; }
+    if (abort_sh) { if (tid == 0) __atomic_store_n(&aux->abort, 1ull, __ATOMIC_RELAXED); return; }
     for (int i = tid; i < kGSlots; i += kRBlock) {
       if (tkey[i] == kREmpty) continue;
       const uint64_t r = trow[i], v = tval[i];
@@ -722,7 +722,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_group(const uint32_t* __restr
       if (mark) { atomicOr((unsigned long long*)&bitmap[r >> 6], 1ull << (r & 63)); atomicAdd(&tile_counts[r >> 10], 1u); }
     }
     if (mark && p == 0 && tid < 2) {                          // the two keys kept aside: the unstorable image, missing
-      const uint64_t r = aux[tid];
+      const uint64_t r = aux->special_row[tid];
       if (r != kREmpty) { atomicOr((unsigned long long*)&bitmap[r >> 6], 1ull << (r & 63)); atomicAdd(&tile_counts[r >> 10], 1u); }
     }
     __syncthreads();
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(kRBlock) void k_radix_group(const uint32_t* __restr
 // results -> the groups' places: a result's group is the rank of its first row among the first rows (the bitmap's set bits, `prefix` = set bits before every
 // 1024-row tile); the unstorable key's group takes the partition pass's own accumulator
 __global__ void k_radix_group_finish(const uint4* __restrict__ results, const uint32_t* __restrict__ nres, const uint64_t* __restrict__ ubits, const uint64_t* __restrict__ uprefix,
-                                     const uint64_t* aux, const uint64_t* gspec, uint64_t* __restrict__ cnt, uint64_t* __restrict__ val) {
+                                     const KeyAux* aux, const uint64_t* gspec, uint64_t* __restrict__ cnt, uint64_t* __restrict__ val) {
   auto rank_of = [&](uint64_t row) -> uint64_t {
     const uint64_t tile = row >> 10, w = (row & 1023) >> 6;
     uint64_t r = uprefix[tile];
@@ -744,7 +744,7 @@ __global__ void k_radix_group_finish(const uint4* __restrict__ results, const ui
     const uint64_t g = rank_of(r.x);
     cnt[g] = r.y; val[g] = (uint64_t)r.w << 32 | r.z;
   }
-  if (blockIdx.x == 0 && threadIdx.x < 2 && aux[threadIdx.x] != kREmpty) { const uint64_t g = rank_of(aux[threadIdx.x]); cnt[g] = gspec[2 * threadIdx.x]; val[g] = gspec[2 * threadIdx.x + 1]; }
+  if (blockIdx.x == 0 && threadIdx.x < 2 && aux->special_row[threadIdx.x] != kREmpty) { const uint64_t g = rank_of(aux->special_row[threadIdx.x]); cnt[g] = gspec[2 * threadIdx.x]; val[g] = gspec[2 * threadIdx.x + 1]; }
 }
 }  // namespace
 
@@ -774,12 +774,12 @@ bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const ColRef& key, 
 }
 // (512-thread workgroups sorting 4096 rows, two per CU, instead of one of 1024 sorting 8192: 5.36-5.43 ms against 5.32-5.33 — the pass waits for its stores either way)
 // group = nullptr: 12-byte records for unique; otherwise 20-byte records {key, row, value} for groupreduce (group->val may be no column: count only)
-bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, const RadixPool& pool, uint32_t* recs_out, uint64_t* aux,
+bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, const RadixPool& pool, uint32_t* recs_out, KeyAux* aux,
                             const RadixGroup* group, bool hot) {
   const int kbits = grid.kbits, chunks = grid.chunks;
   if (kbits < 6 || kbits > 10 || nrows < 1 || chunks % kRShare) return false;
   RadixVals v{};
-  if (group) { v.col = group->val.data; v.vdt = group->val.dtype; v.gspec = group->gspec; v.gop = group->gop; v.vkind = group->vkind; }
+  if (group) { v.col = group->val.data; v.vdt = group->val.dtype; v.gspec = group->aux->gspec; v.gop = group->gop; v.vkind = group->vkind; }
   const bool v8 = !group || !group->val.data || dt_is_w8(group->val.dtype);
   return with_radix_kind(key.dtype, [&](auto kind) {
     auto go = [&](auto hasval, auto v8_c, auto hot_c) {
@@ -794,19 +794,18 @@ bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& ke
     return hot ? go(no, yes, yes) : go(no, yes, no);
   });
 }
-bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux,
-                        const RadixGroup& group, int cus) {
+bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, const RadixGroup& group, int cus) {
   const size_t lds = (size_t)kGSlots * 24 + (size_t)(kRBlock / 64) * kRQueue * 20;
   if (!allow_dynamic_lds((const void*)k_radix_group, 156 * 1024)) return false;
   const int P = 1 << kbits;
-  hipLaunchKernelGGL(k_radix_group, dim3(P < cus ? P : cus), dim3(kRBlock), lds, s, recs, pool, P, mark ? 1 : 0, bitmap, tile_counts, aux, (uint4*)group.results, group.nres,
+  hipLaunchKernelGGL(k_radix_group, dim3(P < cus ? P : cus), dim3(kRBlock), lds, s, recs, pool, P, mark ? 1 : 0, bitmap, tile_counts, &group.aux->head, (uint4*)group.results, (uint32_t*)&group.aux->nres,
                      group.gop, group.vkind, kbits);
   return hipGetLastError() == hipSuccess;
 }
-void launch_radix_group_finish(hipStream_t s, const RadixGroup& group, const uint64_t* ubits, const uint64_t* uprefix, const uint64_t* aux, uint64_t* cnt, uint64_t* val) {
-  hipLaunchKernelGGL(k_radix_group_finish, dim3(1024), dim3(256), 0, s, (const uint4*)group.results, group.nres, ubits, uprefix, aux, group.gspec, cnt, val);
+void launch_radix_group_finish(hipStream_t s, const RadixGroup& group, const uint64_t* ubits, const uint64_t* uprefix, uint64_t* cnt, uint64_t* val) {
+  hipLaunchKernelGGL(k_radix_group_finish, dim3(1024), dim3(256), 0, s, (const uint4*)group.results, (const uint32_t*)&group.aux->nres, ubits, uprefix, &group.aux->head, group.aux->gspec, cnt, val);
 }
-bool launch_radix_unique(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux, int cus) {
+bool launch_radix_unique(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, uint64_t* bitmap, uint32_t* tile_counts, KeyAux* aux, int cus) {
   const size_t lds = (size_t)kRSlots * 12 + (size_t)(kRBlock / 64) * kRQueue * 12;
   if (!allow_dynamic_lds((const void*)k_radix_unique, 156 * 1024)) return false;
   const int P = 1 << kbits;

@@ -32,17 +32,15 @@ namespace dfdb {
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = 4;
 constexpr int64_t kTile = 1024;
-constexpr uint64_t kEmpty = 0xFFFFFFFFFFFFFFFFull;    // never stored as a key: a value with this image uses aux[0]
+constexpr uint64_t kEmpty = 0xFFFFFFFFFFFFFFFFull;    // never stored as a key: a value with this image uses KeyAux::special_row
 constexpr int kMaxProbe = 256;                        // a longer probe sequence means the table is too full: abort, the host grows it
-// aux (8 x u64 beside the table): 0 = smallest row whose key is kEmpty, 1 = smallest missing row, 2 = claimed slots, 3 = abort flag, 4 = (int) hash collision seen
-constexpr int kAuxClaims = 2, kAuxAbort = 3;
 constexpr uint64_t kNoSlot = 0xFFFFFFFFFFFFFFFFull;
 
 __device__ __forceinline__ uint64_t slot_of(uint64_t key, uint64_t mask) { return splitmix64(key) & mask; }
 
 // -> the key's slot, bit 63 set when the key was already there (clear: this call claimed the slot), kNoSlot when the probe sequence got too long
 // (h: where the probe sequence starts — slot_of(key) for values that are their own keys, the low bits of a String's key, which is a hash already)
-__device__ __forceinline__ uint64_t table_insert(UniqueEntry* ent, uint64_t mask, uint64_t key, uint64_t row, uint64_t* aux, uint64_t h) {
+__device__ __forceinline__ uint64_t table_insert(UniqueEntry* ent, uint64_t mask, uint64_t key, uint64_t row, UniqueAux* aux, uint64_t h) {
   for (int probes = 0; probes < kMaxProbe; probes++) {
     // plain loads first (key and row of a slot share a line): with few distinct values nearly every row finds its key in place and a smaller row
     // recorded, and skips both atomics (5e8 rows of 10 distinct strings: 0.60 s with every row hammering the same 10 addresses, 0.023 s so).  A
@@ -56,7 +54,7 @@ __device__ __forceinline__ uint64_t table_insert(UniqueEntry* ent, uint64_t mask
     }
     h = (h + 1) & mask;
   }
-  __atomic_store_n(&aux[kAuxAbort], 1ull, __ATOMIC_RELAXED);
+  __atomic_store_n(&aux->head.abort, 1ull, __ATOMIC_RELAXED);
   return kNoSlot;
 }
 __device__ __forceinline__ uint64_t table_find(const UniqueEntry* ent, uint64_t mask, uint64_t key, uint64_t h) {
@@ -85,17 +83,17 @@ __device__ __forceinline__ uint64_t table_row_maybe(const UniqueEntry* ent, uint
   }
   return kEmpty;
 }
-// a workgroup's claimed slots -> aux[kAuxClaims] (one atomic per workgroup)
-__device__ __forceinline__ void add_claims(uint32_t mine, uint32_t* sh, uint64_t* aux) {
+// a workgroup's claimed slots -> aux->head.claims (one atomic per workgroup)
+__device__ __forceinline__ void add_claims(uint32_t mine, uint32_t* sh, UniqueAux* aux) {
   if (mine) atomicAdd(sh, mine);
   __syncthreads();
-  if (threadIdx.x == 0 && *sh) atomicAdd((unsigned long long*)&aux[kAuxClaims], (unsigned long long)*sh);
+  if (threadIdx.x == 0 && *sh) atomicAdd((unsigned long long*)&aux->head.claims, (unsigned long long)*sh);
 }
 
 // ---------------------------------------------------------------- fixed-width columns
 __global__ __launch_bounds__(kBlock) void k_unique_insert(const uint64_t* __restrict__ bitmap, const void* __restrict__ col, int dtype,
                                                           const uint64_t* __restrict__ missing, int64_t row0, int64_t row1, UniqueEntry* ent,
-                                                          uint64_t mask, uint64_t* aux) {
+                                                          uint64_t mask, UniqueAux* aux) {
   __shared__ uint32_t claims_sh;
   if (threadIdx.x == 0) claims_sh = 0;
   __syncthreads();
@@ -103,9 +101,9 @@ __global__ __launch_bounds__(kBlock) void k_unique_insert(const uint64_t* __rest
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t row = row0 + (int64_t)blockIdx.x * kBlock + threadIdx.x; row < row1; row += stride) {
     if (!((bitmap[row >> 6] >> (row & 63)) & 1ull)) continue;
-    if (missing && ((missing[row >> 6] >> (row & 63)) & 1ull)) { if (__atomic_load_n(&aux[1], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux[1], (unsigned long long)row); continue; }
+    if (missing && ((missing[row >> 6] >> (row & 63)) & 1ull)) { if (__atomic_load_n(&aux->head.special_row[SPECIAL_MISSING], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux->head.special_row[SPECIAL_MISSING], (unsigned long long)row); continue; }
     const uint64_t key = key_image(col, dtype, row);
-    if (key == kEmpty) { if (__atomic_load_n(&aux[0], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux[0], (unsigned long long)row); continue; }
+    if (key == kEmpty) { if (__atomic_load_n(&aux->head.special_row[SPECIAL_UNSTORABLE], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux->head.special_row[SPECIAL_UNSTORABLE], (unsigned long long)row); continue; }
     const uint64_t r = table_insert(ent, mask, key, (uint64_t)row, aux, slot_of(key, mask));
     if (r == kNoSlot) break;                          // the table is too full: the host grows it and repeats the chunk
     mine += (uint32_t)!(r >> 63);
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void k_unique_insert(const uint64_t* __rest
 
 // the entries of a table that became too small, into its successor (strings: with their representatives)
 __global__ __launch_bounds__(kBlock) void k_unique_migrate(const UniqueEntry* __restrict__ from, const uint64_t* __restrict__ from_off, const uint32_t* __restrict__ from_len,
-                                                           uint64_t from_cap, UniqueEntry* ent, uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, uint64_t* aux) {
+                                                           uint64_t from_cap, UniqueEntry* ent, uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, UniqueAux* aux) {
   __shared__ uint32_t claims_sh;
   if (threadIdx.x == 0) claims_sh = 0;
   __syncthreads();
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void k_unique_migrate(const UniqueEntry* __
 
 __global__ __launch_bounds__(kBlock) void k_unique_mark(uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, const void* __restrict__ col,
                                                         int dtype, const uint64_t* __restrict__ missing, int64_t nrows, int64_t ntiles,
-                                                        const UniqueEntry* __restrict__ ent, uint64_t mask, const uint64_t* __restrict__ aux) {
+                                                        const UniqueEntry* __restrict__ ent, uint64_t mask, const UniqueAux* __restrict__ aux) {
   const int lane = lane_id();
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
@@ -148,10 +146,10 @@ __global__ __launch_bounds__(kBlock) void k_unique_mark(uint64_t* __restrict__ b
       if (w) {
         const int64_t row = tile * kTile + j * 64 + lane;
         if (row < nrows && ((w >> lane) & 1ull)) {
-          if (missing && ((missing[row >> 6] >> (row & 63)) & 1ull)) first = aux[1] == (uint64_t)row;
+          if (missing && ((missing[row >> 6] >> (row & 63)) & 1ull)) first = aux->head.special_row[SPECIAL_MISSING] == (uint64_t)row;
           else {
             const uint64_t key = key_image(col, dtype, row);
-            first = key == kEmpty ? aux[0] == (uint64_t)row : ent[table_find(ent, mask, key, slot_of(key, mask))].row == (uint64_t)row;
+            first = key == kEmpty ? aux->head.special_row[SPECIAL_UNSTORABLE] == (uint64_t)row : ent[table_find(ent, mask, key, slot_of(key, mask))].row == (uint64_t)row;
           }
         }
       }
@@ -166,13 +164,13 @@ __global__ __launch_bounds__(kBlock) void k_unique_mark(uint64_t* __restrict__ b
 
 // the first occurrences straight out of the table (few distinct values beside the rows): one bit + one tile count per occupied slot, into a
 // bitmap and tile counts the host has cleared
-__global__ __launch_bounds__(kBlock) void k_unique_scatter(const UniqueEntry* __restrict__ ent, uint64_t cap, const uint64_t* __restrict__ aux,
+__global__ __launch_bounds__(kBlock) void k_unique_scatter(const UniqueEntry* __restrict__ ent, uint64_t cap, const UniqueAux* __restrict__ aux,
                                                            uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts) {
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < cap + 2; i += stride) {
     uint64_t r;
     if (i < cap) { if (ent[i].key == kEmpty) continue; r = ent[i].row; }
-    else { r = aux[i - cap]; if (r == kEmpty) continue; }
+    else { r = aux->head.special_row[i - cap]; if (r == kEmpty) continue; }
     atomicOr((unsigned long long*)&bitmap[r >> 6], 1ull << (r & 63));
     atomicAdd(&tile_counts[r >> 10], 1u);
   }
@@ -328,9 +326,9 @@ __device__ __forceinline__ void group_flush(const uint64_t* lcnt, const uint64_t
 // KIND 0: insert {key, row} for the tiles [tile0, tile1); 1: compare every selected row with its slot's representative; 2: groupreduce's accumulate pass (+ that compare)
 struct StrPassArgs {
   const uint64_t* sel; const int32_t* sizes; const int64_t* tile_off; const uint8_t* bytes; int64_t nrows, tile0, tile1;
-  UniqueEntry* ent; uint64_t* rep_off; uint32_t* rep_len; uint64_t mask; uint64_t* aux; uint64_t salt;
+  UniqueEntry* ent; uint64_t* rep_off; uint32_t* rep_len; uint64_t mask; UniqueAux* aux; uint64_t salt;
   const void* valcol; int valdt, op; uint64_t* cnt; uint64_t* val; int ngroups; uint64_t val_init;       // KIND 2
-  int maybe;                                                   // KIND 1: the table may not hold every string (an optimistic unique): an unknown one raises aux[kAuxAbort]
+  int maybe;                                                   // KIND 1: the table may not hold every string (an optimistic unique): an unknown one raises aux->head.abort
 };
 constexpr int kHotGroups = 256;                      // LDS slots for hot groups where every row's value goes through a global atomic (k_group_acc<0>, k_str_pass<2, 0>)
 // NGL: groups the workgroup's LDS accumulators hold (0: global atomics — and kHotGroups slots for hot groups, as in k_group_acc<0>); OPK: group_add_t; V8: the value column is 8 bytes wide (loaded as is; the narrow types'
@@ -362,15 +360,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
   MetCacheT<kSlots> met;
   met.init(met_e[threadIdx.x >> 6], met_c[threadIdx.x >> 6], lane);
   uint32_t claimed = 0;
-  int* collision = (int*)(A.aux + 4);
-  const uint64_t gid_missing = KIND == 2 ? A.aux[1] : 0ull;
+  int* collision = (int*)&A.aux->collision;
+  const uint64_t gid_missing = KIND == 2 ? A.aux->head.special_row[SPECIAL_MISSING] : 0ull;
   // (properties of the value column, looked at ONCE: inside the unrolled row loops the dtype switch was a chain of scalar compares per row)
   const int vkind = KIND == 2 && has_val ? value_kind(A.valdt) : 0;
   constexpr bool val8 = KIND == 2 && has_val && V8;
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
   for (int64_t tile = A.tile0 + wave; tile < A.tile1; tile += nwaves) {
-    if (KIND == 0 && __atomic_load_n(&A.aux[kAuxAbort], __ATOMIC_RELAXED)) break;      // (wave-uniform) too full: the host grows the table and repeats the chunk
+    if (KIND == 0 && __atomic_load_n(&A.aux->head.abort, __ATOMIC_RELAXED)) break;      // (wave-uniform) too full: the host grows the table and repeats the chunk
     const uint64_t mine = lane < 16 ? A.sel[tile * 16 + lane] : 0ull;
     if (__ballot(mine != 0) == 0) continue;
     if (HOT && !hot_on) hot_on = __builtin_amdgcn_readfirstlane((int)*(volatile uint32_t*)&hg_any) != 0;
@@ -417,7 +415,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         bool miss = false;
         if (KIND == 0) {                                        // the word's smallest selected missing row
           const uint64_t mm = __ballot(on[j] && s0 < 0);
-          if (mm && lane == __builtin_ctzll(mm) && __atomic_load_n(&A.aux[1], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&A.aux[1], (unsigned long long)row);
+          if (mm && lane == __builtin_ctzll(mm) && __atomic_load_n(&A.aux->head.special_row[SPECIAL_MISSING], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&A.aux->head.special_row[SPECIAL_MISSING], (unsigned long long)row);
         }
         // (flat: every lane probes the cache — a lane that is off or holds a missing value probes with zeros and ignores the answer —, ONE predicated region does
         // the accumulation; nested `if`s cost an exec-mask save / branch / restore each, 80 scalar instructions per 64 rows before)
@@ -481,7 +479,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         if (r != kNoSlot && s0 <= kMetMaxLen) met.put(c1, c2, (uint32_t)s0, 1u, lane);
       } else {
         const uint64_t hs = (KIND == 2 || A.maybe) ? table_find_maybe(A.ent, A.mask, key, key & A.mask) : table_find(A.ent, A.mask, key, key & A.mask);
-        if (hs == kNoSlot) { __atomic_store_n(&A.aux[kAuxAbort], 1ull, __ATOMIC_RELAXED); continue; }   // a string the (optimistically filled) table does not hold: the host runs everything again
+        if (hs == kNoSlot) { __atomic_store_n(&A.aux->head.abort, 1ull, __ATOMIC_RELAXED); continue; }   // a string the (optimistically filled) table does not hold: the host runs everything again
         const bool same = !A.rep_off || same_bytes(p, s0, A.bytes + A.rep_off[hs], A.rep_len[hs]);
         if (!same) atomicOr(collision, 1);                      // two different strings, one key: the host repeats with another salt
         if (KIND == 2) {
@@ -517,7 +515,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 // mark the first occurrences row by row (many distinct values: the table's rows are compared with every selected row's own)
 __global__ __launch_bounds__(kBlock) void k_unique_str_mark(uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, const int32_t* __restrict__ sizes,
                                                             const int64_t* __restrict__ tile_off, const uint8_t* __restrict__ bytes, int64_t nrows, int64_t ntiles,
-                                                            const UniqueEntry* __restrict__ ent, uint64_t mask, const uint64_t* __restrict__ aux, uint64_t salt) {
+                                                            const UniqueEntry* __restrict__ ent, uint64_t mask, const UniqueAux* __restrict__ aux, uint64_t salt) {
   const int lane = lane_id();
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
@@ -536,7 +534,7 @@ __global__ __launch_bounds__(kBlock) void k_unique_str_mark(uint64_t* __restrict
       const uint64_t w = __shfl(mine, j, 64);
       bool first = false;
       if (row < nrows && ((w >> lane) & 1ull)) {
-        if (sz < 0) first = aux[1] == (uint64_t)row;
+        if (sz < 0) first = aux->head.special_row[SPECIAL_MISSING] == (uint64_t)row;
         else {
           const uint8_t* p = bytes + off;
           uint64_t key = hash_bytes(p, sz, salt, sz > 0 ? load8(p) : 0ull, sz > 8 ? load8(p + 8) : 0ull);
@@ -567,20 +565,20 @@ static int grid_str_pass(int64_t nt) {
   return (int)b;
 }
 
-void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, UniqueEntry* ent, uint64_t mask, uint64_t* aux) {
+void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, UniqueEntry* ent, uint64_t mask, UniqueAux* aux) {
   if (row1 <= row0) return;
   hipLaunchKernelGGL(k_unique_insert, dim3(grid_rows(row1 - row0)), dim3(kBlock), 0, s, bitmap, key.data, (int)key.dtype, key.missing, row0, row1, ent, mask, aux);
 }
-void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const ColRef& key, int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* aux) {
+void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const ColRef& key, int64_t nrows, const UniqueEntry* ent, uint64_t mask, const UniqueAux* aux) {
   if (nrows <= 0) return;
   const int64_t ntiles = (nrows + kTile - 1) / kTile;
   hipLaunchKernelGGL(k_unique_mark, dim3(grid_tiles(ntiles)), dim3(kBlock), 0, s, bitmap, tile_counts, key.data, (int)key.dtype, key.missing, nrows, ntiles, ent, mask, aux);
 }
 void launch_unique_migrate(hipStream_t s, const UniqueEntry* from, const uint64_t* from_off, const uint32_t* from_len, uint64_t from_cap, UniqueEntry* ent,
-                           uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, uint64_t* aux) {
+                           uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, UniqueAux* aux) {
   hipLaunchKernelGGL(k_unique_migrate, dim3(grid_rows((int64_t)from_cap)), dim3(kBlock), 0, s, from, from_off, from_len, from_cap, ent, rep_off, rep_len, mask, aux);
 }
-void launch_unique_scatter(hipStream_t s, const UniqueEntry* ent, uint64_t cap, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts) {
+void launch_unique_scatter(hipStream_t s, const UniqueEntry* ent, uint64_t cap, const UniqueAux* aux, uint64_t* bitmap, uint32_t* tile_counts) {
   hipLaunchKernelGGL(k_unique_scatter, dim3(grid_rows((int64_t)cap + 2)), dim3(kBlock), 0, s, ent, cap, aux, bitmap, tile_counts);
 }
 // the String passes' arguments: the key column and its table
@@ -676,9 +674,9 @@ __global__ __launch_bounds__(NG > kGroupLds ? 1024 : kBlock) void k_group_acc(co
       gid[k] = 0;
       if (!on[k]) continue;
       if (SRC == 1) gid[k] = A.rank_of_code[key[k]];
-      else if (miss[k]) gid[k] = A.special[1];
+      else if (miss[k]) gid[k] = A.special[SPECIAL_MISSING];
       else if (SRC == 2) gid[k] = A.gids[key[k] - A.lo];
-      else if (key[k] == kEmpty) gid[k] = A.special[0];
+      else if (key[k] == kEmpty) gid[k] = A.special[SPECIAL_UNSTORABLE];
       else gid[k] = table_row_maybe(A.ent, A.mask, key[k], slot_of(key[k], A.mask));      // (kEmpty: no slot — only an optimistically filled table can say that)
       // (no group: the key, `missing` or the unstorable key never turned up among the rows the table was made from — the host runs everything again)
       if (SRC == 0 && gid[k] >= (uint64_t)A.ngroups) { unknown = true; on[k] = false; }
@@ -839,7 +837,7 @@ __global__ __launch_bounds__(1024) void k_group_acc_hash_lds(const AccArgs A, co
   for (int g = threadIdx.x; g < A.ngroups; g += 1024) { lcnt[g] = 0; lval[g] = A.val_init; }
   for (uint32_t i = threadIdx.x; i < slots; i += 1024) lkey[i] = kEmpty;
   __syncthreads();
-  const uint64_t g_unstorable = A.special[0], g_missing = A.special[1];       // the groups of the key that cannot be stored / of `missing` (kEmpty: there is none)
+  const uint64_t g_unstorable = A.special[SPECIAL_UNSTORABLE], g_missing = A.special[SPECIAL_MISSING];       // the groups of the key that cannot be stored / of `missing` (kEmpty: there is none)
   for (int g = threadIdx.x; g < A.ngroups; g += 1024) {
     if ((uint64_t)g == g_unstorable || (uint64_t)g == g_missing) continue;     // (their first rows hold no key of the table)
     const uint64_t key = key_image(gkeys, A.keydt, g);
@@ -990,8 +988,6 @@ void launch_group_finish(hipStream_t s, uint64_t* val, int64_t ng, int kind, int
 constexpr int kDenseBlock = 1024;
 constexpr int kDenseWords = 39936;                                   // u32 words of LDS per workgroup (156 KB of the CU's 160)
 constexpr int64_t kDenseRange = (int64_t)kDenseWords * 32;
-constexpr int kAuxMissing = 1, kAuxOutside = 5, kAuxDistinct = 6, kAuxFound = 7, kAuxMin = 8, kAuxMax = 9, kAuxFoundBefore = 10;
-constexpr int kAuxSpanLo = 11, kAuxSpanHi = 12;            // smallest / largest value index with its presence bit set (k_dense_count): the span the keys really cover
 
 int64_t unique_dense_max_range() { return kDenseRange; }
 bool unique_dense_dtype(int dtype) {
@@ -1028,28 +1024,28 @@ __device__ __forceinline__ void walk_selected(const uint64_t* __restrict__ bitma
     }
   }
 }
-__device__ __forceinline__ void note_missing(uint64_t* aux, int64_t row) {
-  if (__atomic_load_n(&aux[kAuxMissing], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux[kAuxMissing], (unsigned long long)row);
+__device__ __forceinline__ void note_missing(UniqueAux* aux, int64_t row) {
+  if (__atomic_load_n(&aux->head.special_row[SPECIAL_MISSING], __ATOMIC_RELAXED) > (uint64_t)row) atomicMin((unsigned long long*)&aux->head.special_row[SPECIAL_MISSING], (unsigned long long)row);
 }
 __device__ __forceinline__ uint64_t wave_min64(uint64_t v) { for (int d = 32; d; d >>= 1) { const uint64_t o = __shfl_xor(v, d, 64); v = o < v ? o : v; } return v; }
 __device__ __forceinline__ uint64_t wave_max64(uint64_t v) { for (int d = 32; d; d >>= 1) { const uint64_t o = __shfl_xor(v, d, 64); v = o > v ? o : v; } return v; }
 
-// smallest and largest selected key as order-preserving images (signed: sign bit flipped) -> aux[kAuxMin], aux[kAuxMax]
+// smallest and largest selected key as order-preserving images (signed: sign bit flipped) -> aux->min_image, aux->max_image
 // (every tile_step-th tile: a sample)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_dense_minmax(const uint64_t* __restrict__ bitmap, const T* __restrict__ col, const uint64_t* __restrict__ missing,
-                                                         int64_t nrows, int64_t ntiles, int64_t tile_step, uint64_t* aux) {
+                                                         int64_t nrows, int64_t ntiles, int64_t tile_step, UniqueAux* aux) {
   const uint64_t flip = (T)-1 < (T)0 ? (1ull << 63) : 0ull;
   uint64_t lo = ~0ull, hi = 0ull;
   walk_selected<T>(bitmap, col, missing, nrows, 0, ntiles, ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * tile_step, (int64_t)gridDim.x * kWavesPerBlock * tile_step,
                    [&](uint64_t key, int64_t) { const uint64_t im = key ^ flip; lo = im < lo ? im : lo; hi = im > hi ? im : hi; }, [&](int64_t) {});
   lo = wave_min64(lo); hi = wave_max64(hi);
-  if (lane_id() == 0 && lo <= hi) { atomicMin((unsigned long long*)&aux[kAuxMin], (unsigned long long)lo); atomicMax((unsigned long long*)&aux[kAuxMax], (unsigned long long)hi); }
+  if (lane_id() == 0 && lo <= hi) { atomicMin((unsigned long long*)&aux->min_image, (unsigned long long)lo); atomicMax((unsigned long long*)&aux->max_image, (unsigned long long)hi); }
 }
 
 template <typename T>
 __global__ __launch_bounds__(kDenseBlock) void k_dense_presence(const uint64_t* __restrict__ bitmap, const T* __restrict__ col, const uint64_t* __restrict__ missing,
-                                                                int64_t nrows, int64_t ntiles, uint64_t lo, uint32_t range, uint32_t* __restrict__ present, uint64_t* aux) {
+                                                                int64_t nrows, int64_t ntiles, uint64_t lo, uint32_t range, uint32_t* __restrict__ present, UniqueAux* aux) {
   __shared__ uint32_t bits[kDenseWords];
   const int words = (int)((range + 31u) >> 5);
   for (int i = threadIdx.x; i < words; i += kDenseBlock) bits[i] = 0;
@@ -1064,11 +1060,11 @@ __global__ __launch_bounds__(kDenseBlock) void k_dense_presence(const uint64_t* 
                      else outside = true;
                    },
                    [&](int64_t row) { note_missing(aux, row); });
-  if (outside) __atomic_store_n(&aux[kAuxOutside], 1ull, __ATOMIC_RELAXED);
+  if (outside) __atomic_store_n(&aux->outside, 1ull, __ATOMIC_RELAXED);
   __syncthreads();
   for (int i = threadIdx.x; i < words; i += kDenseBlock) { const uint32_t b = bits[i]; if (b) atomicOr(&present[i], b); }
 }
-__global__ __launch_bounds__(kBlock) void k_dense_count(const uint32_t* __restrict__ present, int words, uint64_t* aux) {
+__global__ __launch_bounds__(kBlock) void k_dense_count(const uint32_t* __restrict__ present, int words, UniqueAux* aux) {
   uint32_t n = 0, lo = 0xFFFFFFFFu, hi = 0;
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < words; i += gridDim.x * kBlock) {
     const uint32_t b = present[i];
@@ -1076,8 +1072,8 @@ __global__ __launch_bounds__(kBlock) void k_dense_count(const uint32_t* __restri
   }
   for (int d = 32; d; d >>= 1) { n += __shfl_xor(n, d, 64); lo = min(lo, (uint32_t)__shfl_xor(lo, d, 64)); hi = max(hi, (uint32_t)__shfl_xor(hi, d, 64)); }
   if (lane_id() == 0 && n) {
-    atomicAdd((unsigned long long*)&aux[kAuxDistinct], (unsigned long long)n);
-    atomicMin((unsigned long long*)&aux[kAuxSpanLo], (unsigned long long)lo); atomicMax((unsigned long long*)&aux[kAuxSpanHi], (unsigned long long)hi);
+    atomicAdd((unsigned long long*)&aux->distinct, (unsigned long long)n);
+    atomicMin((unsigned long long*)&aux->span_lo, (unsigned long long)lo); atomicMax((unsigned long long*)&aux->span_hi, (unsigned long long)hi);
   }
 }
 
@@ -1085,12 +1081,12 @@ __global__ __launch_bounds__(kBlock) void k_dense_count(const uint32_t* __restri
 // every one of them waited for the one before, ~30 us per tile, and the launches that find the first rows are a few tiles per wave)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_dense_first(const uint64_t* __restrict__ bitmap, const T* __restrict__ col, const uint64_t* __restrict__ missing,
-                                                        int64_t nrows, int64_t tile0, int64_t tile1, uint64_t lo, uint32_t range, uint64_t distinct, uint64_t* first, uint64_t* aux) {
-  // every value's first row lies in an EARLIER launch?  The test reads kAuxFoundBefore — kAuxFound as the launches before this one left it (k_dense_snap copies it
+                                                        int64_t nrows, int64_t tile0, int64_t tile1, uint64_t lo, uint32_t range, uint64_t distinct, uint64_t* first, UniqueAux* aux) {
+  // every value's first row lies in an EARLIER launch?  The test reads found_before — `found` as the launches before this one left it (k_dense_snap copies it
   // between two launches of the row-ordered series) — never the live counter: workgroups of THIS launch add to that as they finish, a workgroup that starts
   // late could see found == distinct and skip its tiles although they hold an earlier row of a value a sibling has just found in a later tile (first[value]
   // would then not be the smallest row, and unique's order with it).  `distinct` comes from the host, which read it after the presence pass.
-  if (aux[kAuxFoundBefore] >= distinct) return;
+  if (aux->found_before >= distinct) return;
   const int lane = lane_id();
   const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * kWavesPerBlock;
   uint32_t fresh = 0;
@@ -1125,28 +1121,28 @@ __global__ __launch_bounds__(kBlock) void k_dense_first(const uint64_t* __restri
     for (int j = 0; j < 16; j++) fresh += (uint32_t)(old[j] == kEmpty);
   }
   for (int d = 32; d; d >>= 1) fresh += __shfl_xor(fresh, d, 64);
-  if (lane == 0 && fresh) atomicAdd((unsigned long long*)&aux[kAuxFound], (unsigned long long)fresh);
+  if (lane == 0 && fresh) atomicAdd((unsigned long long*)&aux->found, (unsigned long long)fresh);
 }
 
-__global__ void k_dense_snap(uint64_t* aux) { aux[kAuxFoundBefore] = aux[kAuxFound]; }
+__global__ void k_dense_snap(UniqueAux* aux) { aux->found_before = aux->found; }
 
-__global__ __launch_bounds__(kBlock) void k_dense_scatter(const uint64_t* __restrict__ first, uint32_t range, const uint64_t* __restrict__ aux,
+__global__ __launch_bounds__(kBlock) void k_dense_scatter(const uint64_t* __restrict__ first, uint32_t range, const UniqueAux* __restrict__ aux,
                                                           uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i > range) return;
-  const uint64_t r = i < range ? first[i] : aux[kAuxMissing];
+  const uint64_t r = i < range ? first[i] : aux->head.special_row[SPECIAL_MISSING];
   if (r == kEmpty) return;
   atomicOr((unsigned long long*)&bitmap[r >> 6], 1ull << (r & 63));
   atomicAdd(&tile_counts[r >> 10], 1u);
 }
-__global__ __launch_bounds__(kBlock) void k_dense_group_ids(uint64_t* __restrict__ first, uint32_t range, uint64_t* __restrict__ aux,
+__global__ __launch_bounds__(kBlock) void k_dense_group_ids(uint64_t* __restrict__ first, uint32_t range, UniqueAux* __restrict__ aux,
                                                             const uint64_t* __restrict__ ubits, const uint64_t* __restrict__ uprefix) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < range) { if (first[i] != kEmpty) first[i] = rank_of_row(ubits, uprefix, first[i]); }
-  else if (i == range && aux[kAuxMissing] != kEmpty) aux[kAuxMissing] = rank_of_row(ubits, uprefix, aux[kAuxMissing]);
+  else if (i == range && aux->head.special_row[SPECIAL_MISSING] != kEmpty) aux->head.special_row[SPECIAL_MISSING] = rank_of_row(ubits, uprefix, aux->head.special_row[SPECIAL_MISSING]);
 }
 
-void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, int64_t tile_step, uint64_t* aux) {
+void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, int64_t tile_step, UniqueAux* aux) {
   if (nrows <= 0) return;
   const int64_t ntiles = (nrows + kTile - 1) / kTile, visited = (ntiles + tile_step - 1) / tile_step;
   const dim3 g(grid_tiles(visited) > 2048 ? 2048 : grid_tiles(visited)), b(kBlock);
@@ -1155,7 +1151,7 @@ void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& ke
     hipLaunchKernelGGL((k_dense_minmax<T>), g, b, 0, s, bitmap, (const T*)key.data, key.missing, nrows, ntiles, tile_step, aux);
   });
 }
-void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, uint64_t lo, uint32_t range, uint32_t* present, uint64_t* aux) {
+void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, uint64_t lo, uint32_t range, uint32_t* present, UniqueAux* aux) {
   if (nrows <= 0) return;
   const int64_t ntiles = (nrows + kTile - 1) / kTile;
   int64_t nb = (ntiles + kDenseBlock / 64 - 1) / (kDenseBlock / 64); if (nb > 256) nb = 256;      // one workgroup per CU: its LDS is the whole CU's
@@ -1168,7 +1164,7 @@ void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const ColRef& 
   hipLaunchKernelGGL(k_dense_count, dim3((words + kBlock - 1) / kBlock > 64 ? 64 : (words + kBlock - 1) / kBlock), dim3(kBlock), 0, s, present, words, aux);
 }
 void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, uint64_t lo, uint32_t range, uint64_t distinct,
-                        uint64_t* first, uint64_t* aux) {
+                        uint64_t* first, UniqueAux* aux) {
   if (row1 <= row0) return;
   const int64_t tile0 = row0 / kTile, tile1 = (row1 + kTile - 1) / kTile;
   const dim3 g(grid_tiles(tile1 - tile0) > 2048 ? 2048 : grid_tiles(tile1 - tile0)), b(kBlock);
@@ -1178,10 +1174,10 @@ void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const ColRef& key
     hipLaunchKernelGGL((k_dense_first<T>), g, b, 0, s, bitmap, (const T*)key.data, key.missing, row1, tile0, tile1, lo, range, distinct, first, aux);
   });
 }
-void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts) {
+void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, const UniqueAux* aux, uint64_t* bitmap, uint32_t* tile_counts) {
   hipLaunchKernelGGL(k_dense_scatter, dim3((range + 1 + kBlock) / kBlock), dim3(kBlock), 0, s, first, range, aux, bitmap, tile_counts);
 }
-void launch_dense_group_ids(hipStream_t s, uint64_t* first, uint32_t range, uint64_t* aux, const uint64_t* ubits, const uint64_t* uprefix) {
+void launch_dense_group_ids(hipStream_t s, uint64_t* first, uint32_t range, UniqueAux* aux, const uint64_t* ubits, const uint64_t* uprefix) {
   hipLaunchKernelGGL(k_dense_group_ids, dim3((range + 1 + kBlock) / kBlock), dim3(kBlock), 0, s, first, range, aux, ubits, uprefix);
 }
 // The dense form with its group-number table IN LDS (round 5): per row the pass looked its key's group up in `gids` — a random 8-byte load per lane, 64 different lines
@@ -1195,7 +1191,7 @@ __global__ __launch_bounds__(1024) void k_group_acc_dense_lds(const AccArgs A, u
   constexpr bool has_val = OPK != 0;
   for (int g = threadIdx.x; g < A.ngroups; g += 1024) { lcnt[g] = 0; lval[g] = A.val_init; }
   for (uint32_t i = threadIdx.x; i < range; i += 1024) tbl[i] = (uint32_t)A.gids[i];
-  if (threadIdx.x == 0) tbl[range] = (uint32_t)A.special[1];
+  if (threadIdx.x == 0) tbl[range] = (uint32_t)A.special[SPECIAL_MISSING];
   __syncthreads();
   // every load of a trip is issued before any of them is looked at: the selection word, the key and the value of a row do not wait for each other (a key loaded only
   // where the selection bit is set costs a second dependent round trip per trip: the counters showed waves waiting 89 % of their cycles with ~37 lines in flight per CU)
@@ -1276,7 +1272,7 @@ __device__ __forceinline__ void rank_emit(const RankArgs& A, int64_t row, uint64
   if (r >= A.n) { bad = true; return; }
   if (A.img_out) A.img_out[row] = (uint64_t)gp * A.n + r; else A.g_out[row] = (uint32_t)r;
 }
-// SRC 0: the hash table (special: unique's aux — [0] the group of the unstorable key, [1] of missing), 1: dictionary codes, 2: the dense form's table, 3: the same
+// SRC 0: the hash table (special: KeyAux::special_row of unique's aux — the groups of the unstorable key and of missing), 1: dictionary codes, 2: the dense form's table, 3: the same
 // table copied into LDS first (a range of at most kRankLdsRange values: the lookup is a ds_read, not a random 8-byte load per row — that load made the pass
 // 6.0 ms at 1e9 rows by 5000 keys)
 constexpr uint32_t kRankLdsRange = 16000;           // (+1 for missing: under 64 KB of static LDS)
@@ -1285,7 +1281,7 @@ __global__ __launch_bounds__(kBlock) void k_group_rank(const RankArgs A) {
   __shared__ uint32_t ltab[SRC == 3 ? kRankLdsRange + 1 : 1];
   if (SRC == 3) {
     for (uint32_t i = threadIdx.x; i < A.range; i += kBlock) { const uint64_t v = A.gids[i]; ltab[i] = v < 0xFFFFFFFFull ? (uint32_t)v : 0xFFFFFFFFu; }
-    if (threadIdx.x == 0) { const uint64_t v = A.special[1]; ltab[A.range] = v < 0xFFFFFFFFull ? (uint32_t)v : 0xFFFFFFFFu; }
+    if (threadIdx.x == 0) { const uint64_t v = A.special[SPECIAL_MISSING]; ltab[A.range] = v < 0xFFFFFFFFull ? (uint32_t)v : 0xFFFFFFFFu; }
     __syncthreads();
   }
   constexpr int U = 4;                                          // (every load of a trip before any is used, as in k_group_acc)
@@ -1311,9 +1307,9 @@ __global__ __launch_bounds__(kBlock) void k_group_rank(const RankArgs A) {
       uint64_t r;
       if (SRC == 1) r = A.rank_of_code[key[k]];
       else if (SRC == 3) { const uint64_t i = key[k] - A.lo; r = miss ? (uint64_t)ltab[A.range] : (i < (uint64_t)A.range ? (uint64_t)ltab[i] : kEmpty); if (r == 0xFFFFFFFFull) r = kEmpty; }
-      else if (miss) r = A.special[1];
+      else if (miss) r = A.special[SPECIAL_MISSING];
       else if (SRC == 2) r = key[k] - A.lo < (uint64_t)A.range ? A.gids[key[k] - A.lo] : kEmpty;
-      else if (key[k] == kEmpty) r = A.special[0];
+      else if (key[k] == kEmpty) r = A.special[SPECIAL_UNSTORABLE];
       else r = table_row_maybe(A.ent, A.mask, key[k], slot_of(key[k], A.mask));
       rank_emit(A, row, r, gp[k], bad);
     }
@@ -1341,7 +1337,7 @@ __global__ __launch_bounds__(kBlock) void k_group_rank_str(const RankArgs A, con
       const uint64_t w = __shfl(mine, j, 64);
       if (row < A.nrows && ((w >> lane) & 1ull)) {
         uint64_t r;
-        if (sz < 0) r = A.special[1];
+        if (sz < 0) r = A.special[SPECIAL_MISSING];
         else {
           const uint8_t* p = bytes + off;
           uint64_t key = hash_bytes(p, sz, salt, sz > 0 ? load8(p) : 0ull, sz > 8 ? load8(p + 8) : 0ull);

@@ -2,6 +2,7 @@
 // Every launcher enqueues on `s` and returns immediately; none allocates or synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 #include "../../include/dfdb.h"
 
@@ -189,18 +190,59 @@ void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* t
 int select_key_bits(int dtype, bool full);
 uint64_t select_key_value(int dtype, bool full, uint64_t key);      // a finished key -> the value's 64 accumulator bits (integers widened, floats as Float64)
 
-// ---- unique(col) as a selection of first occurrences (k_unique.hip: hash table of {key, smallest row}; k_unique_dense.hip: integer keys of a small range)
+// ---- the control words of unique / groupreduce: 128 bytes of device memory through which the kernels of k_unique.hip and k_radix.hip report to the host, which
+// reads every retry decision from them.  The host sets them with device memsets (all zero, then all ones where a field says so) and reads them back whole.
+// KeyAux is the head every form shares — all the radix kernels and the `special` pointers of AccArgs / RankArgs see —, UniqueAux what unique's table and dense
+// forms lay behind it, RadixGroupAux what groupreduce by radix lays there instead.  The static_asserts below are the layout.
+enum SpecialRow : int { SPECIAL_UNSTORABLE = 0, SPECIAL_MISSING = 1 };
+struct KeyAux {
+  // the two keys no table holds: [SPECIAL_UNSTORABLE] the key whose image is all ones (the tables' "empty"), [SPECIAL_MISSING] the missing key.  All ones before
+  // a pass: no such row; the insert / presence / partition passes lower a word (atomicMin) to the smallest selected row that holds the key; the group-number
+  // kernels (k_group_ids, k_dense_group_ids) then replace a row by its group's number, which is what AccArgs::special / RankArgs::special read
+  uint64_t special_row[2];
+  uint64_t claims;      // hash table: the slots claimed since the host last cleared it (every reset; before a migration, which counts them again).  Zero for the other forms
+  // raised (1) by a pass that cannot finish with the table it was given, cleared by the host before every pass that may raise it: an insert whose probe sequence got too
+  // long (the host grows the table and repeats the chunk), a partition that outgrew its pages or its LDS table (the host falls back to the hash table), and — as
+  // AccArgs::unknown_flag, or String pass 3 — a selected row whose key the table, filled from a prefix of the rows only, does not hold (everything again over every row)
+  uint64_t abort;
+};
+struct UniqueAux {
+  KeyAux head;
+  uint64_t collision;     // String keys: two different strings shared a key (the host: again under the next salt).  An int: the String pass raises the low 32 bits through an int*.  Cleared by the reset only
+  // the dense form (integer keys of a small range), zero after the reset unless said otherwise:
+  uint64_t outside;       // k_dense_presence: a selected key lies outside [lo, lo + range)
+  uint64_t distinct;      // k_dense_count: the presence bits set
+  uint64_t found;         // k_dense_first: the values whose first row is known
+  uint64_t min_image;     // k_dense_minmax: the smallest selected key as an order-preserving image (all ones after the reset) ...
+  uint64_t max_image;     // ... and the largest
+  uint64_t found_before;  // k_dense_snap: `found` as the launches before the current k_dense_first left it
+  uint64_t span_lo;       // k_dense_count: the smallest value index whose presence bit is set (all ones after the reset) ...
+  uint64_t span_hi;       // ... and the largest
+  uint64_t reserved[3];
+};
+struct RadixGroupAux {
+  KeyAux head;            // (claims stays zero)
+  uint64_t gspec[4];      // {rows, value} of the unstorable key's group, then of the missing key's: added up by the partition pass (a minimum starts at all ones), read by the finish
+  uint64_t nres;          // the results the table pass wrote; the kernels use the low 32 bits
+  uint64_t reserved[7];
+};
+static_assert(sizeof(KeyAux) == 32 && offsetof(KeyAux, special_row) == 0 && offsetof(KeyAux, claims) == 16 && offsetof(KeyAux, abort) == 24, "words 0-3");
+static_assert(sizeof(UniqueAux) == 128 && offsetof(UniqueAux, head) == 0 && offsetof(UniqueAux, collision) == 32 && offsetof(UniqueAux, outside) == 40 &&
+              offsetof(UniqueAux, distinct) == 48 && offsetof(UniqueAux, found) == 56 && offsetof(UniqueAux, min_image) == 64 && offsetof(UniqueAux, max_image) == 72 &&
+              offsetof(UniqueAux, found_before) == 80 && offsetof(UniqueAux, span_lo) == 88 && offsetof(UniqueAux, span_hi) == 96, "words 4-12");
+static_assert(sizeof(RadixGroupAux) == 128 && offsetof(RadixGroupAux, head) == 0 && offsetof(RadixGroupAux, gspec) == 32 && offsetof(RadixGroupAux, nres) == 64, "words 4-8");
+
+// ---- unique(col) as a selection of first occurrences (k_unique.hip: a hash table of {key, smallest row}, or — integer keys of a small range — the dense form)
 struct UniqueEntry { uint64_t key, row; };
-void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, UniqueEntry* ent, uint64_t mask, uint64_t* aux);
-void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const ColRef& key, int64_t nrows, const UniqueEntry* ent, uint64_t mask, const uint64_t* aux);
+void launch_unique_insert(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, UniqueEntry* ent, uint64_t mask, UniqueAux* aux);
+void launch_unique_mark(hipStream_t s, uint64_t* bitmap, uint32_t* tile_counts, const ColRef& key, int64_t nrows, const UniqueEntry* ent, uint64_t mask, const UniqueAux* aux);
 void launch_unique_migrate(hipStream_t s, const UniqueEntry* from, const uint64_t* from_off, const uint32_t* from_len, uint64_t from_cap, UniqueEntry* ent,
-                           uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, uint64_t* aux);
-void launch_unique_scatter(hipStream_t s, const UniqueEntry* ent, uint64_t cap, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts);
+                           uint64_t* rep_off, uint32_t* rep_len, uint64_t mask, UniqueAux* aux);
+void launch_unique_scatter(hipStream_t s, const UniqueEntry* ent, uint64_t cap, const UniqueAux* aux, uint64_t* bitmap, uint32_t* tile_counts);
 // the hash table of a flat String key: a slot's key is the salted hash of the string, rep_off / rep_len say where one holder's bytes lie (the representative)
-struct StrTable { UniqueEntry* ent; uint64_t* rep_off; uint32_t* rep_len; uint64_t mask; uint64_t* aux; uint64_t salt; };
+struct StrTable { UniqueEntry* ent; uint64_t* rep_off; uint32_t* rep_len; uint64_t mask; UniqueAux* aux; uint64_t salt; };
 // pass 0: insert the tiles [tile0, tile1), 1: verify (3: the table may not hold every string), 2: mark
 void launch_unique_str(hipStream_t s, int pass, uint64_t* bitmap, uint32_t* tile_counts, const StrSide& key, int64_t nrows, int64_t tile0, int64_t tile1, const StrTable& tab);
-// dense form.  aux words: 1 = smallest missing row, 5 = a key outside [lo, lo + range) was met, 6 = distinct keys, 7 = keys whose first row is known, 8 / 9 = min / max image
 // radix-partitioned form of the hash-table unique (k_radix.hip): partition into a pool of pages -> one LDS table per partition.  false: the launch is
 // not possible or refused (LDS attribute refused, too many partition bits, a launch error): the caller stays with the hash table.  The pool: `front` [2^kbits x radix_share()] running
 // positions of the streams (zero before the pass), `pt` [2^kbits x radix_share()][maxv] the streams' pages (all ones before the pass), `next_page` the pool's
@@ -217,24 +259,23 @@ uint32_t radix_pool_maxv(int64_t cnt, int kbits);
 bool launch_radix_sample(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, int step, uint32_t* counts /* [2^kbits], zero before */);
 // groupreduce by radix: the records carry the row's 8-byte value (val; no column: count only); gop 0 count only, 1 wrapping integer sum, 2 double sum, 3 min, 4 max
 // (of order images: vkind 0 signed, 1 unsigned, 2 double); results [<= groups] {first row, rows, value} + their count nres; gspec {rows, value} of the unstorable key
-// and of the missing key (their first rows: aux[0], aux[1])
-struct RadixGroup { ColRef val; int gop; int vkind; void* results; uint32_t* nres; uint64_t* gspec /* [4]: the unstorable key's, the missing key's */; };
+// and of the missing key (their first rows: the head's special_row), both in `aux`
+struct RadixGroup { ColRef val; int gop; int vkind; void* results; RadixGroupAux* aux; };
 int radix_hot_slots();
-bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, const RadixPool& pool, uint32_t* recs_out /* 12 bytes per record: key image, row; with a group: 20, + the value */, uint64_t* aux,
+bool launch_radix_partition(hipStream_t s, const uint64_t* sel, const ColRef& key, int64_t nrows, const RadixGrid& grid, const RadixPool& pool, uint32_t* recs_out /* 12 bytes per record: key image, row; with a group: 20, + the value */, KeyAux* aux /* with a group: its aux's head */,
                             const RadixGroup* group = nullptr, bool hot = false /* the kernels that keep hot keys out of the records (values narrower than 8 bytes: always) */);
-bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux,
-                        const RadixGroup& group, int cus);
-void launch_radix_group_finish(hipStream_t s, const RadixGroup& group, const uint64_t* ubits, const uint64_t* uprefix, const uint64_t* aux, uint64_t* cnt, uint64_t* val);
-bool launch_radix_unique(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, uint64_t* bitmap, uint32_t* tile_counts, uint64_t* aux, int cus);
+bool launch_radix_group(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, bool mark, uint64_t* bitmap, uint32_t* tile_counts, const RadixGroup& group, int cus);
+void launch_radix_group_finish(hipStream_t s, const RadixGroup& group, const uint64_t* ubits, const uint64_t* uprefix, uint64_t* cnt, uint64_t* val);
+bool launch_radix_unique(hipStream_t s, const uint32_t* recs, const RadixPool& pool, int kbits, uint64_t* bitmap, uint32_t* tile_counts, KeyAux* aux, int cus);
 int64_t unique_dense_max_range();
 bool unique_dense_dtype(int dtype);
-void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, int64_t tile_step, uint64_t* aux);
+void launch_dense_minmax(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, int64_t tile_step, UniqueAux* aux);
 void launch_dense_presence(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t nrows, uint64_t lo, uint32_t range,
-                           uint32_t* present, uint64_t* aux);
+                           uint32_t* present, UniqueAux* aux);
 void launch_dense_first(hipStream_t s, const uint64_t* bitmap, const ColRef& key, int64_t row0, int64_t row1, uint64_t lo,
-                        uint32_t range, uint64_t distinct, uint64_t* first, uint64_t* aux);
-void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, const uint64_t* aux, uint64_t* bitmap, uint32_t* tile_counts);
-void launch_dense_group_ids(hipStream_t s, uint64_t* first, uint32_t range, uint64_t* aux, const uint64_t* ubits, const uint64_t* uprefix);
+                        uint32_t range, uint64_t distinct, uint64_t* first, UniqueAux* aux);
+void launch_dense_scatter(hipStream_t s, const uint64_t* first, uint32_t range, const UniqueAux* aux, uint64_t* bitmap, uint32_t* tile_counts);
+void launch_dense_group_ids(hipStream_t s, uint64_t* first, uint32_t range, UniqueAux* aux, const uint64_t* ubits, const uint64_t* uprefix);
 // K9 (dictionary codes) and groupreduce's group numbers, accumulate passes and finish (k_unique.hip)
 void launch_dict_first_rows(hipStream_t s, const uint64_t* sel, const uint16_t* codes, int64_t nrows, uint64_t* first, int dict_n, int64_t tile0, int64_t tile1);
 void launch_set_rows(hipStream_t s, const uint64_t* rows, int n, uint64_t* bitmap, uint32_t* tile_counts);
@@ -243,11 +284,11 @@ void launch_group_ids(hipStream_t s, UniqueEntry* ent, uint64_t cap, uint64_t* s
 // layout is theirs); `src` says which table numbers the groups and which fields beside the common ones are read
 struct AccArgs {
   const uint64_t* sel; const void* keycol; int keydt; const uint64_t* missing; const void* valcol; int valdt, op; int64_t nrows;
-  const UniqueEntry* ent; uint64_t mask; const uint64_t* special;       // SRC 0 (special: aux — the groups of the unstorable key and of missing)
+  const UniqueEntry* ent; uint64_t mask; const uint64_t* special;       // SRC 0 (special: KeyAux::special_row — the groups of the unstorable key and of missing)
   const uint16_t* codes; const uint32_t* rank_of_code;                  // SRC 1
-  uint64_t lo; const uint64_t* gids;                                    // SRC 2 (special[1]: the group of missing)
+  uint64_t lo; const uint64_t* gids;                                    // SRC 2 (special[SPECIAL_MISSING]: the group of missing)
   uint64_t* cnt; uint64_t* val; int ngroups; uint64_t val_init;
-  uint64_t* unknown_flag;                                               // the LDS forms: raised by a selected row whose key has no group (an optimistic / head-only table)
+  uint64_t* unknown_flag;                                               // (KeyAux::abort) the LDS forms: raised by a selected row whose key has no group (an optimistic / head-only table)
   void key(const ColRef& k) { keycol = k.data; keydt = k.dtype; missing = k.missing; }
   void value(const ColRef& v) { valcol = v.data; valdt = v.dtype; }
 };
@@ -262,7 +303,7 @@ int launch_group_accumulate(hipStream_t s, GroupSrc src, const AccArgs& A, const
 void launch_group_accumulate_str(hipStream_t s, const AccArgs& A, const StrSide& key, const StrTable& tab);
 void launch_group_finish(hipStream_t s, uint64_t* val, int64_t ng, int kind, int op);
 // groupreduce by a tuple of keys (dfdb_query_groupreduce_n): per selected row of `sel`, the rank of its key out of one of the tables above -> g_out (gprev null)
-// or image = gprev[row] * n + rank -> img_out; a rank >= n raises *flag.  src 0: hash table (special = unique's aux), 1: dictionary codes, 2: the dense form (its table in LDS when the range is small)
+// or image = gprev[row] * n + rank -> img_out; a rank >= n raises *flag.  src 0: hash table (special = KeyAux::special_row of unique's aux), 1: dictionary codes, 2: the dense form (its table in LDS when the range is small)
 struct RankArgs {
   const uint64_t* sel; const void* keycol; int keydt; const uint64_t* missing; int64_t nrows;
   const UniqueEntry* ent; uint64_t mask; const uint64_t* special;

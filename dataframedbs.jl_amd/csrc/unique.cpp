@@ -15,24 +15,42 @@ constexpr int64_t kGroupsInLds = 9216;      // groups a workgroup's LDS accumula
 // what unique leaves behind for groupreduce: the hash table {key, first row} (Strings: + where one holder's bytes are), or — integer keys of a small
 // range — the first row per value; groupreduce turns the rows into group numbers in place
 struct UniqueTables {
-  DevBuf ent, aux, rep_off, rep_len, first, present;
+  DevBuf ent, aux, rep_off, rep_len, first, present;     // (aux: the control words, a UniqueAux — kernels.hpp)
   uint64_t cap = 0, salt = 0, lo = 0; uint32_t range = 0; bool is_str = false, dense = false;
   uint64_t span_lo = ~0ull, span_hi = 0;   // dense form: the first / last value index that is present (the table is laid out for the widest span it can hold)
-  // in: the dense form may look at the HEAD of the column only (groupreduce over integer keys, round 5: its accumulate pass meets every row anyway and reports a key
-  // that has no group — one outside the span laid out, or one that first turns up behind the head —, in which case everything runs again over all rows); out: it did
-  bool allow_head = false, head_only = false;
-  bool defer_verify = false;     // in: the caller's own pass over the rows compares every String with its slot's representative (groupreduce's accumulate pass)
-  int salt_skip = 0;             // in: salts already found colliding
-  // in: String keys with defer_verify — if the second insert chunk (16 M rows) met no string the first (1 M rows) had not, the rest of the rows are NOT
-  // inserted: the caller's pass meets every row anyway and reports a string that is not in the table (`optimistic` comes back true; the caller then
-  // runs everything again with allow_optimistic = false).  Ten brands over 5e8 rows: the insert pass 2.2 -> 0.1 ms.
-  bool allow_optimistic = false, optimistic = false;
-  // in: the caller can reduce by radix (group_radix: more groups than LDS accumulators hold) and wants to know EARLY whether that is the case; out: the number of
-  // distinct keys the first chunk's rows promise when it is more than 9216 — and then nothing else was done: the selection is as it was, no table was finished
-  bool group_probe = false; int64_t group_estimate = 0;
-  bool allow_radix = true;       // in: the radix form of unique may take the job (it leaves no table to look keys up in: groupreduce_n's rank pass says no)
+  bool head_only = false;        // the dense form looked at the head of the column only (UniqueRequest::allow_head)
+  bool optimistic = false;       // the rows behind the second insert chunk were not inserted (UniqueRequest::allow_optimistic)
+  // UniqueRequest::group_probe: the number of distinct keys the first chunk's rows promise when it is more than 9216 — and then nothing else was done: the
+  // selection is as it was, no table was finished
+  int64_t group_estimate = 0;
+  UniqueAux* ctl() const { return aux.as<UniqueAux>(); }
 };
-static StrTable str_table(const UniqueTables& T) { return StrTable{T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.aux.as<uint64_t>(), T.salt}; }
+// what the caller of unique asks for (all off: a complete, verified table — or no table at all, where the radix form took the job)
+struct UniqueRequest {
+  // the dense form may look at the HEAD of the column only (groupreduce over integer keys, round 5: its accumulate pass meets every row anyway and reports a key
+  // that has no group — one outside the span laid out, or one that first turns up behind the head —, in which case everything runs again over all rows)
+  bool allow_head = false;
+  bool defer_verify = false;     // the caller's own pass over the rows compares every String with its slot's representative (groupreduce's accumulate pass)
+  // String keys, or defer_verify — if the second insert chunk (16 M rows) met no string the first (1 M rows) had not, the rest of the rows are NOT inserted: a
+  // later pass meets every row anyway and reports a string that is not in the table (UniqueTables::optimistic comes back true; unique's own verify pass then
+  // inserts every row, a caller with defer_verify asks again without this).  Ten brands over 5e8 rows: the insert pass 2.2 -> 0.1 ms.
+  bool allow_optimistic = false;
+  // the caller can reduce by radix (group_radix: more groups than LDS accumulators hold) and wants to know EARLY whether that is the case (UniqueTables::group_estimate)
+  bool group_probe = false;
+  bool allow_radix = true;       // the radix form of unique may take the job (it leaves no table to look keys up in: groupreduce_n's rank pass says no)
+  int salt_skip = 0;             // salts already found colliding
+};
+static StrTable str_table(const UniqueTables& T) { return StrTable{T.ent.as<UniqueEntry>(), T.rep_off.as<uint64_t>(), T.rep_len.as<uint32_t>(), T.cap - 1, T.ctl(), T.salt}; }
+// a control record (UniqueAux, RadixGroupAux) off the device, whole: fetch_aux enqueues the copy, read_aux also waits for it
+template <typename Aux> static void fetch_aux(dfdb_ctx* ctx, const Aux* dev, Aux* host) { HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(Aux), hipMemcpyDeviceToHost, ctx->stream)); }
+template <typename Aux> static Aux read_aux(dfdb_ctx* ctx, const Aux* dev) { Aux h; fetch_aux(ctx, dev, &h); stream_wait(ctx); return h; }
+// before a pass that may raise it
+static void clear_abort(dfdb_ctx* ctx, KeyAux* head) { HIP_CHECK(hipMemsetAsync(&head->abort, 0, sizeof head->abort, ctx->stream)); }
+// before a migration, which counts the claims again: the claims and the abort word, which lie side by side, in one memset
+static void clear_claims_and_abort(dfdb_ctx* ctx, KeyAux* head) {
+  static_assert(offsetof(KeyAux, abort) == offsetof(KeyAux, claims) + sizeof head->claims, "one memset covers both");
+  HIP_CHECK(hipMemsetAsync(&head->claims, 0, sizeof head->claims + sizeof head->abort, ctx->stream));
+}
 // K9: unique over a String column that has a dictionary — the first selected row of every code, no hash table.  Leaves what unique_impl leaves (the
 // bitmap holds exactly the first occurrences, prefix scanned); rank_of_code (optional) maps a code to its group number in order of first appearance.
 static int64_t dict_unique(dfdb_query* q, const Column& col, DevBuf* rank_of_code) {
@@ -74,14 +92,14 @@ static int64_t dict_unique(dfdb_query* q, const Column& col, DevBuf* rank_of_cod
   stream_wait(ctx);                                        // rows / rank are pageable host memory
   return ng;
 }
-constexpr size_t kUniqueAuxBytes = 128;      // k_unique.hip: 0 first row of the key that cannot be stored, 1 first missing row, 2 claimed slots, 3 abort, 4 collision, 5-10 the dense form's (10: found-before snapshot)
-static void unique_reset_aux(dfdb_ctx* ctx, DevBuf& aux) {
+static void unique_reset_aux(dfdb_ctx* ctx, DevBuf& buf) {
   hipStream_t s = ctx->stream;
-  aux.ensure(kUniqueAuxBytes);
-  HIP_CHECK(hipMemsetAsync(aux.p, 0, kUniqueAuxBytes, s));
-  HIP_CHECK(hipMemsetAsync(aux.p, 0xFF, 16, s));                       // no such row yet
-  HIP_CHECK(hipMemsetAsync((char*)aux.p + 64, 0xFF, 8, s));            // the running minimum (k_dense_minmax)
-  HIP_CHECK(hipMemsetAsync((char*)aux.p + 88, 0xFF, 8, s));            // the smallest present value index (k_dense_count)
+  buf.ensure(sizeof(UniqueAux));
+  UniqueAux* aux = buf.as<UniqueAux>();
+  HIP_CHECK(hipMemsetAsync(aux, 0, sizeof(UniqueAux), s));
+  HIP_CHECK(hipMemsetAsync(aux->head.special_row, 0xFF, sizeof aux->head.special_row, s));      // no such row yet
+  HIP_CHECK(hipMemsetAsync(&aux->min_image, 0xFF, sizeof aux->min_image, s));                   // the running minimum (k_dense_minmax)
+  HIP_CHECK(hipMemsetAsync(&aux->span_lo, 0xFF, sizeof aux->span_lo, s));                       // the smallest present value index (k_dense_count)
 }
 static uint64_t pow2_at_least(uint64_t n) { uint64_t c = 1024; while (c < n) c <<= 1; return c; }
 
@@ -103,22 +121,22 @@ static uint64_t unique_capacity_wanted(uint64_t d, uint64_t r, uint64_t remainin
 }
 
 // integer keys whose selected values span less than the dense form's range (k_unique.hip, last section).  false: the span is too wide
-static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
+static bool unique_dense(dfdb_query* q, const Column& col, const UniqueRequest& R, UniqueTables& T) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const int dt = dt_base(col.dtype);
   const int64_t limit = std::min<int64_t>(unique_dense_max_range(), ctx_option(ctx, "unique_dense_range", unique_dense_max_range()));
   const ColRef key = col_ref(col);
   const uint64_t flip = dt_issigned(dt) ? (1ull << 63) : 0ull;
-  uint64_t* aux = nullptr;
+  UniqueAux* aux = nullptr;
   uint64_t distinct = 0;
   const int64_t nt_all = ceil_div(t->nrows, kTileRows), head_tiles = std::max<int64_t>(1, ctx_option(ctx, "dense_head_tiles", 4096));
-  T.head_only = T.allow_head && nt_all >= 8 * head_tiles;               // (the sample below still looks at the whole column: the span is laid around what IT saw)
+  T.head_only = R.allow_head && nt_all >= 8 * head_tiles;               // (the sample below still looks at the whole column: the span is laid around what IT saw)
   auto prows = [&]() -> int64_t { return T.head_only ? head_tiles * kTileRows : t->nrows; };      // the rows the presence pass and the first-row launches walk
   auto minmax = [&](int64_t tile_step, uint64_t* mm) {                 // order-preserving images of the smallest / largest selected key (of every tile_step-th tile)
     unique_reset_aux(ctx, T.aux);
-    { LaunchTimer lt(ctx, "unique_minmax"); launch_dense_minmax(s, q->bitmap.as<uint64_t>(), key, t->nrows, tile_step, T.aux.as<uint64_t>()); }
-    HIP_CHECK(hipMemcpyAsync(mm, (char*)T.aux.p + 64, 16, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
+    { LaunchTimer lt(ctx, "unique_minmax"); launch_dense_minmax(s, q->bitmap.as<uint64_t>(), key, t->nrows, tile_step, T.ctl()); }
+    const UniqueAux a = read_aux(ctx, T.ctl());
+    mm[0] = a.min_image; mm[1] = a.max_image;
   };
   auto presence = [&](uint64_t lo_im, uint64_t span) -> bool {         // false: a selected key lies outside [lo, lo + span]
     T.lo = lo_im ^ flip; T.range = (uint32_t)(span + 1);
@@ -127,15 +145,13 @@ static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
     HIP_CHECK(hipMemsetAsync(T.first.p, 0xFF, (size_t)T.range * 8, s));
     HIP_CHECK(hipMemsetAsync(T.present.p, 0, words * 4, s));
     unique_reset_aux(ctx, T.aux);
-    aux = T.aux.as<uint64_t>();
+    aux = T.ctl();
     { LaunchTimer lt(ctx, "unique_presence");
       launch_dense_presence(s, q->bitmap.as<uint64_t>(), key, prows(), T.lo, T.range, T.present.as<uint32_t>(), aux); }
-    uint64_t od[8] = {0, 0, 0, 0, 0, 0, 0, 0};                          // [0] a key outside?  [1] distinct values ... [6], [7] the span of the present values
-    HIP_CHECK(hipMemcpyAsync(od, (char*)T.aux.p + 40, 64, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    distinct = od[1];
-    T.span_lo = od[6]; T.span_hi = od[7];
-    return od[0] == 0;
+    const UniqueAux a = read_aux(ctx, aux);
+    distinct = a.distinct;
+    T.span_lo = a.span_lo; T.span_hi = a.span_hi;
+    return a.outside == 0;
   };
   const int64_t nt = ceil_div(t->nrows, kTileRows);
   bool placed = false;
@@ -192,10 +208,8 @@ static bool unique_dense(dfdb_query* q, const Column& col, UniqueTables& T) {
   HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
   HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
   { LaunchTimer lt(ctx, "unique_mark"); launch_dense_scatter(s, T.first.as<uint64_t>(), T.range, aux, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>()); }
-  uint64_t st[3];
-  HIP_CHECK(hipMemcpyAsync(st, (char*)T.aux.p + 40, 24, hipMemcpyDeviceToHost, s));      // outside flag, distinct values, values whose first row is known
-  stream_wait(ctx);
-  if (st[0] != 0 || st[1] != st[2]) fail(DFDB_ERR_DEVICE, "unique: the dense form lost a key (outside %llu, distinct %llu, found %llu)", (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2]);
+  const UniqueAux a = read_aux(ctx, aux);
+  if (a.outside != 0 || a.distinct != a.found) fail(DFDB_ERR_DEVICE, "unique: the dense form lost a key (outside %llu, distinct %llu, found %llu)", (unsigned long long)a.outside, (unsigned long long)a.distinct, (unsigned long long)a.found);
   return true;
 }
 
@@ -297,7 +311,7 @@ static bool unique_radix(dfdb_query* q, const Column& col, int64_t cnt, UniqueTa
   if (sk < 0) return false;
   if (sk) prof_note(ctx, "unique_radix.skewed");
   { LaunchTimer lt(ctx, "radix_partition");
-    if (!launch_radix_partition(s, q->bitmap.as<uint64_t>(), key, t->nrows, run.grid(), pool, recs.as<uint32_t>(), T.aux.as<uint64_t>(), nullptr, sk != 0)) return false; }
+    if (!launch_radix_partition(s, q->bitmap.as<uint64_t>(), key, t->nrows, run.grid(), pool, recs.as<uint32_t>(), &T.ctl()->head, nullptr, sk != 0)) return false; }
   // the selection is set aside (a partition that outgrows its table means: back to the hash table, over the same selection)
   HIP_CHECK(hipMemcpyAsync(sel_keep.p, q->bitmap.p, nw * 8, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(tc_keep.p, q->tile_counts.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
@@ -305,13 +319,12 @@ static bool unique_radix(dfdb_query* q, const Column& col, int64_t cnt, UniqueTa
   HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)nt * 4, s));
   bool ok;
   { LaunchTimer lt(ctx, "radix_unique");
-    ok = launch_radix_unique(s, recs.as<uint32_t>(), pool, kbits, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), T.aux.as<uint64_t>(), ctx->prop.multiProcessorCount); }
-  uint64_t aborted = 0;
-  if (ok) { HIP_CHECK(hipMemcpyAsync(&aborted, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s)); stream_wait(ctx); }
+    ok = launch_radix_unique(s, recs.as<uint32_t>(), pool, kbits, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), &T.ctl()->head, ctx->prop.multiProcessorCount); }
+  const uint64_t aborted = ok ? read_aux(ctx, T.ctl()).head.abort : 0;
   if (!ok || aborted || ctx_option(ctx, "unique_radix", 1) == 3) {        // (3: a test knob — behave as if a partition had overflowed)
     HIP_CHECK(hipMemcpyAsync(q->bitmap.p, sel_keep.p, nw * 8, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(q->tile_counts.p, tc_keep.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));
+    clear_abort(ctx, &T.ctl()->head);
     stream_wait(ctx);
     prof_note(ctx, "unique_radix.fell_back");
     return false;
@@ -322,7 +335,7 @@ static bool unique_radix(dfdb_query* q, const Column& col, int64_t cnt, UniqueTa
 }
 
 // the general form: an open-addressing table of {key, first row} sized by the distinct values as they turn up (k_unique.hip)
-static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueTables& T) {
+static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, const UniqueRequest& R, UniqueTables& T) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const bool is_str = T.is_str;
   const ColRef key = is_str ? ColRef{} : col_ref(col);                 // (a flat String key travels as str_side(col) + str_table(T))
@@ -340,11 +353,11 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
   auto insert = [&](int64_t t0, int64_t t1) {
     LaunchTimer lt(ctx, "unique_insert");
     if (is_str) launch_unique_str(s, 0, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), str_side(col), t->nrows, t0, t1, str_table(T));
-    else launch_unique_insert(s, q->bitmap.as<uint64_t>(), key, t0 * kTileRows, std::min(t->nrows, t1 * kTileRows), T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
+    else launch_unique_insert(s, q->bitmap.as<uint64_t>(), key, t0 * kTileRows, std::min(t->nrows, t1 * kTileRows), T.ent.as<UniqueEntry>(), T.cap - 1, T.ctl());
   };
-  uint64_t st[2] = {0, 0};                                             // claimed slots, abort flag
+  UniqueAux st{};                                                      // the control words as last read: claimed slots, abort flag
   auto read_state = [&](uint64_t* selected_before, int64_t tile) {
-    HIP_CHECK(hipMemcpyAsync(st, (char*)T.aux.p + 16, 16, hipMemcpyDeviceToHost, s));
+    fetch_aux(ctx, T.ctl(), &st);
     if (selected_before) HIP_CHECK(hipMemcpyAsync(selected_before, q->prefix.as<uint64_t>() + tile, 8, hipMemcpyDeviceToHost, s));
     stream_wait(ctx);
   };
@@ -352,16 +365,17 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
     LaunchTimer lt(ctx, "unique_migrate");
     UniqueTables N; N.is_str = is_str;
     alloc(N, cap);
-    HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 16, 0, 16, s));
+    clear_claims_and_abort(ctx, &T.ctl()->head);
     launch_unique_migrate(s, T.ent.as<UniqueEntry>(), is_str ? T.rep_off.as<uint64_t>() : nullptr, is_str ? T.rep_len.as<uint32_t>() : nullptr, T.cap, N.ent.as<UniqueEntry>(),
-                          N.rep_off.as<uint64_t>(), N.rep_len.as<uint32_t>(), cap - 1, T.aux.as<uint64_t>());
+                          N.rep_off.as<uint64_t>(), N.rep_len.as<uint32_t>(), cap - 1, T.ctl());
     read_state(nullptr, 0);
-    if (st[1]) fail(DFDB_ERR_DEVICE, "unique: %llu entries do not fit a table of %llu slots", (unsigned long long)st[0], (unsigned long long)cap);
+    if (st.head.abort) fail(DFDB_ERR_DEVICE, "unique: %llu entries do not fit a table of %llu slots", (unsigned long long)st.head.claims, (unsigned long long)cap);
     T.ent = std::move(N.ent); T.rep_off = std::move(N.rep_off); T.rep_len = std::move(N.rep_len); T.cap = cap;
   };
   T.salt = 0x51ED270B27B4F3CFull;
-  for (int k = 0; k < T.salt_skip; k++) T.salt = splitmix64_host(T.salt);
-  for (int tries = T.salt_skip;; tries++, T.salt = splitmix64_host(T.salt)) {
+  for (int k = 0; k < R.salt_skip; k++) T.salt = splitmix64_host(T.salt);
+  bool allow_optimistic = R.allow_optimistic;                          // (until an optimistic table turns out incomplete)
+  for (int tries = R.salt_skip;; tries++, T.salt = splitmix64_host(T.salt)) {
     if (!T.ent.p || T.cap != cap0) { T.ent.release(); alloc(T, cap0); } else HIP_CHECK(hipMemsetAsync(T.ent.p, 0xFF, T.cap * sizeof(UniqueEntry), s));
     unique_reset_aux(ctx, T.aux);
     int64_t t0 = 0;
@@ -377,84 +391,84 @@ static void unique_hashed(dfdb_query* q, const Column& col, int64_t cnt, UniqueT
       // (numeric keys: only for a caller whose own pass over the rows can report a key without a slot — groupreduce's accumulate pass, defer_verify —, and only when
       // the distinct keys are few beside the rows, so that the first rows come straight out of the table below)
       // (String keys too.  After an optimistic break the mark step below must take the first rows straight out of the table — launch_unique_scatter,
-      // `st[0] * 8 <= cnt` — because the per-row mark pass looks every selected row up with an unbounded probe, and a row of the un-inserted tail whose
+      // `claims * 8 <= cnt` — because the per-row mark pass looks every selected row up with an unbounded probe, and a row of the un-inserted tail whose
       // string the table does not hold would never leave that loop: a GPU hang, which no host-side guard can catch.)
-      if (c == 2 && (is_str || T.defer_verify) && T.allow_optimistic && claims_c0 != ~0ull && st[0] * 8 <= (uint64_t)cnt) { T.optimistic = true; break; }
+      if (c == 2 && (is_str || R.defer_verify) && allow_optimistic && claims_c0 != ~0ull && st.head.claims * 8 <= (uint64_t)cnt) { T.optimistic = true; break; }
       for (;;) {
         insert(t0, t1);
         read_state(&r, t1);
-        if (!st[1]) break;
-        if (T.cap >= capmax) fail(DFDB_ERR_DEVICE, "unique: probe sequences of a half-empty table got too long (%llu slots, %llu keys)", (unsigned long long)T.cap, (unsigned long long)st[0]);
+        if (!st.head.abort) break;
+        if (T.cap >= capmax) fail(DFDB_ERR_DEVICE, "unique: probe sequences of a half-empty table got too long (%llu slots, %llu keys)", (unsigned long long)T.cap, (unsigned long long)st.head.claims);
         grow(std::min(capmax, T.cap * 4));                             // (that clears the flag) and the chunk again: inserts are idempotent
       }
       // (optimistic: chunk 1 must have fed at least 64 K selected rows and claimed nothing that chunk 0 had not)
-      if (c == 0) { claims_c0 = st[0]; rows_c0 = r; }
-      else if (c == 1 && !(st[0] == claims_c0 && r >= rows_c0 + 65536)) claims_c0 = ~0ull;
+      if (c == 0) { claims_c0 = st.head.claims; rows_c0 = r; }
+      else if (c == 1 && !(st.head.claims == claims_c0 && r >= rows_c0 + 65536)) claims_c0 = ~0ull;
       if (c == 0 && !is_str) {
-        if (T.group_probe && r > 0) {                                  // groupreduce asks: more groups than LDS accumulators hold?  Then it reduces by radix, first rows included
-          const double D = estimate_distinct(st[0], r, cnt);
+        if (R.group_probe && r > 0) {                                  // groupreduce asks: more groups than LDS accumulators hold?  Then it reduces by radix, first rows included
+          const double D = estimate_distinct(st.head.claims, r, cnt);
           if (D > (double)kGroupsInLds) { T.group_estimate = (int64_t)D; return; }
         }
-        if (!T.defer_verify && T.allow_radix && unique_radix(q, col, cnt, T, st[0], r)) return;      // the radix-partitioned form took it: q's bitmap holds the first occurrences
+        if (!R.defer_verify && R.allow_radix && unique_radix(q, col, cnt, T, st.head.claims, r)) return;      // the radix-partitioned form took it: q's bitmap holds the first occurrences
       }
       if (c == 0 && bounds[1] <= bounds[0]) claims_c0 = ~0ull;
-      const uint64_t want = unique_capacity_wanted(st[0], r, (uint64_t)cnt - std::min<uint64_t>(r, (uint64_t)cnt), T.cap, capmax);
+      const uint64_t want = unique_capacity_wanted(st.head.claims, r, (uint64_t)cnt - std::min<uint64_t>(r, (uint64_t)cnt), T.cap, capmax);
       if (want > T.cap) grow(want);
       t0 = t1;
     }
-    if (!is_str || T.defer_verify) break;
+    if (!is_str || R.defer_verify) break;
     // the pass that compares every selected row with its slot's representative.  After an optimistic insert it also meets the rows that were never inserted: a string
     // the table does not hold raises the abort word and everything runs again with every row inserted (as groupreduce's accumulate pass does it)
-    if (T.optimistic) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));
+    if (T.optimistic) clear_abort(ctx, &T.ctl()->head);
     launch_unique_str(s, T.optimistic ? 3 : 1, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), str_side(col), t->nrows, 0, nt, str_table(T));
-    int hit = 0; uint64_t unknown = 0;
-    HIP_CHECK(hipMemcpyAsync(&hit, (char*)T.aux.p + 32, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    if (T.optimistic && (unknown != 0 || ctx_option(ctx, "groupreduce_optimistic", 1) == 2)) { T.allow_optimistic = false; continue; }   // (2: the test knob, as in groupreduce)
-    if (!hit) break;                                                   // no two different strings shared a key: the table is exact
+    const UniqueAux v = read_aux(ctx, T.ctl());
+    if (T.optimistic && (v.head.abort != 0 || ctx_option(ctx, "groupreduce_optimistic", 1) == 2)) { allow_optimistic = false; continue; }   // (2: the test knob, as in groupreduce)
+    if (!(uint32_t)v.collision) break;                                 // no two different strings shared a key: the table is exact
     if (tries >= 8) fail(DFDB_ERR_DEVICE, "unique: hash collisions under 8 different salts");
   }
   LaunchTimer lt(ctx, "unique_mark");
-  if (st[0] * 8 <= (uint64_t)cnt) {                                    // few distinct values beside the rows: the first rows straight out of the table
+  if (st.head.claims * 8 <= (uint64_t)cnt) {                           // few distinct values beside the rows: the first rows straight out of the table
     HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
     HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)nt * 4, s));
-    launch_unique_scatter(s, T.ent.as<UniqueEntry>(), T.cap, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>());
+    launch_unique_scatter(s, T.ent.as<UniqueEntry>(), T.cap, T.ctl(), q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>());
   } else if (is_str) {
     launch_unique_str(s, 2, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), str_side(col), t->nrows, 0, nt, str_table(T));
   } else {
-    launch_unique_mark(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), key, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, T.aux.as<uint64_t>());
+    launch_unique_mark(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), key, t->nrows, T.ent.as<UniqueEntry>(), T.cap - 1, T.ctl());
   }
 }
 
 // (col: a column of the table, or a transient one that belongs to no table's column list — groupreduce_n's images)
-static void unique_impl_col(dfdb_query* q, const Column& col, UniqueTables* keep) {
+static void unique_impl_col(dfdb_query* q, const Column& col, const UniqueRequest& R, UniqueTables* keep) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
   const int64_t cnt = query_count(q, -1);
   if (cnt == 0 || t->nrows == 0) return;
   if (!keep && col.dict_n > 0) { dict_unique(q, col, nullptr); return; }
   UniqueTables local;
   UniqueTables& T = keep ? *keep : local;
-  T.is_str = dt_base(col.dtype) == DFDB_STRING; T.dense = false;
-  if (!keep) local.allow_optimistic = ctx_option(ctx, "groupreduce_optimistic", 1) != 0;      // (unique's own compare pass meets every row: the same bargain)
+  T.is_str = dt_base(col.dtype) == DFDB_STRING; T.dense = false; T.group_estimate = 0;
   {
     LaunchTimer lt(ctx, "unique");
-    const bool dense = !T.is_str && unique_dense_dtype(dt_base(col.dtype)) && ctx_option(ctx, "unique_dense", 1) != 0 && unique_dense(q, col, T);
-    if (!dense) unique_hashed(q, col, cnt, T);
+    const bool dense = !T.is_str && unique_dense_dtype(dt_base(col.dtype)) && ctx_option(ctx, "unique_dense", 1) != 0 && unique_dense(q, col, R, T);
+    if (!dense) unique_hashed(q, col, cnt, R, T);
   }
   scan_prefix(q);
   selection_changed(q); q->left.cap_col = -1; q->left.cap_col2 = -1; q->left.cap_str_col = -1; q->left.agg_col = -1;
   stream_wait(ctx);                                        // the tables die here (or stay with the caller: groupreduce looks rows up in them)
   if (!keep) { RecycleScope rs; local = UniqueTables(); }
 }
-static void unique_impl(dfdb_query* q, int32_t p, UniqueTables* keep) {
+static void unique_impl(dfdb_query* q, int32_t p, const UniqueRequest& R, UniqueTables* keep) {
   ensure_executed_checked(q);
   if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
   const Node& e = *q->proj[(size_t)p].expr;
   if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "unique of a computed column: materialise it as a column first (dfdb_table_add_from_query)");
-  unique_impl_col(q, need_resident(q->t, e.col), keep);
+  unique_impl_col(q, need_resident(q->t, e.col), R, keep);
 }
-void query_unique(dfdb_query* q, int32_t p) { unique_impl(q, p, nullptr); }
+void query_unique(dfdb_query* q, int32_t p) {
+  UniqueRequest R;
+  R.allow_optimistic = ctx_option(q->t->ctx, "groupreduce_optimistic", 1) != 0;      // (unique's own compare pass meets every row: the same bargain as groupreduce's)
+  unique_impl(q, p, R, nullptr);
+}
 
 // the groups' counts (zero) and values (the identity of `op`) for `ng` groups
 static void reset_group_outputs(dfdb_query* q, int64_t ng, int op) {
@@ -488,18 +502,18 @@ static bool group_radix(dfdb_query* q, const ColRef& key, const Column* vc, int 
   const int P = 1 << kbits;
   PooledScratch res(ctx);
   RadixRun run(ctx, kbits);
-  if (!run.prepare(nsel, true, 128) || !try_ensure(res.buf, (size_t)(mark ? (int64_t)P * radix_group_slots() : ng) * 16 + 256)) return false;
+  if (!run.prepare(nsel, true, sizeof(RadixGroupAux)) || !try_ensure(res.buf, (size_t)(mark ? (int64_t)P * radix_group_slots() : ng) * 16 + 256)) return false;
   const RadixPool& pool = run.pool;
   DevBuf& recs = ctx->radix_recs;
-  uint64_t* aux = (uint64_t*)run.extra();                                // [0] the unstorable key's first row, [1] the missing key's, [3] abort; [4..7] gspec; [8] nres
+  RadixGroupAux* aux = (RadixGroupAux*)run.extra();                      // (zero: prepare cleared it)
   RadixGroup g{};
   g.val = col_ref(vc);
   const int kind = q->gr_kinds_n[0];
   g.gop = op == DFDB_AGG_SUM ? (kind == 2 ? 2 : 1) : (op == DFDB_AGG_MIN ? 3 : (op == DFDB_AGG_MAX ? 4 : 0));
   if (!vc) g.gop = 0;
-  g.vkind = kind; g.results = res.buf.p; g.gspec = aux + 4; g.nres = (uint32_t*)(aux + 8);
-  HIP_CHECK(hipMemsetAsync(aux, 0xFF, 16, s));                           // aux[0], aux[1] = none
-  if (g.gop == 3) { HIP_CHECK(hipMemsetAsync(aux + 5, 0xFF, 8, s)); HIP_CHECK(hipMemsetAsync(aux + 7, 0xFF, 8, s)); }      // gspec[1], [3]: a minimum starts at all ones
+  g.vkind = kind; g.results = res.buf.p; g.aux = aux;
+  HIP_CHECK(hipMemsetAsync(aux->head.special_row, 0xFF, sizeof aux->head.special_row, s));      // no such row yet
+  if (g.gop == 3) for (int k = 0; k < 2; k++) HIP_CHECK(hipMemsetAsync(&aux->gspec[2 * k + 1], 0xFF, sizeof aux->gspec[0], s));      // the two groups' values: a minimum starts at all ones
   // a key that a large part of the rows hold is reduced by the partition pass itself (k_radix.hip, hot keys: the form this replaces sent every one of its rows
   // through a global atomic on ONE address — 3.6 s per 1e9 rows with a key that 30 % of them hold); the kernels that do so are 0.8-1.1 ms slower where nothing is
   // hot, so the sample picks: some partition above THREE average ones, and they run
@@ -507,27 +521,25 @@ static bool group_radix(dfdb_query* q, const ColRef& key, const Column* vc, int 
   if (sk < 0) return false;
   if (sk) prof_note(ctx, "group_radix.skewed");
   { LaunchTimer lt(ctx, "radix_partition");
-    if (!launch_radix_partition(s, sel, key, t->nrows, run.grid(), pool, recs.as<uint32_t>(), aux, &g, sk != 0)) return false; }
+    if (!launch_radix_partition(s, sel, key, t->nrows, run.grid(), pool, recs.as<uint32_t>(), &aux->head, &g, sk != 0)) return false; }
   if (mark) {
     HIP_CHECK(hipMemsetAsync(q->bitmap.p, 0, padded_words(t->nrows) * 8, s));
     HIP_CHECK(hipMemsetAsync(q->tile_counts.p, 0, (size_t)ceil_div(t->nrows, kTileRows) * 4, s));
   }
   { LaunchTimer lt(ctx, "radix_group");
-    if (!launch_radix_group(s, recs.as<uint32_t>(), pool, kbits, mark, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), aux, g, ctx->prop.multiProcessorCount)) return false; }
-  uint64_t tailw[9] = {};
-  HIP_CHECK(hipMemcpyAsync(tailw, aux, 72, hipMemcpyDeviceToHost, s));
-  stream_wait(ctx);
-  const uint32_t nres = (uint32_t)tailw[8];
-  if (tailw[3] != 0) { prof_note(ctx, "group_radix.fell_back"); return false; }
+    if (!launch_radix_group(s, recs.as<uint32_t>(), pool, kbits, mark, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), g, ctx->prop.multiProcessorCount)) return false; }
+  const RadixGroupAux a = read_aux(ctx, aux);
+  const uint32_t nres = (uint32_t)a.nres;
+  if (a.head.abort != 0) { prof_note(ctx, "group_radix.fell_back"); return false; }
   if (mark) {
     scan_prefix(q);
     selection_changed(q);
     ng = query_count(q, -1);
     *ng_io = ng;
   }
-  if ((int64_t)nres + (tailw[0] != ~0ull ? 1 : 0) + (tailw[1] != ~0ull ? 1 : 0) != ng) { prof_note(ctx, "group_radix.mismatch"); return false; }     // (cannot happen: the table pass saw every key unique saw)
+  if ((int64_t)nres + (a.head.special_row[SPECIAL_UNSTORABLE] != ~0ull ? 1 : 0) + (a.head.special_row[SPECIAL_MISSING] != ~0ull ? 1 : 0) != ng) { prof_note(ctx, "group_radix.mismatch"); return false; }     // (cannot happen: the table pass saw every key unique saw)
   reset_group_outputs(q, ng, op);
-  launch_radix_group_finish(s, g, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), aux, q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>());
+  launch_radix_group_finish(s, g, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>(), q->gr_cnt.as<uint64_t>(), q->gr_val.as<uint64_t>());
   prof_note(ctx, "group_radix.taken");
   return true;                                                           // (the temporaries' destructor drains the stream)
 }
@@ -547,6 +559,7 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   int64_t ng = 0;
   bool pessimistic = false, whole_dense = false, radix_failed = false;
+  int collisions = 0;                                            // salts found colliding so far
   // integer keys, dense form: the table of first rows / group numbers is made from the HEAD of the column (4 M rows) when the accumulate pass can be the one with
   // the table in LDS — that pass meets every row anyway and raises a flag for a key that has no group, after which everything runs again over every row
   // (the presence pass over the whole key column was 1.3 of the 5.0 ms of 1e9 rows by 5000 keys)
@@ -555,12 +568,13 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
   for (;;) {
     // String keys: the pass that compares every row with its slot's representative (unique's verify pass) is folded into the accumulate pass below, which
     // hashes every row and finds its slot anyway; should two different strings share a key the selection is put back and everything runs again under the next salt
-    T.defer_verify = true;
-    T.allow_optimistic = !pessimistic && ctx_option(ctx, "groupreduce_optimistic", 1) != 0;
-    T.allow_head = head_ok && !whole_dense;
-    T.group_probe = !radix_failed && ctx_option(ctx, "unique_radix", 1) != 0 && dt_base(kc.dtype) != DFDB_STRING;
-    T.group_estimate = 0;
-    unique_impl(q, key_p, &T);
+    UniqueRequest R;
+    R.defer_verify = true;
+    R.allow_optimistic = !pessimistic && ctx_option(ctx, "groupreduce_optimistic", 1) != 0;
+    R.allow_head = head_ok && !whole_dense;
+    R.group_probe = !radix_failed && ctx_option(ctx, "unique_radix", 1) != 0 && dt_base(kc.dtype) != DFDB_STRING;
+    R.salt_skip = collisions;
+    unique_impl(q, key_p, R, &T);
     if (T.group_estimate > 0) {                                  // the first chunk of rows promises more groups than any accumulate pass's LDS holds: by radix, first rows and all
       ng = T.group_estimate;
       if (group_radix(q, col_ref(kc), vc, op, nsel, &ng, q->gr_sel.as<uint64_t>(), true)) break;
@@ -569,11 +583,12 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
       continue;
     }
     const bool head_table = T.dense && T.head_only;
-    if (head_table) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));        // (the word the accumulate pass raises: aux[3])
-    if (T.optimistic) HIP_CHECK(hipMemsetAsync((char*)T.aux.p + 24, 0, 8, s));      // the accumulate pass raises this word when it meets a string the table does not hold
+    UniqueAux* aux = T.ctl();
+    if (head_table) clear_abort(ctx, &aux->head);        // (the word the accumulate pass raises)
+    if (T.optimistic) clear_abort(ctx, &aux->head);      // the accumulate pass raises this word when it meets a string the table does not hold
     ng = query_count(q, -1);
-    uint64_t* special = T.aux.as<uint64_t>();
-    if (T.dense) launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, special, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
+    uint64_t* special = aux->head.special_row;
+    if (T.dense) launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, aux, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
     else launch_group_ids(s, T.ent.as<UniqueEntry>(), T.cap, special, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
     reset_group_outputs(q, ng, op);
     // more groups than the LDS accumulators of any accumulate pass hold: by radix (group_radix) — which needs EVERY group's first row in the bitmap: a table made
@@ -594,7 +609,7 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
       A.special = special;
       if (T.dense) {
         A.key(col_ref(kc)); A.lo = T.lo; A.gids = T.first.as<uint64_t>();
-        A.unknown_flag = head_table ? T.aux.as<uint64_t>() + 3 : nullptr;
+        A.unknown_flag = head_table ? &aux->head.abort : nullptr;
         dense_lds = launch_group_accumulate(s, GROUP_SRC_DENSE, A, GroupAccExtra{nullptr, T.range, T.span_lo, T.span_hi});
       } else if (T.is_str)
         launch_group_accumulate_str(s, A, str_side(kc), str_table(T));
@@ -607,16 +622,13 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
           gkeys = q->gr_keys.p;
         }
         A.key(col_ref(kc)); A.ent = T.ent.as<UniqueEntry>(); A.mask = T.cap - 1;
-        A.unknown_flag = T.optimistic ? T.aux.as<uint64_t>() + 3 : nullptr;      // the table was filled from a prefix of the rows: a key without a slot raises this word
+        A.unknown_flag = T.optimistic ? &aux->head.abort : nullptr;      // the table was filled from a prefix of the rows: a key without a slot raises this word
         if (launch_group_accumulate(s, GROUP_SRC_HASH, A, GroupAccExtra{gkeys, 0, 0, 0}) > 0) prof_note(ctx, "group_accumulate.hash_lds");
       } }
     if (dense_lds > 0) prof_note(ctx, "group_accumulate.dense_lds");
     if (head_table) {
       uint64_t unknown = dense_lds < 0 ? 1ull : 0ull;                  // (-1: the LDS form could not take the job and nothing ran)
-      if (!unknown) {
-        HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
-        stream_wait(ctx);
-      }
+      if (!unknown) unknown = read_aux(ctx, aux).head.abort;
       if (unknown || ctx_option(ctx, "groupreduce_optimistic", 1) == 2) {          // (2: the test knob — as if a key had been missing)
         whole_dense = true;
         prof_note(ctx, "group_accumulate.head_redo");
@@ -626,15 +638,13 @@ static int64_t groupreduce_hashed(dfdb_query* q, int32_t key_p, const Column& kc
       prof_note(ctx, "group_accumulate.head_table");
     }
     if (!T.is_str && !T.optimistic) break;
-    int hit = 0; uint64_t unknown = 0;
-    HIP_CHECK(hipMemcpyAsync(&hit, (char*)T.aux.p + 32, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&unknown, (char*)T.aux.p + 24, 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    const bool redo_all = T.optimistic && (unknown != 0 || ctx_option(ctx, "groupreduce_optimistic", 1) == 2);      // (2: a test knob — behave as if a string had been missing)
+    const UniqueAux a = read_aux(ctx, aux);
+    const bool hit = (uint32_t)a.collision != 0;
+    const bool redo_all = T.optimistic && (a.head.abort != 0 || ctx_option(ctx, "groupreduce_optimistic", 1) == 2);      // (2: a test knob — behave as if a string had been missing)
     if (!T.is_str && !redo_all) break;                       // (numeric keys: nothing to collide)
-    if (!hit && !redo_all && ctx_option(ctx, "unique_test_collide", 0) <= T.salt_skip) break;
+    if (!hit && !redo_all && ctx_option(ctx, "unique_test_collide", 0) <= collisions) break;
     if (redo_all) pessimistic = true;                         // a string first met after the inserted prefix: everything again, every row inserted
-    else if (++T.salt_skip > 8) fail(DFDB_ERR_DEVICE, "unique: hash collisions under 8 different salts");
+    else if (++collisions > 8) fail(DFDB_ERR_DEVICE, "unique: hash collisions under 8 different salts");
     restore_group_selection(q);     // the full selection again
   }
   return ng;
@@ -774,22 +784,23 @@ static int64_t group_rank_key(dfdb_query* q, const Column& kc, const uint32_t* g
     ok = launch_group_rank(s, 1, A);
   } else {
     UniqueTables T;
-    T.allow_radix = false;                                      // (defer_verify, allow_optimistic, allow_head, group_probe: all off by default)
-    unique_impl_col(q, kc, &T);
+    UniqueRequest R;                                            // a complete, verified table ...
+    R.allow_radix = false;                                      // ... and a table it must be
+    unique_impl_col(q, kc, R, &T);
     n = query_count(q, -1);
-    A.n = (uint64_t)n; A.special = T.aux.as<uint64_t>();
+    A.n = (uint64_t)n; A.special = T.ctl()->head.special_row;
     const ColRef key = col_ref(kc);
     A.keycol = key.data; A.keydt = key.dtype; A.missing = T.is_str ? nullptr : key.missing;
     LaunchTimer lt(ctx, "group_rank");
     if (T.dense) {
-      launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
+      launch_dense_group_ids(s, T.first.as<uint64_t>(), T.range, T.ctl(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
       A.lo = T.lo; A.range = T.range; A.gids = T.first.as<uint64_t>();
       if (T.span_lo <= T.span_hi && T.span_hi < (uint64_t)T.range) {      // the table is laid out wider than the keys: only the span they cover (small: in LDS)
         A.lo = T.lo + T.span_lo; A.range = (uint32_t)(T.span_hi - T.span_lo + 1); A.gids = T.first.as<uint64_t>() + T.span_lo;
       }
       ok = launch_group_rank(s, 2, A);
     } else {
-      launch_group_ids(s, T.ent.as<UniqueEntry>(), T.cap, T.aux.as<uint64_t>(), q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
+      launch_group_ids(s, T.ent.as<UniqueEntry>(), T.cap, T.ctl()->head.special_row, q->bitmap.as<uint64_t>(), q->prefix.as<uint64_t>());
       A.ent = T.ent.as<UniqueEntry>(); A.mask = T.cap - 1;
       if (T.is_str) ok = launch_group_rank_str(s, A, str_side(kc), T.salt);
       else ok = launch_group_rank(s, 0, A);
