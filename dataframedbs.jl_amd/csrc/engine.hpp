@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "expr.hpp"
 #include "kernels.hpp"
+#include <functional>
 #include <memory>
 #include <mutex>
 
@@ -222,7 +223,13 @@ void query_select_indices(dfdb_query* q, int64_t* out, int64_t cap, int32_t memk
 int64_t query_string_bytes(dfdb_query* q, int i);
 void query_materialize(dfdb_query* q, dfdb_outcol* outs, int32_t ncols);
 void query_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, double* out_f);
+// project.cpp over k_select.hip: the select keys of up to kSelectMaxRanks ranks among the selected non-missing values of a resident column (see there)
+struct SelectRanks { int n; int64_t rank[kSelectMaxRanks]; };
+int select_keys(dfdb_query* q, const Column& col, bool full, bool count, int max_ranks, int64_t cnt[3], const std::function<void(SelectRanks&)>& choose, uint64_t* keys);
 void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts);   // project.cpp over k_select.hip
+// sort.cpp over k_sort.hip: the stable sortperm of the selected rows by projection column p; the projection at given rows
+void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info);
+void query_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols);
 void query_unique(dfdb_query* q, int32_t p);
 void query_groupreduce(dfdb_query* q, int32_t key_p, int32_t val_p, int32_t op, int64_t* ngroups, int64_t* key_bytes);
 void query_groupreduce_fetch(dfdb_query* q, dfdb_outcol* keys, int64_t* counts, int64_t* vals_i, double* vals_f);

@@ -1299,6 +1299,12 @@ int32_t dfdb_selftest(const char* name, int64_t arg, int64_t* out, int32_t nout)
       }
       return;
     }
+    if (!strcmp(name, "sort_geometry")) {
+      // the chunk geometry of the radix sort's passes (k_sort.hip): out = [pairs per chunk, threads per workgroup]
+      if (nout < 2) fail(DFDB_ERR_ARGUMENT, "ArgumentError: sort_geometry fills 2 values");
+      sort_geometry(out);
+      return;
+    }
     fail(DFDB_ERR_ARGUMENT, "ArgumentError: no self-test named %s", name);
   });
 }

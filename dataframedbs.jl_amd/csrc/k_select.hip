@@ -22,6 +22,7 @@
 //   algorithmic bytes / row / pass: 1/8 (bitmap) + sigma * W (column) [+ 1/8 (missing bitmap) for a nullable column]
 #include "device_utils.hpp"
 #include "value_rules.hpp"
+#include "select_key.hpp"
 #include "kernels.hpp"
 #include "launch_dispatch.hpp"
 #include "../../include/dfdb_ir.h"
@@ -32,36 +33,6 @@ constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = 4;
 constexpr int kSelBlocks = 2048;      // 8 workgroups per CU: the 32-wave limit, 128 KB of the CU's 160 KB of LDS
 
-template <int DT> struct SelT { using type = uint64_t; };
-template <> struct SelT<DFDB_I8> { using type = int8_t; };   template <> struct SelT<DFDB_I16> { using type = int16_t; };
-template <> struct SelT<DFDB_I32> { using type = int32_t; }; template <> struct SelT<DFDB_I64> { using type = int64_t; };
-template <> struct SelT<DFDB_U8> { using type = uint8_t; };  template <> struct SelT<DFDB_U16> { using type = uint16_t; };
-template <> struct SelT<DFDB_U32> { using type = uint32_t; }; template <> struct SelT<DFDB_F32> { using type = float; };
-template <> struct SelT<DFDB_F64> { using type = double; };
-
-// how many bits the select key of a column has (Bool is stored as UInt8)
-int select_key_bits(int dtype, bool full) {
-  if (full) return 64;
-  switch (dtype) {
-    case DFDB_I8: case DFDB_U8: case DFDB_BOOL: return 8;
-    case DFDB_I16: case DFDB_U16: return 16;
-    case DFDB_I32: case DFDB_U32: case DFDB_F32: return 32;
-    default: return 64;
-  }
-}
-// the select key of the value at `p` (one element of a column of base dtype DT)
-template <int DT, bool FULL> __device__ __forceinline__ uint64_t select_key(const void* p) {
-  if (FULL || DT == DFDB_I64 || DT == DFDB_U64 || DT == DFDB_F64) return order_image(value_image(p, DT, 0), value_kind(DT), false);
-  if (DT == DFDB_F32) {                                                  // Float32 -> Float64 is exact and monotonic: the same order in the float's own bits
-    const float f = *(const float*)p;
-    const uint32_t b = f32_bits(f);
-    return f != f ? 0xffffffffull : (uint64_t)((b >> 31) ? ~b : (b | 0x80000000u));
-  }
-  if (DT == DFDB_I8) return (uint64_t)(uint8_t)(*(const uint8_t*)p ^ 0x80u);
-  if (DT == DFDB_I16) return (uint64_t)(uint16_t)(*(const uint16_t*)p ^ 0x8000u);
-  if (DT == DFDB_I32) return (uint64_t)(*(const uint32_t*)p ^ 0x80000000u);
-  return value_image(p, DT, 0);                                          // the narrow unsigned types and Bool: the value
-}
 // the way back: a select key -> the 64 bits of the value's accumulator (value_rules.hpp value_image: integers widened, floats as Float64; the NaN key
 // is the canonical quiet NaN)
 uint64_t select_key_value(int dtype, bool full, uint64_t key) {

@@ -187,8 +187,33 @@ constexpr int kSelectMaxRanks = 16;
 struct SelectPass { uint64_t prefix[kSelectMaxRanks]; int32_t ngroups; int32_t shift; int32_t first; };
 void launch_select_hist(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const ColRef& col, bool full,
                         int64_t nrows, const SelectPass& P, uint64_t* hist /* [kSelectMaxRanks * 256] */, uint64_t* counts /* [3] */);
-int select_key_bits(int dtype, bool full);
+// (select_key_bits, the number of key bits of a dtype: select_key.hpp)
 uint64_t select_key_value(int dtype, bool full, uint64_t key);      // a finished key -> the value's 64 accumulator bits (integers widened, floats as Float64)
+
+// ---- K12: stable sortperm of the selected rows by radix sort, and the gather that follows a row list (k_sort.hip) ------------------
+// The build: every selected row that is not missing and that `keep` admits becomes a pair {key ^ flip, 0-based row} at live_base[tile] + its rank among the
+// tile's kept rows (live_base: the selection's own prefix when every selected row is kept, else the scan of the count phase's live_cnt); every selected
+// missing row goes to miss_rows at miss_base[tile] + its rank (null: the column has no missing bitmap).  The write phase adds the kept keys' per-byte
+// histograms to ghist[byte * 256 + digit] (64-bit counters the caller zeroes).  The count phase fills live_cnt / miss_cnt [tiles] (zeroed by the caller).
+enum SortKeep : int { SORT_KEEP_ALL = 0, SORT_KEEP_CUT = 1 /* key ^ flip <= cut */, SORT_KEEP_NONE = 2 };
+struct SortBuild {
+  const uint64_t* bitmap; const uint32_t* tile_counts; int64_t nrows;
+  const uint64_t* live_base; const uint64_t* miss_base;
+  uint64_t flip, cut; int32_t keep;
+  uint64_t* keys; uint32_t* rows; int64_t cap; uint32_t* miss_rows; int64_t miss_cap;
+  uint32_t* live_cnt; uint32_t* miss_cnt;
+  unsigned long long* ghist;
+};
+void launch_sort_build(hipStream_t s, const ColRef& col, const SortBuild& B, bool count_phase);
+void sort_geometry(int64_t out[2]);                  // {pairs per chunk of a pass, threads per workgroup}
+int64_t sort_chunks(int64_t npairs);
+// one pass over key bits [shift, shift + 8): counts [256 * sort_chunks(n)] bin-major, their exclusive scan `starts` (launch_scan_counts), the stable scatter
+void launch_sort_count(hipStream_t s, const uint64_t* keys, int64_t n, int shift, uint32_t* counts);
+void launch_sort_scatter(hipStream_t s, const uint64_t* keys_in, const uint32_t* rows_in, int64_t n, int shift, const uint64_t* starts, uint64_t* keys_out, uint32_t* rows_out);
+void launch_sort_emit(hipStream_t s, const uint32_t* rows, int64_t n, int64_t* out, int64_t row_base);      // out[i] = row_base + rows[i] + 1
+// out[i] = col[rows[i] - 1 - row_base], mout[i] = that row's missing bit (mout null: none wanted); a row outside [0, nrows) raises *flag and writes nothing
+void launch_gather_rows(hipStream_t s, const int64_t* rows, int64_t n, const void* col, int width, void* out, const uint64_t* missing, uint8_t* mout, int64_t row_base,
+                        int64_t nrows, uint32_t* flag);
 
 // ---- the control words of unique / groupreduce: 128 bytes of device memory through which the kernels of k_unique.hip and k_radix.hip report to the host, which
 // reads every retry decision from them.  The host sets them with device memsets (all zero, then all ones where a field says so) and reads them back whole.

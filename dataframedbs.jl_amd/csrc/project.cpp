@@ -8,6 +8,7 @@
 // what that execution left behind in dfdb_query::left.
 #include "engine.hpp"
 #include "ooc.hpp"
+#include "select_key.hpp"
 #include <algorithm>
 
 namespace dfdb {
@@ -408,9 +409,52 @@ void query_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, doubl
   else { const int64_t v = ctx->pinned_scalar[0]; if (out_i) *out_i = v; if (out_f) *out_f = dt == DFDB_U64 ? (double)(uint64_t)v : (double)v; }
 }
 
+// Most-significant-digit radix select (k_select.hip) of up to kSelectMaxRanks ranks among the selected, non-missing values of `col`: one histogram pass per 8
+// key bits, the bins chosen here in between.  Every rank carries the key bits decided so far (its prefix) and its position inside the bin they name; ranks with
+// one prefix are one group of the pass.  `choose` names the ranks (1-based, R.n <= max_ranks of them) once cnt = {not missing, missing, NaN} of the selected rows
+// is known: at once when the caller gives cnt (count = false), else after the first pass, which counts them — until then every possible rank shares the
+// empty prefix, one group.  R.n = 0 ends the select (a counting pass alone when max_ranks = 0).  Returns R.n; keys[i] is the select key of rank i.
+int select_keys(dfdb_query* q, const Column& col, bool full, bool count, int max_ranks, int64_t cnt[3], const std::function<void(SelectRanks&)>& choose, uint64_t* keys) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  SelectRanks R{}; bool chosen = false;
+  uint64_t prefix[kSelectMaxRanks] = {}; int64_t rel[kSelectMaxRanks] = {};     // per rank
+  if (!count) { choose(R); chosen = true; for (int i = 0; i < R.n; i++) rel[i] = R.rank[i]; if (R.n == 0) return 0; }
+  DevBuf& st = q->tmp_a; st.ensure((size_t)(kSelectMaxRanks * 256 + 8) * 8);       // histograms, then the three counts
+  uint64_t* hist = st.as<uint64_t>(); uint64_t* dcnt = hist + kSelectMaxRanks * 256;
+  std::vector<uint64_t> h((size_t)kSelectMaxRanks * 256 + 8);
+  const int nbits = select_key_bits(dt_base(col.dtype), full);
+  for (int shift = nbits - 8; shift >= 0; shift -= 8) {
+    SelectPass P{}; P.shift = shift; P.first = shift == nbits - 8 && count;
+    int grp[kSelectMaxRanks];
+    const int pending = chosen ? R.n : max_ranks;
+    for (int i = 0; i < pending; i++) {
+      int g = 0;
+      while (g < P.ngroups && P.prefix[g] != prefix[i]) g++;
+      if (g == P.ngroups) P.prefix[P.ngroups++] = prefix[i];
+      grp[i] = g;
+    }
+    const size_t used = P.first ? h.size() : (size_t)P.ngroups * 256;
+    HIP_CHECK(hipMemsetAsync(hist, 0, used * 8, s));
+    { LaunchTimer lt(ctx, "select_hist");
+      launch_select_hist(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col_ref(col), full, t->nrows, P, hist, dcnt); }
+    HIP_CHECK(hipMemcpyAsync(h.data(), hist, used * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));            // (`h` is pageable host memory)
+    if (P.first) for (int k = 0; k < 3; k++) cnt[k] = (int64_t)h[(size_t)kSelectMaxRanks * 256 + k];
+    if (!chosen) { choose(R); chosen = true; for (int i = 0; i < R.n; i++) rel[i] = R.rank[i]; if (R.n == 0) return 0; }
+    for (int i = 0; i < R.n; i++) {                // the bin that holds rank i of its group; the rank becomes relative to it
+      const uint64_t* hg = h.data() + (size_t)grp[i] * 256;
+      int b = 0;
+      while (b < 256 && (uint64_t)rel[i] > hg[b]) { rel[i] -= (int64_t)hg[b]; b++; }
+      if (b == 256) fail(DFDB_ERR_DEVICE, "radix select: the histogram of key bits %d.. holds fewer rows than the rank", shift);
+      prefix[i] = (prefix[i] << 8) | (uint64_t)b;
+    }
+  }
+  for (int i = 0; i < R.n; i++) keys[i] = prefix[i];
+  return R.n;
+}
+
 // the k-th smallest values of projection column p over the selected rows (dfdb_order_statistics: Statistics.median / quantile over
-// Base.iterate(::DFColumn), column.jl:102-126) by radix select (k_select.hip): one histogram pass per 8 key bits, the bins chosen here in between.
-// Every rank carries the key bits decided so far (its prefix) and its position inside the bin they name; ranks with one prefix are one group of the pass.
+// Base.iterate(::DFColumn), column.jl:102-126) by radix select (select_keys above)
 void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts) {
   if (nranks < 0 || nranks > kSelectMaxRanks) fail(DFDB_ERR_ARGUMENT, "ArgumentError: order statistics take 0 to %d ranks per call, %d given", kSelectMaxRanks, nranks);
   if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
@@ -418,7 +462,7 @@ void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int3
   if (dt_base(e.dtype) == DFDB_STRING) fail(DFDB_ERR_ARGUMENT, "ArgumentError: order statistics of a String column are not defined");
   if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "order statistics of a computed column: materialise it as a column first (dfdb_table_add_from_query)");
   if (!dt_isnum(e.dtype)) fail(DFDB_ERR_UNSUPPORTED, "order statistics over %s are not supported", dt_name(e.dtype).c_str());
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
   // the column must be resident decoded: the block-streamed form and the one over the resident LZ4 blocks are follow-ups
   if (query_out_of_core(q)) fail(DFDB_ERR_UNSUPPORTED, "order statistics over a view that is out of core (its columns are not resident) are not supported: dfdb_table_load the columns first");
   if (t->cols[(size_t)e.col].comp_only)
@@ -428,46 +472,17 @@ void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int3
   const int dt = dt_base(e.dtype), kind = value_kind(dt);
   const bool nullable = dt_nullable(e.dtype), full = ctx_option(ctx, "select_full_image", 0) != 0;
   int64_t cnt[3] = {0, 0, 0};
-  uint64_t prefix[kSelectMaxRanks] = {}; int64_t rel[kSelectMaxRanks] = {};     // per rank
+  uint64_t keys[kSelectMaxRanks] = {};
   if (nranks == 0 && !nullable && kind != kAccFloat) cnt[0] = query_count(q, -1);   // nothing can be missing or NaN: the selection's own count
-  else {
-    DevBuf& st = q->tmp_a; st.ensure((size_t)(kSelectMaxRanks * 256 + 8) * 8);       // histograms, then the three counts
-    uint64_t* hist = st.as<uint64_t>(); uint64_t* dcnt = hist + kSelectMaxRanks * 256;
-    std::vector<uint64_t> h((size_t)kSelectMaxRanks * 256 + 8);
-    const int nbits = select_key_bits(dt, full);
-    for (int i = 0; i < nranks; i++) rel[i] = ranks[i];
-    for (int shift = nbits - 8; shift >= 0; shift -= 8) {
-      SelectPass P{}; P.shift = shift; P.first = shift == nbits - 8;
-      int grp[kSelectMaxRanks];
-      for (int i = 0; i < nranks; i++) {
-        int g = 0;
-        while (g < P.ngroups && P.prefix[g] != prefix[i]) g++;
-        if (g == P.ngroups) P.prefix[P.ngroups++] = prefix[i];
-        grp[i] = g;
-      }
-      const size_t used = P.first ? h.size() : (size_t)P.ngroups * 256;
-      HIP_CHECK(hipMemsetAsync(hist, 0, used * 8, s));
-      { LaunchTimer lt(ctx, "select_hist");
-        launch_select_hist(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), col_ref(col), full, t->nrows, P, hist, dcnt); }
-      HIP_CHECK(hipMemcpyAsync(h.data(), hist, used * 8, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));            // (`h` is pageable host memory)
-      if (P.first) {
-        for (int k = 0; k < 3; k++) cnt[k] = (int64_t)h[(size_t)kSelectMaxRanks * 256 + k];
-        for (int i = 0; i < nranks; i++)
-          if (ranks[i] < 1 || ranks[i] > cnt[0]) fail(DFDB_ERR_BOUNDS, "BoundsError: rank %lld of %lld ordered values", (long long)ranks[i], (long long)cnt[0]);
-      }
-      for (int i = 0; i < nranks; i++) {             // the bin that holds rank i of its group; the rank becomes relative to it
-        const uint64_t* hg = h.data() + (size_t)grp[i] * 256;
-        int b = 0;
-        while (b < 256 && (uint64_t)rel[i] > hg[b]) { rel[i] -= (int64_t)hg[b]; b++; }
-        if (b == 256) fail(DFDB_ERR_DEVICE, "order statistics: the histogram of key bits %d.. holds fewer rows than the rank", shift);
-        prefix[i] = (prefix[i] << 8) | (uint64_t)b;
-      }
-      if (nranks == 0) break;                        // the counts are all that was asked for
+  else select_keys(q, col, full, true, nranks, cnt, [&](SelectRanks& R) {
+    for (int i = 0; i < nranks; i++) {
+      if (ranks[i] < 1 || ranks[i] > cnt[0]) fail(DFDB_ERR_BOUNDS, "BoundsError: rank %lld of %lld ordered values", (long long)ranks[i], (long long)cnt[0]);
+      R.rank[i] = ranks[i];
     }
-  }
+    R.n = nranks;
+  }, keys);
   for (int i = 0; i < nranks; i++) {
-    const uint64_t bits = select_key_value(dt, full, prefix[i]);
+    const uint64_t bits = select_key_value(dt, full, keys[i]);
     if (kind == kAccFloat) { if (out_f) out_f[i] = bits_f64(bits); }
     else { if (out_i) out_i[i] = (int64_t)bits; if (out_f) out_f[i] = kind == kAccUnsigned ? (double)bits : (double)(int64_t)bits; }
   }

@@ -818,6 +818,50 @@ class _Query:
             out = out != 0
         return out, (int(cnt[0]), int(cnt[1]), int(cnt[2]))
 
+    def sort_indices(self, col: int = 0, rev: bool = False, limit: Optional[int] = None, dev_ptr: Optional[int] = None, cap: Optional[int] = None):
+        """dfdb_sort_indices: (rows, info) — the 1-based table rows of the selected rows in the stable order of projection column `col` (rev: descending;
+        ties keep ascending row order both ways; missing rows last, first under rev), cut to the first `limit`; info = (selected rows, pairs sorted,
+        digit passes run, digit passes skipped).  dev_ptr: write into device memory holding `cap` entries instead, without a count: (None, info)"""
+        L = N.load()
+        flags, lim = (N.SORT_REV if rev else 0), (-1 if limit is None else int(limit))
+        info = np.zeros(4, np.int64)
+        if dev_ptr is not None:
+            N.check(L.dfdb_sort_indices(self._h, col, flags, lim, C.c_void_p(dev_ptr), int(cap), N.MEM_DEVICE, None, info.ctypes.data))
+            return None, tuple(int(x) for x in info)
+        n = self.count() if lim < 0 else min(lim, self.count())
+        out = np.empty(n, np.int64)
+        got = C.c_int64()
+        N.check(L.dfdb_sort_indices(self._h, col, flags, lim, out.ctypes.data if n else None, n, N.MEM_HOST, C.byref(got), info.ctypes.data))
+        return out[:got.value], tuple(int(x) for x in info)
+
+    def gather_rows(self, rows=None, dev_ptr: Optional[int] = None, n: Optional[int] = None) -> List[Any]:
+        """dfdb_gather_rows: the view's (fixed-width) projection columns at the 1-based table `rows`, in that order — any order, repeats allowed, whatever the
+        selection; nullable columns come back masked.  dev_ptr / n: the rows lie in device memory (the device output of sort_indices)"""
+        L = N.load()
+        if dev_ptr is None:
+            rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
+            n, ptr, kind = len(rows), (rows.ctypes.data if len(rows) else None), N.MEM_HOST
+        else:
+            n, ptr, kind = int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
+        ncols = len(self.view.projection)
+        outs = (N.OutCol * max(ncols, 1))()
+        keep = []
+        for i in range(ncols):
+            dt = self.coltype(i)
+            o = outs[i]
+            o.memkind = N.MEM_HOST
+            if (dt & ir.DTYPE_MASK) == ir.STRING:
+                keep.append((dt, None, None))              # (refused by the library, by name)
+                continue
+            arr = np.empty(max(n, 1), ir.numpy_of_dtype(dt))
+            miss = np.zeros(max(n, 1), np.uint8) if dt & ir.NULLABLE else None
+            keep.append((dt, arr, miss))
+            o.data = arr.ctypes.data
+            if miss is not None:
+                o.missing = miss.ctypes.data
+        N.check(L.dfdb_gather_rows(self._h, ptr, n, kind, outs, ncols))
+        return [np.ma.masked_array(a[:n].copy(), mask=m[:n].astype(bool)) if m is not None else a[:n].copy() for _, a, m in keep]
+
 
 class _ChunkQuery(_Query):
     """One chunk of a streamed view: the engine owns the handle (valid until the stream advances)."""
@@ -1174,6 +1218,19 @@ class DFColumn:
                 out[k] = a + g * (b - a) if np.isfinite(a) and np.isfinite(b) else (1 - g) * a + g * b
         return float(out[0]) if np.ndim(p) == 0 else out
 
+    # -- ordering: sortperm / partialsortperm / sort, which the reference answers by collecting Base.iterate(::DFColumn) (column.jl:102-126) and sorting on
+    # the host; here the device sorts {key, row} pairs (dfdb_sort_indices, csrc/k_sort.hip) and gathers the values in that order (dfdb_gather_rows)
+    def sortperm(self, rev: bool = False, limit: Optional[int] = None) -> np.ndarray:
+        """the 1-based TABLE rows of the selected rows in sorted order (stable; rev reverses the ordering, not the ties; missing last, first under rev),
+        the first `limit` of them when given"""
+        return self.view._query().sort_indices(0, rev, limit)[0]
+
+    def sort(self, rev: bool = False, limit: Optional[int] = None):
+        """sort(collect(col); rev) — the first `limit` values of it when given —, missing values as materialize gives them"""
+        q = self.view._query()
+        rows, _ = q.sort_indices(0, rev, limit)
+        return _to_user(q.gather_rows(rows)[0], _logicals(self.view)[0])
+
     # -- broadcasting (columnbroadcast.jl:19-62): every DFColumn argument must share (table, selection)
     def _bc(self, op: int, other, swap: bool = False) -> "DFColumn":
         if isinstance(other, DFColumn):
@@ -1220,6 +1277,22 @@ class DFColumn:
 
 def median(c: DFColumn): return c.median()                # Statistics.median(col)
 def quantile(c: DFColumn, p): return c.quantile(p)        # Statistics.quantile(col, p)
+
+
+def sortperm(c: DFColumn, rev: bool = False, limit: Optional[int] = None): return c.sortperm(rev, limit)      # Base.sortperm(col; rev): table rows
+def sort(c: DFColumn, rev: bool = False, limit: Optional[int] = None): return c.sort(rev, limit)              # Base.sort(col; rev)
+def partialsortperm(c: DFColumn, k: int, rev: bool = False): return c.sortperm(rev, k)                        # Base.partialsortperm(col, 1:k; rev)
+
+
+def sort_view(v: Union[DFView, DFTable], by: str, rev: bool = False, limit: Optional[int] = None):
+    """sort!(materialize(v), by; rev) (first(.., limit) when given): the view's projection columns — fixed-width ones — in the order of its column `by`"""
+    if isinstance(v, DFTable):
+        v = DFView(v)
+    import pandas as pd
+    q = v._query()
+    rows, _ = q.sort_indices(list(v.projection.keys()).index(by), rev, limit)
+    lg = _logicals(v)
+    return pd.DataFrame({k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(v.projection.keys(), q.gather_rows(rows)))})
 
 
 def col_equal(a: DFColumn, b: DFColumn) -> bool:

@@ -689,6 +689,61 @@ function gpu_quantile(c::DFColumn, p::Union{Real,AbstractVector{<:Real}})
     return p isa Real ? out[1] : out
 end
 
+const SORTABLE = Union{Int8,Int16,Int32,Int64,UInt8,UInt16,UInt32,UInt64,Bool,Float32,Float64}
+
+# the sorted table rows of query q's projection column 0 (dfdb_sort_indices): limit < 0 = all of them
+function sort_rows(q, rev::Bool, limit::Integer)
+    n = Ref{Int64}(0)
+    check(ccall((:dfdb_count, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}), q, n))
+    m = limit < 0 ? n[] : min(limit, n[])
+    rows = Vector{Int64}(undef, m); got = Ref{Int64}(0)
+    check(ccall((:dfdb_sort_indices, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}),
+                q, 0, rev ? 1 : 0, limit < 0 ? -1 : limit, rows, m, 0, got, C_NULL))
+    rows
+end
+
+"""
+    gpu_sortperm(c::DFColumn; rev = false, limit = -1) -> Vector{Int64}
+
+The 1-based TABLE rows of the selected rows of `c` in the order `sortperm(collect(c); rev)` gives them — the first `limit` of them when limit >= 0
+(`partialsortperm`) —: dfdb_sort_indices, a stable radix sort of {key, row} pairs on the device.  `isless` order (floats -Inf .. -0.0 < 0.0 .. Inf < NaN),
+ties in ascending row order in both directions, `missing` last (first under `rev`).  The reference collects the column through Base.iterate(::DFColumn)
+(column.jl:102-126) and sorts on the host.  The sharded form, a view that stays on disk and a compressed-only column are `Unsupported`.
+"""
+function gpu_sortperm(c::DFColumn{T}; rev::Bool = false, limit::Integer = -1) where {T}
+    Base.nonmissingtype(T) <: SORTABLE || throw(Unsupported("sorting by a column of $(T)"))
+    sharded() && throw(Unsupported("sorting over a sharded table"))
+    with_query(q -> sort_rows(q, rev, limit), c.view)
+end
+
+"`sort(collect(c); rev)` (its first `limit` values when limit >= 0): the values gathered on the device in the order of gpu_sortperm (dfdb_gather_rows)"
+function gpu_sort(c::DFColumn{T}; rev::Bool = false, limit::Integer = -1) where {T}
+    Base.nonmissingtype(T) <: SORTABLE || throw(Unsupported("sorting a column of $(T)"))
+    sharded() && throw(Unsupported("sorting over a sharded table"))
+    with_query(c.view) do q
+        rows = sort_rows(q, rev, limit)
+        outs, bufs = alloc_outputs(c.view, length(rows), i -> begin
+            dt = Ref{Int32}(0)
+            check(ccall((:dfdb_query_coltype, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), q, i, dt)); dt[]
+        end, i -> 0)
+        GC.@preserve bufs outs check(ccall((:dfdb_gather_rows, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64, Int32, Ptr{OutCol}, Int32),
+                                           q, rows, length(rows), 0, outs, length(outs)))
+        finish_columns(c.view, bufs)[1]
+    end
+end
+
+# the stock path of the three overrides in enable!(): the column collected through the reference's own iteration, sorted on the host.  Defined with the module,
+# so they exist in the world age the fallback dispatches in
+stock_sort(c, rev) = sort(collect(c); rev = rev)
+stock_sortperm(c, rev) = sortperm(collect(c); rev = rev)
+stock_partialsortperm(c, k, rev) = partialsortperm(collect(c), k; rev = rev)
+
+# Base.sortperm / partialsortperm number the elements of collect(c): the table rows are those numbers only when the column's selection queue is empty
+function positions_of(c::DFColumn, rows::Vector{Int64})
+    isempty(c.view.selection) || throw(Unsupported("sortperm of a column under a selection (its positions are not table rows)"))
+    rows
+end
+
 """
 groupreduce(view, (:by,); out = :col => Stat()) on the device (src/tables/aggregate.jl:1-36: exported by the reference, unfinished there — it numbers the
 groups in order of first appearance and stops).  Returns a DataFrame with one row per distinct value of `by` in order of first appearance, the group's
@@ -856,7 +911,7 @@ end
 """
 Route the hot-path consumers of DataFrameDBs through the MI355X engine, falling back to the stock path when an expression is outside the IR:
 `materialize(::DFView)`, `nrow(::DFView)` (and with it `size` / `length(::DFColumn)`), `materialize(::DFColumn)`, `copyto!(dest, ::DFColumn)`,
-`copyto!(dest, ::Broadcasted{DFColumnStyle})` (`dest .= col_expr`), and `sum` / `minimum` / `maximum` / `Statistics.mean` / `Statistics.median` / `Statistics.quantile` / `unique` of a DFColumn
+`copyto!(dest, ::Broadcasted{DFColumnStyle})` (`dest .= col_expr`), and `sum` / `minimum` / `maximum` / `Statistics.mean` / `Statistics.median` / `Statistics.quantile` / `unique` / `sort` / `sortperm` / `partialsortperm` of a DFColumn
 (which otherwise pull one element at a time through `Base.iterate(::DFColumn)`, column.jl:102-126).
 """
 function enable!()
@@ -890,6 +945,10 @@ function enable!()
         Base.unique(c::DFColumn) = with_fallback(() -> gpu_unique(c), Base.unique, c)
         Statistics.median(c::DFColumn) = with_fallback(() -> gpu_median(c), Statistics.median, c)
         Statistics.quantile(c::DFColumn, p) = with_fallback(() -> gpu_quantile(c, p), Statistics.quantile, c, p)
+        Base.sortperm(c::DFColumn; rev::Bool = false) = with_fallback(() -> positions_of(c, gpu_sortperm(c; rev = rev)), stock_sortperm, c, rev)
+        Base.sort(c::DFColumn; rev::Bool = false) = with_fallback(() -> gpu_sort(c; rev = rev), stock_sort, c, rev)
+        Base.partialsortperm(c::DFColumn, k::Integer; rev::Bool = false) =
+            with_fallback(() -> positions_of(c, gpu_sortperm(c; rev = rev, limit = k))[k], stock_partialsortperm, c, k, rev)
     end
     ENABLED[] = true
     nothing

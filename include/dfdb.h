@@ -119,6 +119,7 @@ int32_t dfdb_jit_cache_dir(char* buf, size_t cap);
  *   2 order_image (parameter: accumulator kind, 0 signed / 1 unsigned / 2 float), 3 minmax_f64 over the pairs out[2i], out[2i + 1] (the result in out[2i]),
  *   4 int_lo, 5 int_hi and 6 wrap_int (parameter: dtype; 4 and 5 ignore the operand), 7 value_kind (dtype), 8 kind_dtype (kind), 9 the reduction identity of
  *   the DFDB_AGG_* operator in the operand (parameter: kind).
+ *   "sort_geometry": the chunk geometry of dfdb_sort_indices' passes (csrc/k_sort.hip): out[0..1] = pairs per chunk, threads per workgroup.
  * An unknown name is ArgumentError. */
 int32_t dfdb_selftest(const char* name, int64_t arg, int64_t* out, int32_t nout);
 int32_t dfdb_device_count(int32_t* n);   /* visible HIP devices (0 without a GPU: no error); the Julia shim forms a group when n > 1 */
@@ -407,6 +408,35 @@ int32_t dfdb_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, dou
  * sharded form over a dfdb_group; all three are follow-ups.  The query's selection is left as it was found;
  * dfdb_query_reset / _execute mean what they meant. */
 int32_t dfdb_order_statistics(dfdb_query* q, int32_t proj_col, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts);
+/* sortperm(collect(col)) / partialsortperm over the selected rows: their 1-based table row numbers in the order of projection column proj_col, by a
+ * stable least-significant-digit radix sort of {key, row} pairs on the device (csrc/k_sort.hip).  The answer is unique — it does not depend on grid size,
+ * launch order or timing.
+ *   order    rows that are not missing by isless of their values (integers by value, floats -Inf .. -0.0 < 0.0 .. Inf, every NaN last), descending with
+ *            DFDB_SORT_REV.  Ties stay in ascending row order in BOTH directions (sortperm is stable; rev reverses the ordering, not the ties).  Missing
+ *            rows come after all others, before them with DFDB_SORT_REV (isless(x, missing)), in ascending row order among themselves; the bytes under a
+ *            missing bit are never read (quirk Q11).
+ *   limit    < 0: every selected row; >= 0: the first min(limit, selected) entries of that same order.  The device then sorts only the rows that can be
+ *            among them: with L of the first `limit` entries not missing, the rows whose key does not exceed the key of rank L in the sort direction
+ *            (found by the radix select of dfdb_order_statistics); stability makes the cut at `limit` pick the smallest rows among tied keys.
+ *   out, n   as dfdb_select_indices: *n receives the length of the result, min(limit, selected) (selected when limit < 0); the first min(*n, cap) entries
+ *            are written to `out` in host or device memory (memkind); n may be NULL.
+ *   info     [4] (may be NULL): selected rows, pairs sorted (the rows kept after the cut), digit passes run, digit passes skipped.  A pass covers 8 key
+ *            bits; a key has as many bytes as the column's values are wide, and the pass of a byte that has one value in every pair is skipped.
+ *   column   as dfdb_order_statistics takes it: a plain numeric or Bool column, nullable or not, resident and decoded.  DFDB_ERR_UNSUPPORTED with a
+ *            message that names the form for a String column, a computed column (materialise it as a column first: dfdb_table_add_from_query), a view
+ *            that is out of core, a compressed-only column, and a table of 2^31 rows or more (rows travel in 32 bits); DFDB_ERR_BOUNDS for a proj_col
+ *            the view does not have; DFDB_ERR_NOMEM when the pairs (2 x 12 bytes per sorted row) do not fit.
+ * The query's selection is left as it was found.  Sorting by several keys composes — sort by the minor key first — but has no entry point yet, like the
+ * sharded form. */
+enum { DFDB_SORT_REV = 1 };
+int32_t dfdb_sort_indices(dfdb_query* q, int32_t proj_col, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info);
+/* the projection at the 1-based table rows rows[0 .. n), in that order: any order, repeats allowed, independent of the query's selection (with
+ * dfdb_sort_indices: sort(collect(col)), sort!(materialize(v), :col)).  `rows` lies in host or device memory (rows_memkind): the device output of
+ * dfdb_sort_indices feeds it without leaving the device.  outs[i] (ncols = the view's columns) receives projection column i: data, missing bytes, count = n
+ * and dtype as dfdb_materialize fills them.  Every column must be a plain fixed-width column, resident and decoded: a String or computed column and the
+ * out-of-core and compressed-only forms are DFDB_ERR_UNSUPPORTED with a message that names the form.  A row outside 1..nrows is DFDB_ERR_BOUNDS, and nothing
+ * is written for that row. */
+int32_t dfdb_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols);
 
 /* ---- out of core behind the ordinary entry points (round 6) ----
  * The reference never holds more than one block per column (src/io/blocksiterator.jl:98-121, src/io/BlockStreams.jl:9-15; "memory use is O(block)",
