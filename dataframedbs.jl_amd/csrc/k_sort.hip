@@ -1,4 +1,5 @@
-// k_sort.hip — K12: stable sortperm of the selected rows by one fixed-width column, and the gather that follows a row list (gfx950).
+// k_sort.hip — K12: stable sortperm of the selected rows by one fixed-width column (by several: one key after another, k_sort_rekey below), and the gather that
+// follows a row list (gfx950).
 //
 // Replaces sortperm(collect(col)) / partialsortperm / sort over Base.iterate(::DFColumn) (src/tables/column.jl:102-126): the reference collects the selected
 // values one element at a time and sorts them on the host.
@@ -62,6 +63,21 @@ __device__ __forceinline__ uint64_t match_digit(uint32_t d, bool valid) {
   return m;
 }
 
+// the wave's kept keys (kmask: their lanes) into the per-byte digit histograms hist[byte * 256 + digit] in LDS
+template <int NB>
+__device__ __forceinline__ void hist_add_keys(uint32_t* hist, uint64_t key, bool kept, uint64_t kmask, int lane) {
+  if (kmask == 0) return;
+  const int src = __ffsll((unsigned long long)kmask) - 1;
+#pragma unroll
+  for (int b = 0; b < NB; b++) {
+    const uint32_t d = (uint32_t)(key >> (8 * b)) & 255u;
+    const uint32_t d0 = (uint32_t)__shfl((int)d, src, 64);
+    if (__ballot(kept && d != d0) == 0) {                        // one digit in the whole wave: one add
+      if (lane == src) atomicAdd(&hist[b * 256 + d0], (uint32_t)__popcll(kmask));
+    } else if (kept) atomicAdd(&hist[b * 256 + d], 1u);
+  }
+}
+
 // PHASE 0: the kept and the missing selected rows per tile -> B.live_cnt / B.miss_cnt (zeroed by the caller: dead tiles write nothing)
 // PHASE 1: the pairs, the missing rows' list, the per-byte histograms
 template <int DT, int PHASE>
@@ -113,17 +129,7 @@ __global__ __launch_bounds__(kSortBlock) void k_sort_build(const typename SelT<D
           const uint64_t pos = mbase + mrun + (uint32_t)__popcll(mmask & below);
           if (pos < (uint64_t)B.miss_cap) B.miss_rows[pos] = row;
         }
-        if (kmask != 0) {
-          const int src = __ffsll((unsigned long long)kmask) - 1;
-#pragma unroll
-          for (int b = 0; b < NB; b++) {
-            const uint32_t d = (uint32_t)(key >> (8 * b)) & 255u;
-            const uint32_t d0 = (uint32_t)__shfl((int)d, src, 64);
-            if (__ballot(kept && d != d0) == 0) {                // one digit in the whole wave: one add
-              if (lane == src) atomicAdd(&hist[b * 256 + d0], (uint32_t)__popcll(kmask));
-            } else if (kept) atomicAdd(&hist[b * 256 + d], 1u);
-          }
-        }
+        hist_add_keys<NB>(hist, key, kept, kmask, lane);
       }
       lrun += (uint32_t)__popcll(kmask); mrun += (uint32_t)__popcll(mmask);
     }
@@ -148,7 +154,101 @@ void launch_sort_build(hipStream_t s, const ColRef& col, const SortBuild& B, boo
   });
 }
 
-// one workgroup per chunk: counts[bin * nchunks + chunk] = the chunk's pairs whose key bits [shift, shift + 8) are `bin`
+// REKEY (k_sort_rekey): the build of the NEXT key of a sort by several columns — it starts from a row order instead of the selection.  One wave owns 1024
+// consecutive entries of `order` in 16 rounds of 64, lane = entry: 16 coalesced loads of the entries, then the 16 loads of the rows' missing words (32-bit
+// halves of the bitmap's words), then the 16 column loads of the live entries — two rounds of gathers, each 16 deep.  The positions are the build's
+// arithmetic over the list: base of the tile + the running count in the wave + the popcount of the ballot below the lane, so pairs and missing rows keep
+// the order they have in `order`.  An entry at or beyond n does nothing; a row that is not < nrows is treated as absent (a guard: no list made here has one).
+// PHASE 0: the live and the missing entries per tile -> R.live_cnt / R.miss_cnt (every tile writes)
+// PHASE 1: the pairs, the missing rows' list, the per-byte histograms
+//   algorithmic bytes / entry: 4 (order) + 12 written; what it MOVES is a 128-byte line per gathered value (and per missing word) when the rows are scattered
+template <int DT, int PHASE>
+__global__ __launch_bounds__(kSortBlock) void k_sort_rekey(const typename SelT<DT>::type* __restrict__ col, const uint64_t* __restrict__ missing, SortRekey R) {
+  using T = typename SelT<DT>::type;
+  constexpr int NB = select_key_bits(DT, false) / 8;
+  __shared__ uint32_t hist[PHASE == 1 ? NB * 256 : 1];
+  if (PHASE == 1) {
+    for (int i = threadIdx.x; i < NB * 256; i += kSortBlock) hist[i] = 0;
+    __syncthreads();
+  }
+  const int lane = lane_id();
+  const uint64_t below = (1ull << lane) - 1ull;
+  const int64_t wave = (int64_t)blockIdx.x * kSortWaves + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * kSortWaves;
+  const int64_t ntiles = (R.n + 1023) / 1024;
+  const uint32_t* mhalf = (const uint32_t*)missing;              // little-endian: bit (r & 31) of half (r >> 5) is bit (r & 63) of word (r >> 6)
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    const int64_t e0 = tile * 1024 + lane;
+    uint32_t r[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int64_t i = e0 + j * 64;
+      r[j] = i < R.n ? __builtin_nontemporal_load(R.order + i) : 0xffffffffu;
+    }
+    uint32_t mh[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      mh[j] = 0;
+      if (missing && (int64_t)r[j] < R.nrows) mh[j] = mhalf[r[j] >> 5];
+    }
+    uint32_t pres = 0, miss = 0;                                 // bit j: entry j of this lane is there / is missing in this column
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      if ((int64_t)r[j] < R.nrows) pres |= 1u << j;
+      if ((mh[j] >> (r[j] & 31u)) & 1u) miss |= 1u << j;
+    }
+    const uint32_t livem = pres & ~miss;
+    T v[PHASE == 1 ? 16 : 1];
+    if (PHASE == 1) {
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        v[j] = T(0);
+        if ((livem >> j) & 1u) v[j] = col[r[j]];                 // the live entries only (a row of the table, never under a missing bit)
+      }
+    }
+    uint32_t lrun = 0, mrun = 0;                                 // wave-uniform: live / missing entries of the tile so far
+    uint64_t lbase = 0, mbase = 0;
+    if (PHASE == 1) { lbase = R.live_base ? R.live_base[tile] : (uint64_t)tile * 1024; mbase = R.miss_base ? R.miss_base[tile] : 0ull; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const bool live = (livem >> j) & 1u;
+      const uint64_t kmask = __ballot(live), mmask = __ballot((miss >> j) & 1u);
+      if (PHASE == 1) {
+        const uint64_t key = select_key<DT, false>(&v[j]) ^ R.flip;
+        if (live) {
+          const uint64_t pos = lbase + lrun + (uint32_t)__popcll(kmask & below);
+          if (pos < (uint64_t)R.cap) { R.keys[pos] = key; R.rows[pos] = r[j]; }
+        }
+        if ((mmask >> lane) & 1ull) {
+          const uint64_t pos = mbase + mrun + (uint32_t)__popcll(mmask & below);
+          if (pos < (uint64_t)R.miss_cap) R.miss_rows[pos] = r[j];
+        }
+        hist_add_keys<NB>(hist, key, live, kmask, lane);
+      }
+      lrun += (uint32_t)__popcll(kmask); mrun += (uint32_t)__popcll(mmask);
+    }
+    if (PHASE == 0 && lane == 0) { R.live_cnt[tile] = lrun; R.miss_cnt[tile] = mrun; }
+  }
+  if (PHASE == 1) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < NB * 256; i += kSortBlock) { const uint32_t h = hist[i]; if (h) atomicAdd(&R.ghist[i], (unsigned long long)h); }
+  }
+}
+
+void launch_sort_rekey(hipStream_t s, const ColRef& col, const SortRekey& R, bool count_phase) {
+  const int64_t ntiles = (R.n + 1023) / 1024;
+  if (ntiles < 1) return;
+  int grid = (int)((ntiles + kSortWaves - 1) / kSortWaves);
+  if (grid > kSortBuildBlocks) grid = kSortBuildBlocks;
+  with_dtype<DtValues>(col.dtype, [&](auto c) {      // (Bool as DFDB_U8)
+    constexpr int DT = decltype(c)::dtype;
+    using T = typename SelT<DT>::type;
+    if (count_phase) hipLaunchKernelGGL((k_sort_rekey<DT, 0>), dim3(grid), dim3(kSortBlock), 0, s, (const T*)col.data, col.missing, R);
+    else hipLaunchKernelGGL((k_sort_rekey<DT, 1>), dim3(grid), dim3(kSortBlock), 0, s, (const T*)col.data, col.missing, R);
+  });
+}
+
+// one workgroup per chunk: counts[bin * nchunks + chunk] =the chunk's pairs whose key bits [shift, shift + 8) are `bin`
 __global__ __launch_bounds__(kSortBlock) void k_sort_count(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ counts, int64_t nchunks) {
   __shared__ uint32_t hist[256];
   hist[threadIdx.x] = 0;

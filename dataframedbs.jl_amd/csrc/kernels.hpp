@@ -205,6 +205,19 @@ struct SortBuild {
   unsigned long long* ghist;
 };
 void launch_sort_build(hipStream_t s, const ColRef& col, const SortBuild& B, bool count_phase);
+// The build that starts from a row order (the next key of a sort by several columns): order[0 .. n) holds 0-based rows; every entry whose row is not
+// missing in `col` becomes a pair {key ^ flip, row}, every other one goes to miss_rows, both IN THE ORDER OF `order`: entry i of 1024-entry tile t lands at
+// live_base[t] (miss_base[t]) + its rank among the tile's live (missing) entries.  live_base null: the column has no missing bitmap and tile t starts at
+// t * 1024 (entry i becomes pair i, one launch).  The count phase fills live_cnt / miss_cnt [ceil(n / 1024)]; the write phase adds to ghist like the build
+struct SortRekey {
+  const uint32_t* order; int64_t n; int64_t nrows;
+  const uint64_t* live_base; const uint64_t* miss_base;
+  uint64_t flip;
+  uint64_t* keys; uint32_t* rows; int64_t cap; uint32_t* miss_rows; int64_t miss_cap;
+  uint32_t* live_cnt; uint32_t* miss_cnt;
+  unsigned long long* ghist;
+};
+void launch_sort_rekey(hipStream_t s, const ColRef& col, const SortRekey& R, bool count_phase);
 void sort_geometry(int64_t out[2]);                  // {pairs per chunk of a pass, threads per workgroup}
 int64_t sort_chunks(int64_t npairs);
 // one pass over key bits [shift, shift + 8): counts [256 * sort_chunks(n)] bin-major, their exclusive scan `starts` (launch_scan_counts), the stable scatter

@@ -1,5 +1,5 @@
-// sort.cpp — ordering on the device: dfdb_sort_indices (the stable sortperm of the selected rows by one projection column, with a limit) and
-// dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip.
+// sort.cpp — ordering on the device: dfdb_sort_indices (the stable sortperm of the selected rows by one projection column, with a limit), dfdb_sort_indices_n
+// (the same by several columns, the most minor key first) and dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip.
 //
 // Replaces sortperm(collect(col)), partialsortperm and sort over Base.iterate(::DFColumn) (src/tables/column.jl:102-126), which pull every selected value to
 // the host.  The host side here plans: which rows are kept (the top-k cut, found with the radix select of k_select.hip), which key bytes order anything (the
@@ -29,12 +29,12 @@ namespace {
 // the sort's device memory: taken from the pool, back to it when the call ends (the stream drained first)
 struct SortScratch {
   dfdb_ctx* ctx;
-  DevBuf keys[2], rows[2], miss_rows, tile_cnt, tile_base, scan_scratch, counts, starts, hist, stage;
+  DevBuf keys[2], rows[2], miss_rows, order, tile_cnt, tile_base, scan_scratch, counts, starts, hist, stage;
   explicit SortScratch(dfdb_ctx* c) : ctx(c) {}
   ~SortScratch() {
     (void)hipStreamSynchronize(ctx->stream);
     RecycleScope rs;
-    for (DevBuf* b : {&keys[0], &keys[1], &rows[0], &rows[1], &miss_rows, &tile_cnt, &tile_base, &scan_scratch, &counts, &starts, &hist, &stage}) b->release();
+    for (DevBuf* b : {&keys[0], &keys[1], &rows[0], &rows[1], &miss_rows, &order, &tile_cnt, &tile_base, &scan_scratch, &counts, &starts, &hist, &stage}) b->release();
   }
 };
 struct SortPlan { int64_t nlive = 0, nmiss = 0, L = 0; bool cut = false; uint64_t cutkey = 0; };
@@ -55,31 +55,28 @@ static SortPlan plan_sort(dfdb_query* q, const Column& col, bool rev, int64_t li
   return P;
 }
 
-void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
+static uint64_t flip_of(int nbits, bool rev) { return rev ? (nbits == 64 ? ~0ull : (1ull << nbits) - 1ull) : 0ull; }
+static void check_sort_flags(int32_t flags) {
   if (flags & ~DFDB_SORT_REV) fail(DFDB_ERR_ARGUMENT, "ArgumentError: sort flags %d (DFDB_SORT_REV is the only one)", flags);
-  const Column& col = ordered_column(q, p, "sorting by");
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+}
+static void check_sort_rows(const dfdb_table* t) {
   if (t->nrows >= (int64_t)1 << 31) fail(DFDB_ERR_UNSUPPORTED, "sorting a table of 2^31 rows or more is not supported: the pairs carry rows in 32 bits");
-  ensure_executed_checked(q);
-  const bool rev = (flags & DFDB_SORT_REV) != 0, nullable = dt_nullable(col.dtype);
-  const int dt = dt_base(col.dtype), nbits = select_key_bits(dt, false), nbytes = nbits / 8;
-  const int64_t sel = query_count(q, -1);
-  const int64_t total = limit < 0 ? sel : std::min(limit, sel);
-  int64_t inf[4] = {sel, 0, 0, nbytes};
-  if (n) *n = total;
-  const int64_t m = std::min(total, std::max<int64_t>(cap, 0));
-  if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
-  if (total == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
+}
 
-  SortScratch S(ctx);
-  const SortPlan P = plan_sort(q, col, rev, limit, sel);
+// The build from the selection: the pairs of the selected rows `col` keeps (not missing; P.cut: key <= the cut; P.L == 0: none) into S.keys[0] / S.rows[0]
+// and the selected missing rows into S.miss_rows, both in table order; the kept keys' per-byte histograms into S.hist.  Returns the pairs; *nmiss: the
+// missing rows.  check: the counts must agree with the plan's
+static int64_t sort_build_pairs(dfdb_query* q, const Column& col, SortScratch& S, bool rev, const SortPlan& P, bool check, int64_t sel, int64_t* nmiss) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const int nbits = select_key_bits(dt_base(col.dtype), false);
   const int64_t ntiles = ceil_div(t->nrows, kTileRows);
-  const uint64_t flip = rev ? (nbits == 64 ? ~0ull : (1ull << nbits) - 1ull) : 0ull;
+  const uint64_t flip = flip_of(nbits, rev);
   SortBuild B{};
   B.bitmap = q->bitmap.as<uint64_t>(); B.tile_counts = q->tile_counts.as<uint32_t>(); B.nrows = t->nrows;
   B.flip = flip; B.cut = P.cutkey ^ flip; B.keep = P.L == 0 ? SORT_KEEP_NONE : (P.cut ? SORT_KEEP_CUT : SORT_KEEP_ALL);
   int64_t npairs = sel;
-  if (!nullable && !P.cut) B.live_base = q->prefix.as<uint64_t>();     // every selected row is kept: the selection's own scan places them
+  *nmiss = 0;
+  if (!dt_nullable(col.dtype) && !P.cut) B.live_base = q->prefix.as<uint64_t>();     // every selected row is kept: the selection's own scan places them
   else {                                                                // count the kept and the missing rows per tile, scan both
     S.tile_cnt.ensure((size_t)(ntiles + 8) * 4 * 2); S.tile_base.ensure((size_t)(ntiles + 8) * 8 * 2); S.scan_scratch.ensure(scan_counts_scratch_bytes(ntiles));
     B.live_cnt = S.tile_cnt.as<uint32_t>(); B.miss_cnt = B.live_cnt + (ntiles + 8);
@@ -92,57 +89,171 @@ void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, 
     HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, lb + ntiles, 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar + 1, mb + ntiles, 8, hipMemcpyDeviceToHost, s));
     stream_wait(ctx);
-    npairs = ctx->pinned_scalar[0];
-    if (ctx->pinned_scalar[1] != P.nmiss || npairs < P.L) fail(DFDB_ERR_DEVICE, "sort: the build counted %lld kept and %lld missing rows, the plan has %lld and %lld",
-                                                               (long long)npairs, (long long)ctx->pinned_scalar[1], (long long)P.L, (long long)P.nmiss);
+    npairs = ctx->pinned_scalar[0]; *nmiss = ctx->pinned_scalar[1];
+    if (check && (*nmiss != P.nmiss || npairs < P.L)) fail(DFDB_ERR_DEVICE, "sort: the build counted %lld kept and %lld missing rows, the plan has %lld and %lld",
+                                                           (long long)npairs, (long long)*nmiss, (long long)P.L, (long long)P.nmiss);
     B.live_base = lb; B.miss_base = mb;
   }
-  inf[1] = npairs;
   S.keys[0].ensure((size_t)std::max<int64_t>(npairs, 1) * 8); S.rows[0].ensure((size_t)std::max<int64_t>(npairs, 1) * 4);
-  S.miss_rows.ensure((size_t)std::max<int64_t>(P.nmiss, 1) * 4);
+  S.miss_rows.ensure((size_t)std::max<int64_t>(*nmiss, 1) * 4);
   S.hist.ensure((size_t)(kSelectMaxRanks * 256 + 8) * 8);
   B.keys = S.keys[0].as<uint64_t>(); B.rows = S.rows[0].as<uint32_t>(); B.cap = npairs;
-  B.miss_rows = S.miss_rows.as<uint32_t>(); B.miss_cap = P.nmiss;
+  B.miss_rows = S.miss_rows.as<uint32_t>(); B.miss_cap = *nmiss;
   B.ghist = (unsigned long long*)S.hist.p;
-  HIP_CHECK(hipMemsetAsync(S.hist.p, 0, (size_t)nbytes * 256 * 8, s));
+  HIP_CHECK(hipMemsetAsync(S.hist.p, 0, (size_t)(nbits / 8) * 256 * 8, s));
   { LaunchTimer lt(ctx, "sort_build"); launch_sort_build(s, col_ref(col), B, false); }
+  return npairs;
+}
 
-  // a byte whose histogram has a single non-zero bin orders nothing: its pass is not run
+// The passes over the npairs pairs of S.keys[0] / S.rows[0], by the histograms a build left in S.hist: a byte whose histogram has a single non-zero bin
+// orders nothing and its pass is not run.  Returns the half that holds the sorted pairs; *run: the passes run.  pair_cap >= npairs: the pairs the second half
+// is made for (the most any key of the call has)
+static int sort_run_passes(dfdb_ctx* ctx, SortScratch& S, int64_t npairs, int64_t pair_cap, int nbytes, int64_t* run) {
+  hipStream_t s = ctx->stream;
   int cur = 0;
-  if (npairs > 1) {
-    std::vector<uint64_t> gh((size_t)nbytes * 256);
-    HIP_CHECK(hipMemcpyAsync(gh.data(), S.hist.p, gh.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));              // (`gh` is pageable host memory)
-    const int64_t nchunks = sort_chunks(npairs);
-    for (int b = 0; b < nbytes; b++) {
-      int used = 0;
-      for (int d = 0; d < 256; d++) used += gh[(size_t)b * 256 + (size_t)d] != 0;
-      if (used <= 1) continue;
-      if (!S.keys[1].p) {
-        S.keys[1].ensure((size_t)npairs * 8); S.rows[1].ensure((size_t)npairs * 4);
-        S.counts.ensure((size_t)(256 * nchunks + 8) * 4); S.starts.ensure((size_t)(256 * nchunks + 8) * 8); S.scan_scratch.ensure(scan_counts_scratch_bytes(256 * nchunks));
-      }
-      { LaunchTimer lt(ctx, "sort_count"); launch_sort_count(s, S.keys[cur].as<uint64_t>(), npairs, 8 * b, S.counts.as<uint32_t>()); }
-      { LaunchTimer lt(ctx, "scan_counts"); launch_scan_counts(s, S.counts.as<uint32_t>(), S.starts.as<uint64_t>(), 256 * nchunks, S.scan_scratch.as<uint64_t>()); }
-      { LaunchTimer lt(ctx, "sort_scatter");
-        launch_sort_scatter(s, S.keys[cur].as<uint64_t>(), S.rows[cur].as<uint32_t>(), npairs, 8 * b, S.starts.as<uint64_t>(), S.keys[cur ^ 1].as<uint64_t>(),
-                            S.rows[cur ^ 1].as<uint32_t>()); }
-      cur ^= 1;
-      inf[2]++;
+  *run = 0;
+  if (npairs <= 1) return cur;
+  std::vector<uint64_t> gh((size_t)nbytes * 256);
+  HIP_CHECK(hipMemcpyAsync(gh.data(), S.hist.p, gh.size() * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));              // (`gh` is pageable host memory)
+  const int64_t nchunks = sort_chunks(npairs), cchunks = sort_chunks(pair_cap);
+  for (int b = 0; b < nbytes; b++) {
+    int used = 0;
+    for (int d = 0; d < 256; d++) used += gh[(size_t)b * 256 + (size_t)d] != 0;
+    if (used <= 1) continue;
+    if (!S.keys[1].p) {
+      S.keys[1].ensure((size_t)pair_cap * 8); S.rows[1].ensure((size_t)pair_cap * 4);
+      S.counts.ensure((size_t)(256 * cchunks + 8) * 4); S.starts.ensure((size_t)(256 * cchunks + 8) * 8); S.scan_scratch.ensure(scan_counts_scratch_bytes(256 * cchunks));
     }
+    { LaunchTimer lt(ctx, "sort_count"); launch_sort_count(s, S.keys[cur].as<uint64_t>(), npairs, 8 * b, S.counts.as<uint32_t>()); }
+    { LaunchTimer lt(ctx, "scan_counts"); launch_scan_counts(s, S.counts.as<uint32_t>(), S.starts.as<uint64_t>(), 256 * nchunks, S.scan_scratch.as<uint64_t>()); }
+    { LaunchTimer lt(ctx, "sort_scatter");
+      launch_sort_scatter(s, S.keys[cur].as<uint64_t>(), S.rows[cur].as<uint32_t>(), npairs, 8 * b, S.starts.as<uint64_t>(), S.keys[cur ^ 1].as<uint64_t>(),
+                          S.rows[cur ^ 1].as<uint32_t>()); }
+    cur ^= 1;
+    ++*run;
   }
+  return cur;
+}
+
+// first[0 .. first_n) then second[0 .. second_n) as 1-based table rows into the caller's buffer (first_n + second_n = m entries, host or device memory)
+static void sort_emit_rows(dfdb_table* t, SortScratch& S, const uint32_t* first, int64_t first_n, const uint32_t* second, int64_t second_n, int64_t* out, int32_t memkind) {
+  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const int64_t m = first_n + second_n;
+  int64_t* dst = out;
+  if (memkind != DFDB_MEM_DEVICE && m > 0) { S.stage.ensure((size_t)m * 8); dst = S.stage.as<int64_t>(); }
+  { LaunchTimer lt(ctx, "sort_emit");
+    launch_sort_emit(s, first, first_n, dst, t->row_base);
+    launch_sort_emit(s, second, second_n, dst + first_n, t->row_base); }
+  if (memkind != DFDB_MEM_DEVICE && m > 0) { HIP_CHECK(hipMemcpyAsync(out, dst, (size_t)m * 8, hipMemcpyDeviceToHost, s)); stream_wait(ctx); }
+}
+
+void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
+  check_sort_flags(flags);
+  const Column& col = ordered_column(q, p, "sorting by");
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
+  check_sort_rows(t);
+  ensure_executed_checked(q);
+  const bool rev = (flags & DFDB_SORT_REV) != 0;
+  const int nbytes = select_key_bits(dt_base(col.dtype), false) / 8;
+  const int64_t sel = query_count(q, -1);
+  const int64_t total = limit < 0 ? sel : std::min(limit, sel);
+  int64_t inf[4] = {sel, 0, 0, nbytes};
+  if (n) *n = total;
+  const int64_t m = std::min(total, std::max<int64_t>(cap, 0));
+  if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
+  if (total == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
+
+  SortScratch S(ctx);
+  const SortPlan P = plan_sort(q, col, rev, limit, sel);
+  int64_t nmiss = 0;
+  const int64_t npairs = sort_build_pairs(q, col, S, rev, P, true, sel, &nmiss);
+  inf[1] = npairs;
+  const int cur = sort_run_passes(ctx, S, npairs, npairs, nbytes, &inf[2]);
   inf[3] = nbytes - inf[2];
 
   // the first `total` of: the sorted live rows, the missing rows behind them (REV: before them) in table order; `m` of them fit the caller's buffer
   const int64_t miss_out = rev ? std::min(total, P.nmiss) : total - std::min(total, P.nlive), live_out = total - miss_out;
-  int64_t* dst = out;
-  if (memkind != DFDB_MEM_DEVICE && m > 0) { S.stage.ensure((size_t)m * 8); dst = S.stage.as<int64_t>(); }
   const int64_t first_n = std::min(m, rev ? miss_out : live_out), second_n = m - first_n;
   const uint32_t* live_rows = S.rows[cur].as<uint32_t>();
-  { LaunchTimer lt(ctx, "sort_emit");
-    launch_sort_emit(s, rev ? S.miss_rows.as<uint32_t>() : live_rows, first_n, dst, t->row_base);
-    launch_sort_emit(s, rev ? live_rows : S.miss_rows.as<uint32_t>(), second_n, dst + first_n, t->row_base); }
-  if (memkind != DFDB_MEM_DEVICE && m > 0) { HIP_CHECK(hipMemcpyAsync(out, dst, (size_t)m * 8, hipMemcpyDeviceToHost, s)); stream_wait(ctx); }
+  sort_emit_rows(t, S, rev ? S.miss_rows.as<uint32_t>() : live_rows, first_n, rev ? live_rows : S.miss_rows.as<uint32_t>(), second_n, out, memkind);
+  if (info) memcpy(info, inf, sizeof inf);
+}
+
+// The sort by several keys, least significant first: the most minor key is sorted from the selection like a single key; every further key towards the
+// major one is built from the ORDER the keys behind it left (k_sort_rekey) and sorted by the same stable passes, so rows equal in it keep that order.
+// After each key its sorted live rows and its missing rows (behind them, REV: before them) are laid into S.order — the next key's input
+void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
+                          int64_t* n, int64_t* info) {
+  if (nkeys < 1 || nkeys > DFDB_SORT_MAX_KEYS) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %d sort keys (1 to %d)", nkeys, (int)DFDB_SORT_MAX_KEYS);
+  if (!proj_cols || !flags) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no sort %s", proj_cols ? "flags" : "columns");
+  if (nkeys == 1) return query_sort_indices(q, proj_cols[0], flags[0], limit, out, cap, memkind, n, info);
+  for (int32_t j = 0; j < nkeys; j++) check_sort_flags(flags[j]);
+  const Column* cols[DFDB_SORT_MAX_KEYS];
+  for (int32_t j = 0; j < nkeys; j++) cols[j] = &ordered_column(q, proj_cols[j], "sorting by");
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  check_sort_rows(t);
+  ensure_executed_checked(q);
+  const int64_t sel = query_count(q, -1);
+  const int64_t total = limit < 0 ? sel : std::min(limit, sel);
+  int64_t inf[4] = {sel, 0, 0, 0};
+  for (int32_t j = 0; j < nkeys; j++) inf[3] += select_key_bits(dt_base(cols[j]->dtype), false) / 8;
+  if (n) *n = total;
+  const int64_t m = std::min(total, std::max<int64_t>(cap, 0));
+  if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
+  if (sel == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
+
+  SortScratch S(ctx);
+  S.keys[0].ensure((size_t)sel * 8); S.rows[0].ensure((size_t)sel * 4); S.miss_rows.ensure((size_t)sel * 4); S.order.ensure((size_t)sel * 4);
+  const int64_t otiles = ceil_div(sel, kTileRows);
+  const uint32_t *first = nullptr, *second = nullptr;      // the key's two lists in output order, first_len rows in the first
+  int64_t first_len = 0;
+  for (int32_t j = nkeys - 1; j >= 0; j--) {
+    const Column& col = *cols[j];
+    const bool rev = (flags[j] & DFDB_SORT_REV) != 0;
+    const int nbits = select_key_bits(dt_base(col.dtype), false), nbytes = nbits / 8;
+    int64_t npairs = sel, nmiss = 0;
+    if (j == nkeys - 1) {
+      SortPlan all; all.L = sel;                            // no cut: every selected row that is not missing is kept
+      npairs = sort_build_pairs(q, col, S, rev, all, false, sel, &nmiss);
+    } else {
+      // lay the key behind into the order this one starts from
+      uint32_t* order = S.order.as<uint32_t>();
+      { LaunchTimer lt(ctx, "sort_order");
+        if (first_len > 0) HIP_CHECK(hipMemcpyAsync(order, first, (size_t)first_len * 4, hipMemcpyDeviceToDevice, s));
+        if (sel > first_len) HIP_CHECK(hipMemcpyAsync(order + first_len, second, (size_t)(sel - first_len) * 4, hipMemcpyDeviceToDevice, s)); }
+      SortRekey R{};
+      R.order = order; R.n = sel; R.nrows = t->nrows; R.flip = flip_of(nbits, rev);
+      if (dt_nullable(col.dtype)) {                         // count the live and the missing entries per 1024 entries of the order, scan both
+        S.tile_cnt.ensure((size_t)(otiles + 8) * 4 * 2); S.tile_base.ensure((size_t)(otiles + 8) * 8 * 2); S.scan_scratch.ensure(scan_counts_scratch_bytes(otiles));
+        R.live_cnt = S.tile_cnt.as<uint32_t>(); R.miss_cnt = R.live_cnt + (otiles + 8);
+        { LaunchTimer lt(ctx, "sort_rekey"); launch_sort_rekey(s, col_ref(col), R, true); }
+        uint64_t* lb = S.tile_base.as<uint64_t>(); uint64_t* mb = lb + (otiles + 8);
+        { LaunchTimer lt(ctx, "scan_counts");
+          launch_scan_counts(s, R.live_cnt, lb, otiles, S.scan_scratch.as<uint64_t>());
+          launch_scan_counts(s, R.miss_cnt, mb, otiles, S.scan_scratch.as<uint64_t>()); }
+        HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, lb + otiles, 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar + 1, mb + otiles, 8, hipMemcpyDeviceToHost, s));
+        stream_wait(ctx);
+        npairs = ctx->pinned_scalar[0]; nmiss = ctx->pinned_scalar[1];
+        if (npairs + nmiss != sel) fail(DFDB_ERR_DEVICE, "sort: the rekey counted %lld live and %lld missing rows of %lld", (long long)npairs, (long long)nmiss, (long long)sel);
+        R.live_base = lb; R.miss_base = mb;
+      }
+      R.keys = S.keys[0].as<uint64_t>(); R.rows = S.rows[0].as<uint32_t>(); R.cap = npairs;
+      R.miss_rows = S.miss_rows.as<uint32_t>(); R.miss_cap = nmiss;
+      R.ghist = (unsigned long long*)S.hist.p;
+      HIP_CHECK(hipMemsetAsync(S.hist.p, 0, (size_t)nbytes * 256 * 8, s));
+      { LaunchTimer lt(ctx, "sort_rekey"); launch_sort_rekey(s, col_ref(col), R, false); }
+    }
+    int64_t run = 0;
+    const int cur = sort_run_passes(ctx, S, npairs, sel, nbytes, &run);
+    inf[1] += npairs; inf[2] += run; inf[3] -= run;
+    const uint32_t* live_rows = S.rows[cur].as<uint32_t>();
+    first = rev ? S.miss_rows.as<uint32_t>() : live_rows; second = rev ? live_rows : S.miss_rows.as<uint32_t>();
+    first_len = rev ? nmiss : npairs;
+  }
+  const int64_t first_n = std::min(m, first_len);
+  sort_emit_rows(t, S, first, first_n, second, m - first_n, out, memkind);
   if (info) memcpy(info, inf, sizeof inf);
 }
 

@@ -834,6 +834,27 @@ class _Query:
         N.check(L.dfdb_sort_indices(self._h, col, flags, lim, out.ctypes.data if n else None, n, N.MEM_HOST, C.byref(got), info.ctypes.data))
         return out[:got.value], tuple(int(x) for x in info)
 
+    def sort_indices_n(self, cols, revs=None, limit: Optional[int] = None, dev_ptr: Optional[int] = None, cap: Optional[int] = None):
+        """dfdb_sort_indices_n: (rows, info) — the 1-based table rows of the selected rows in the lexicographic order of projection columns cols[0] (major)
+        .. cols[-1] (most minor); revs: one bool per column (None: all ascending).  Every key orders as sort_indices orders it, rows equal in every key keep
+        ascending row order; info = (selected rows, pairs keyed, digit passes run, digit passes skipped), the last three summed over the keys.  dev_ptr / cap
+        as sort_indices takes them"""
+        L = N.load()
+        ci = np.ascontiguousarray(cols, np.int32).reshape(-1)
+        fl = np.zeros(len(ci), np.int32) if revs is None else np.array([N.SORT_REV if r else 0 for r in revs], np.int32)
+        if len(fl) != len(ci):
+            raise ValueError(f"ArgumentError: {len(fl)} rev flags for {len(ci)} sort columns")
+        lim = -1 if limit is None else int(limit)
+        info = np.zeros(4, np.int64)
+        if dev_ptr is not None:
+            N.check(L.dfdb_sort_indices_n(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), lim, C.c_void_p(dev_ptr), int(cap), N.MEM_DEVICE, None, info.ctypes.data))
+            return None, tuple(int(x) for x in info)
+        n = self.count() if lim < 0 else min(lim, self.count())
+        out = np.empty(n, np.int64)
+        got = C.c_int64()
+        N.check(L.dfdb_sort_indices_n(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), lim, out.ctypes.data if n else None, n, N.MEM_HOST, C.byref(got), info.ctypes.data))
+        return out[:got.value], tuple(int(x) for x in info)
+
     def gather_rows(self, rows=None, dev_ptr: Optional[int] = None, n: Optional[int] = None) -> List[Any]:
         """dfdb_gather_rows: the view's (fixed-width) projection columns at the 1-based table `rows`, in that order — any order, repeats allowed, whatever the
         selection; nullable columns come back masked.  dev_ptr / n: the rows lie in device memory (the device output of sort_indices)"""
@@ -1284,13 +1305,37 @@ def sort(c: DFColumn, rev: bool = False, limit: Optional[int] = None): return c.
 def partialsortperm(c: DFColumn, k: int, rev: bool = False): return c.sortperm(rev, k)                        # Base.partialsortperm(col, 1:k; rev)
 
 
-def sort_view(v: Union[DFView, DFTable], by: str, rev: bool = False, limit: Optional[int] = None):
-    """sort!(materialize(v), by; rev) (first(.., limit) when given): the view's projection columns — fixed-width ones — in the order of its column `by`"""
+def _sort_keys(v: DFView, by, rev):
+    """(projection columns, one rev per column) of a list of column names and a bool or a list of bools"""
+    names = list(v.projection.keys())
+    revs = [bool(rev)] * len(by) if isinstance(rev, (bool, np.bool_)) else [bool(r) for r in rev]
+    if len(revs) != len(by):
+        raise ValueError(f"ArgumentError: rev has {len(revs)} entries for {len(by)} sort columns")
+    return [names.index(b) for b in by], revs
+
+
+def sortperm_by(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] = None) -> np.ndarray:
+    """sortperm by a tuple of columns: the 1-based TABLE rows of the selected rows of `v` in the lexicographic order of its columns `by` (a name or a list of
+    names, the first one major), `rev` a bool or one per column; rows equal in every key keep ascending row order"""
+    if isinstance(v, DFTable):
+        v = DFView(v)
+    if isinstance(by, str):
+        by = [by]
+    cols, revs = _sort_keys(v, by, rev)
+    return v._query().sort_indices_n(cols, revs, limit)[0]
+
+
+def sort_view(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] = None):
+    """sort!(materialize(v), by; rev) (first(.., limit) when given): the view's projection columns — fixed-width ones — in the order of its column `by`, or
+    of its columns `by` when that is a list of names (the first one major; `rev` a bool or one per column)"""
     if isinstance(v, DFTable):
         v = DFView(v)
     import pandas as pd
     q = v._query()
-    rows, _ = q.sort_indices(list(v.projection.keys()).index(by), rev, limit)
+    if isinstance(by, str):
+        rows, _ = q.sort_indices(list(v.projection.keys()).index(by), rev, limit)
+    else:
+        rows, _ = q.sort_indices_n(*_sort_keys(v, by, rev), limit)
     lg = _logicals(v)
     return pd.DataFrame({k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(v.projection.keys(), q.gather_rows(rows)))})
 

@@ -691,11 +691,16 @@ end
 
 const SORTABLE = Union{Int8,Int16,Int32,Int64,UInt8,UInt16,UInt32,UInt64,Bool,Float32,Float64}
 
-# the sorted table rows of query q's projection column 0 (dfdb_sort_indices): limit < 0 = all of them
-function sort_rows(q, rev::Bool, limit::Integer)
+# how many rows a sort of query q's selection cut to `limit` returns (limit < 0 = all of them)
+function sorted_length(q, limit::Integer)
     n = Ref{Int64}(0)
     check(ccall((:dfdb_count, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}), q, n))
-    m = limit < 0 ? n[] : min(limit, n[])
+    limit < 0 ? n[] : min(limit, n[])
+end
+
+# the sorted table rows of query q's projection column 0 (dfdb_sort_indices): limit < 0 = all of them
+function sort_rows(q, rev::Bool, limit::Integer)
+    m = sorted_length(q, limit)
     rows = Vector{Int64}(undef, m); got = Ref{Int64}(0)
     check(ccall((:dfdb_sort_indices, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}),
                 q, 0, rev ? 1 : 0, limit < 0 ? -1 : limit, rows, m, 0, got, C_NULL))
@@ -714,6 +719,30 @@ function gpu_sortperm(c::DFColumn{T}; rev::Bool = false, limit::Integer = -1) wh
     Base.nonmissingtype(T) <: SORTABLE || throw(Unsupported("sorting by a column of $(T)"))
     sharded() && throw(Unsupported("sorting over a sharded table"))
     with_query(q -> sort_rows(q, rev, limit), c.view)
+end
+
+"""
+    gpu_sortperm(v::DFView, cols::Vector{Symbol}; rev = false, limit = -1) -> Vector{Int64}
+
+The 1-based TABLE rows of the selected rows of `v` in the order `sort(df, cols; rev)` gives them: lexicographic by `cols[1]` (major) .. `cols[end]`, `rev` a
+Bool or one Bool per column, every key ordered as `gpu_sortperm(::DFColumn)` orders it, rows equal in every key in ascending row order
+(dfdb_sort_indices_n: the device sorts by the most minor key first and rekeys the order it has for every further key).  1 to 8 fixed-width columns.
+"""
+function gpu_sortperm(v::DFView, cols::Vector{Symbol}; rev::Union{Bool,AbstractVector{Bool}} = false, limit::Integer = -1)
+    sharded() && throw(Unsupported("sorting over a sharded table"))
+    nk = length(cols)
+    1 <= nk <= 8 || throw(ArgumentError("sorting takes 1 to 8 key columns, not $(nk)"))
+    revs = rev isa Bool ? fill(rev, nk) : collect(Bool, rev)
+    length(revs) == nk || throw(ArgumentError("rev has $(length(revs)) entries for $(nk) key columns"))
+    kidx = Int32.(0:nk-1)
+    flags = Int32[r ? 1 : 0 for r in revs]
+    with_query(v[:, cols]) do q
+        m = sorted_length(q, limit)
+        rows = Vector{Int64}(undef, m); got = Ref{Int64}(0)
+        check(ccall((:dfdb_sort_indices_n, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}),
+                    q, kidx, flags, nk, limit < 0 ? -1 : limit, rows, m, 0, got, C_NULL))
+        rows
+    end
 end
 
 "`sort(collect(c); rev)` (its first `limit` values when limit >= 0): the values gathered on the device in the order of gpu_sortperm (dfdb_gather_rows)"

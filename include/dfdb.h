@@ -426,10 +426,29 @@ int32_t dfdb_order_statistics(dfdb_query* q, int32_t proj_col, const int64_t* ra
  *            message that names the form for a String column, a computed column (materialise it as a column first: dfdb_table_add_from_query), a view
  *            that is out of core, a compressed-only column, and a table of 2^31 rows or more (rows travel in 32 bits); DFDB_ERR_BOUNDS for a proj_col
  *            the view does not have; DFDB_ERR_NOMEM when the pairs (2 x 12 bytes per sorted row) do not fit.
- * The query's selection is left as it was found.  Sorting by several keys composes — sort by the minor key first — but has no entry point yet, like the
- * sharded form. */
+ * The query's selection is left as it was found.  Sorting by several keys composes — sort by the minor key first —: dfdb_sort_indices_n below.  The
+ * sharded form has no entry point yet. */
 enum { DFDB_SORT_REV = 1 };
 int32_t dfdb_sort_indices(dfdb_query* q, int32_t proj_col, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info);
+/* sortperm by a tuple of columns (sort(df, [:a, :b]), sort!(materialize(v), [:a, :b]; rev = [false, true])): the 1-based table rows of the selected rows in
+ * the lexicographic order of projection columns proj_cols[0] (major) .. proj_cols[nkeys - 1] (most minor), 1 <= nkeys <= DFDB_SORT_MAX_KEYS.  The device
+ * sorts by the most minor key as dfdb_sort_indices does, then by every further key towards the major one with the same stable passes over pairs built from
+ * the ORDER the keys behind it left (k_sort_rekey, csrc/k_sort.hip); the answer is unique as dfdb_sort_indices' is.
+ *   order    each key j orders as dfdb_sort_indices orders that column: live values by isless, descending with flags[j] & DFDB_SORT_REV; the rows missing in
+ *            key j after all its live values, before them under that key's REV.  Rows equal in every key (or missing in the same keys) stay in ascending row
+ *            order whatever the flags.  The bytes under a missing bit are never read (quirk Q11).  The same column may appear more than once.
+ *   limit, out, cap, memkind, n   as dfdb_sort_indices takes them.  With nkeys > 1 `limit` only truncates what is written: every selected row is sorted (a
+ *            cut by the major key is a follow-up).
+ *   info     [4] (may be NULL): selected rows; pairs keyed, summed over the keys (each key's selected rows that are not missing in it); digit passes run,
+ *            summed over the keys; digit passes skipped, summed over the keys.
+ *   nkeys == 1 IS dfdb_sort_indices(q, proj_cols[0], flags[0], ..): the top-k cut and the same info.
+ * DFDB_ERR_ARGUMENT for nkeys outside 1 .. DFDB_SORT_MAX_KEYS, a null proj_cols or flags, a flag bit other than DFDB_SORT_REV; per key DFDB_ERR_BOUNDS and
+ * DFDB_ERR_UNSUPPORTED as dfdb_sort_indices raises them for that column (the same messages); DFDB_ERR_NOMEM when the buffers (2 x 8 bytes of keys, 2 x 4 of
+ * rows, 4 of order and 4 of missing list per selected row) do not fit.  Every argument is checked before the first launch; the query's selection is left as
+ * it was found. */
+enum { DFDB_SORT_MAX_KEYS = 8 };
+int32_t dfdb_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
+                            int64_t* n, int64_t* info);
 /* the projection at the 1-based table rows rows[0 .. n), in that order: any order, repeats allowed, independent of the query's selection (with
  * dfdb_sort_indices: sort(collect(col)), sort!(materialize(v), :col)).  `rows` lies in host or device memory (rows_memkind): the device output of
  * dfdb_sort_indices feeds it without leaving the device.  outs[i] (ncols = the view's columns) receives projection column i: data, missing bytes, count = n
