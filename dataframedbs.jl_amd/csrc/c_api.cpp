@@ -232,6 +232,11 @@ int32_t dfdb_ctx_profile_get(dfdb_ctx* ctx, const char* kernel, int64_t* launche
       if (total_ms) *total_ms = 0.0;
       return;
     }
+    if (!strcmp(kernel, "scan_image_bytes")) {       // a state, not a launch: HBM the scan images of this context's tables hold right now
+      if (launches) *launches = ctx->scan_image_bytes;
+      if (total_ms) *total_ms = 0.0;
+      return;
+    }
     profile_resolve(ctx);
     auto it = ctx->prof.find(kernel);
     if (launches) *launches = it == ctx->prof.end() ? 0 : it->second.launches;
@@ -254,6 +259,7 @@ int32_t dfdb_table_close(dfdb_table* t) {
     if (!t) return;
     (void)hipStreamSynchronize(t->ctx->stream);
     for (dfdb_query* q : t->queries) q->t = nullptr;   // orphan live queries: they may be freed later, never used
+    for (Column& c : t->cols) drop_scan_image(t->ctx, c);
     delete t;
   });
 }
@@ -546,6 +552,7 @@ int32_t dfdb_table_unload(dfdb_table* t, const int32_t* ordinals, int32_t ncols)
       if (o < 0 || (size_t)o >= t->cols.size()) fail(DFDB_ERR_KEY, "KeyError: column ordinal %d", o);
       Column& c = t->cols[(size_t)o];
       if (c.file.empty()) fail(DFDB_ERR_ARGUMENT, "ArgumentError: column %s has no backing file: unloading it would lose it", c.name.c_str());
+      drop_scan_image(t->ctx, c);
       c.data.release(); c.bytes.release(); c.tile_off.release(); c.missing.release(); c.comp.release(); c.comp_blocks.release(); c.comp_status.release(); c.comp_index.release();
       c.mask_pref.release(); c.mask_calibrated = false; c.mask_lent = false;
       c.dict_codes.release(); c.dict_len.release(); c.dict_off.release(); c.dict_bytes.release(); c.dict_host.clear(); c.dict_n = 0;

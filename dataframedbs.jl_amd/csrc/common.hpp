@@ -131,6 +131,8 @@ struct dfdb_ctx {
   dfdb::DevBuf radix_recs;                   // unique by radix partition (k_radix.hip): the 12-byte {key image, row} records' scratch, kept between calls
   dfdb::DevBuf hist;                         // K7 HIST forms: a ticket word + one 64-KB history ring per resident wave (k_decode.hip), made on first use
   int hist_waves = 0;
+  dfdb::DevBuf image_flag;                   // the misfit word of a scan-image build (k_image.hip), made on first use
+  int64_t scan_image_bytes = 0;              // HBM held by the scan images of this context's tables (dfdb_ctx_profile_get "scan_image_bytes")
   // two pinned bounce buffers for dfdb_table_load: the file is read piece by piece into one while the other is in flight to HBM
   uint8_t* pin_ring[2] = {nullptr, nullptr};
   size_t pin_ring_cap = 0;

@@ -54,6 +54,15 @@ struct Column {
   DevBuf mask_pref;
   bool mask_calibrated = false, mask_lent = false;
   float mask_ms_best = 0, mask_ms_worst = 0;   // per scanned sample, for dfdb_ctx_profile / the bench's JSON
+  // scan image (query.cpp: scan_image_for; scan_image.hpp; k_image.hip): an Int64 / UInt64 column whose values all fit 32 bits, truncated to 4 bytes per row in
+  // row order with the same 256-byte pad.  Made at the column's second single-term `col OP const` scan (ctx option "scan_image"), read by those scans instead of
+  // `data` from then on: half the bytes.  Holds exactly while `data` holds the contents it was made from — whoever releases, refills or re-decodes `data` calls
+  // drop_scan_image; a swap of `data` for another allocation with the same contents (placement calibration) keeps it.  Never made for a nullable column, one that
+  // keeps LZ4 blocks (comp / comp_only / transient), or a stream slot's chunk.
+  enum : int { kImageNone = 0, kImageBuilt = 1, kImageMisfit = 2 /* some value needs more than 32 bits: never tried again */, kImageNoRoom = 3 /* did not fit the budget */ };
+  DevBuf scan_image;
+  int scan_image_state = kImageNone;
+  int64_t scan_image_scans = 0;   // single-term scans of this column that could have read an image
   // dictionary form of a low-cardinality String column (dfdb_table_build_dictionary / ctx option "string_dictionary"; k_dict.hip): one 16-bit code per
   // row beside the flat form, the distinct strings once on the device and on the host (predicates are evaluated on the host copy)
   DevBuf dict_codes, dict_len, dict_off, dict_bytes;
@@ -276,6 +285,9 @@ void table_drop_transient(dfdb_table* t);
 struct TransientScope { dfdb_table* t; explicit TransientScope(dfdb_table* t_) : t(t_) {} ~TransientScope() { if (t) table_drop_transient(t); } };
 uint8_t* ctx_hist_scratch(dfdb_ctx* ctx, int* waves);       // the history rings of K7's HIST forms (one buffer per context, made on first use)
 void table_resident_bytes(dfdb_table* t, int32_t ordinal, int64_t* decoded, int64_t* compressed);
+// table.cpp: the column's scan image goes (and may be built again: state none, scans counted from 0).  Called wherever Column::data is released or gets new
+// contents; waits for the stream only when there is an image to free
+void drop_scan_image(dfdb_ctx* ctx, Column& c);
 int64_t table_decode_status(dfdb_table* t, int32_t ordinal);   // table.cpp: blocks of the last resident decode whose status is not 0 (synchronises)
 int column_lz4_index(dfdb_ctx* ctx, Column& c, bool form_takes_index);   // table.cpp: 0 / 1 (record) / 2 (use) for launch_lz4_decode*
 int32_t ctx_create_like(const dfdb_ctx* like, dfdb_ctx** out);   // c_api.cpp

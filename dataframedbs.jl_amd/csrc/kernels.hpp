@@ -56,6 +56,9 @@ void launch_scan_cmp(hipStream_t s, const ScanTerm& term, uint64_t* bitmap, uint
                                          narrow columns take k_scan_cmp_narrow (16 bytes per lane): 1 = 1-byte (default), 2 = 1-, 2- and 4-byte, 0 = none */);
 // K1's read stream alone (k_read_probe): an 8-byte column of nrows rows, nothing written (sink: one device word that is never stored to)
 void launch_read_probe(hipStream_t s, const void* col, int64_t nrows, uint64_t* sink);
+// the 4-byte scan image of an Int64 (is_signed) / UInt64 column (k_image.hip; scan_image.hpp): image[i] = the low half of col[i]; *misfit (a device word the caller
+// zeroed) is raised when some value is not its truncation extended back.  col and image are 16-byte aligned and carry the columns' 256-byte pad
+void launch_scan_image_build(hipStream_t s, const void* col, bool is_signed, void* image, int64_t nrows, uint32_t* misfit);
 // extra = 1 (capture): the LAST term's 8-byte column at the finally selected rows, compacted per tile at extra_out[tile*1024 + rank];
 // extra = 2 (sum): one partial sum of that column per 1024-row tile in extra_out[tile] (double, or wrapping 64-bit integer).  AND only.
 // extra = 5 (capture two): the last term's column like extra = 1, and the 8-byte column of the term before it into extra_out2, same layout.

@@ -563,7 +563,7 @@ int32_t query_prepare(dfdb_query* q) {
     const Column& c = t->cols[(size_t)o];
     plain = plain && dt_base(c.dtype) != DFDB_STRING && !dt_nullable(c.dtype);
   }
-  auto unload = [&] { for (int32_t o : need) { Column& c = t->cols[(size_t)o]; if (!c.resident) { c.data.release(); c.bytes.release(); c.missing.release(); c.tile_off.release(); c.comp.release(); c.comp_blocks.release(); c.comp_status.release(); c.comp_index.release(); c.comp_nblocks = 0; c.comp_only = false; } } };
+  auto unload = [&] { for (int32_t o : need) { Column& c = t->cols[(size_t)o]; if (!c.resident) { drop_scan_image(ctx, c); c.data.release(); c.bytes.release(); c.missing.release(); c.tile_off.release(); c.comp.release(); c.comp_blocks.release(); c.comp_status.release(); c.comp_index.release(); c.comp_nblocks = 0; c.comp_only = false; } } };
   const int64_t kc_old = ctx_option(ctx, "keep_compressed", 0);
   struct Restore { dfdb_ctx* c; int64_t v; ~Restore() { c->options["keep_compressed"] = v; } } restore{ctx, kc_old};
   if (dec <= budget && dec + comp_max + (64 << 20) <= free_now) {           // decoded arrays (+ the staging of one column file at a time)

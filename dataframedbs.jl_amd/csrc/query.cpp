@@ -11,6 +11,7 @@
 // dfdb_count reads the scan total, dfdb_materialize reuses the same bitmap.
 #include "engine.hpp"
 #include "ooc.hpp"
+#include "scan_image.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -613,12 +614,68 @@ static bool run_decode_on_scan(dfdb_query* q, const ScanTerm& tm, int ord) {
                          LzScan{q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), tm.cbits, fdt, tm.op}, fc.comp_index.as<uint32_t>(), imode);
   return true;
 }
+// ---- the 4-byte scan image (engine.hpp Column::scan_image, scan_image.hpp, k_image.hip)
+// A lone `col OP const` scan is bound by the column's bytes, and an Int64 / UInt64 column whose values all fit 32 bits carries four bytes per row the
+// comparison does not need.  The column does not change between queries — only the constant does — so its truncated copy is made once and every later such scan reads
+// 4 bytes per row through the shipped k_scan_cmp<int32 / uint32>.  ctx option "scan_image": 1 (default) = the column's SECOND such scan builds it (a one-off query never
+// pays: the build moves 12 bytes per row, a scan saves 4), 2 = the first does (tests), 0 = never built, never read; "scan_image_min_rows" (default 2^24): below it a
+// scan is launch-bound and there is nothing to win.  The image is counted like the decoded form against "hbm_budget_mb" and 80 % of the free HBM; a column that does
+// not fit 32 bits, or the budget, is not tried again until it is reloaded.
+static void build_scan_image(dfdb_table* t, Column& c) {
+  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const size_t bytes = (size_t)t->nrows * 4 + 256;
+  c.scan_image_state = Column::kImageNoRoom;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return; }
+  int64_t budget = ctx_option(ctx, "hbm_budget_mb", 0) << 20;
+  if (budget > 0) { int64_t d = 0, k = 0; table_resident_bytes(t, -1, &d, &k); budget -= d + k; }
+  else budget = INT64_MAX;
+  if ((int64_t)bytes > budget || (int64_t)bytes + (64 << 20) > (int64_t)((double)free_b * 0.8)) { prof_note(ctx, "scan_image.no_room"); return; }
+  try { c.scan_image.ensure(bytes); ctx->image_flag.ensure(256); }
+  catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); c.scan_image.release(); prof_note(ctx, "scan_image.no_room"); return; }
+  HIP_CHECK(hipMemsetAsync(ctx->image_flag.p, 0, 4, s));
+  { LaunchTimer lt(ctx, "scan_image.build");
+    launch_scan_image_build(s, c.data.p, dt_issigned(c.dtype), c.scan_image.p, t->nrows, ctx->image_flag.as<uint32_t>()); }
+  // the image is read only after the flag has been: one small copy and one wait, once per column
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, ctx->image_flag.p, 4, hipMemcpyDeviceToHost, s));
+  stream_wait(ctx);
+  if ((uint32_t)ctx->pinned_scalar[0] != 0) { c.scan_image.release(); c.scan_image_state = Column::kImageMisfit; prof_note(ctx, "scan_image.misfit"); return; }
+  c.scan_image_state = Column::kImageBuilt;
+  ctx->scan_image_bytes += (int64_t)c.scan_image.bytes;
+}
+// May this lone plain term (no transform, no second comparison, nothing captured) over table column `ord` read the column's image?  Then *out is the term as
+// launch_scan_cmp takes it: the image, its 4-byte dtype, the truncated constant.  Counts the scan and builds the image when this scan is the one that does.  A
+// constant outside the image type's range takes the flat column like everything else — nothing is folded.
+static bool scan_image_term(dfdb_query* q, int ord, const ScanTerm& tm, ScanTerm* out) {
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
+  const int64_t opt = ctx_option(ctx, "scan_image", 1);
+  if (opt == 0) return false;
+  Column& c = t->cols[(size_t)ord];
+  const int32_t idt = scan_image_dtype(tm.dtype);
+  if (!idt || dt_nullable(c.dtype) || dt_base(c.dtype) != tm.dtype || tm.col != c.data.p || c.comp.p || c.comp_only || c.transient || t->keep_load_scratch) return false;
+  if (c.scan_image_scans < INT64_MAX) c.scan_image_scans++;
+  if (c.scan_image_state == Column::kImageNone && (opt == 2 || c.scan_image_scans >= 2) && t->nrows >= ctx_option(ctx, "scan_image_min_rows", (int64_t)1 << 24))
+    build_scan_image(t, c);
+  uint64_t cb = 0;
+  if (c.scan_image_state != Column::kImageBuilt || !scan_image_const(tm.dtype, tm.cbits, &cb)) return false;
+  *out = tm; out->col = c.scan_image.p; out->dtype = idt; out->cbits = cb;
+  return true;
+}
+
 // one batch of AND-ed simple terms; ex: the rider (the plan's, on its last batch).  fresh_first: this launch writes the first mask of the query's first stage
 static void run_term_batch(dfdb_query* q, const TermBatch& b, int ex, bool have, bool fresh_first) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const ScanTerms& tb = b.terms;
   const bool one_plain = tb.n == 1 && tb.t[0].op2 < 0 && tb.t[0].pre == 0;
   if (one_plain && ex == EX_NONE && fresh_first && ctx_option(ctx, "decode_on_scan", 0) != 0 && run_decode_on_scan(q, tb.t[0], b.ords[0])) return;
+  ScanTerm img;
+  if (one_plain && ex == EX_NONE && scan_image_term(q, b.ords[0], tb.t[0], &img)) {      // the same launch over the column's 4-byte image, under its own profile key
+    LaunchTimer lt(ctx, "scan_image");
+    prof_note(ctx, img.dtype == DFDB_I32 ? "scan_image.int32" : "scan_image.uint32");
+    launch_scan_cmp(s, img, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have, true, nullptr,
+                    (ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0) | (int)((ctx_option(ctx, "scan_narrow", 1) & 3) << 1));
+    return;
+  }
   if (one_plain && (ex == EX_NONE || (ex == EX_CAPTURE && !have))) {      // (k_scan_cmp captures over a fresh mask only)
     LaunchTimer lt(ctx, "scan_cmp");
     prof_note(ctx, ctx_option(ctx, "scan_wt_store", 1) ? "scan_cmp.wt_store" : "scan_cmp.plain_store");

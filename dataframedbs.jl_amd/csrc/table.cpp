@@ -255,6 +255,7 @@ void launch_unpack_strings(hipStream_t s, const uint8_t* bodies, const int64_t* 
 static void decode_staged(dfdb_table* t, Column& c, const BlockHdr* hs, int64_t nb, int64_t block_first, int64_t comp_lo, dfdb_sizestats* stats,
                           const int64_t* row_pos = nullptr, int64_t total_rows = -1, int64_t predecoded = 0) {
   dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  drop_scan_image(ctx, c);                                // the column gets new contents
   int64_t nrows = 0;
   for (int64_t i = 0; i < nb; i++) nrows += hs[i].rows;
   if (row_pos) nrows = total_rows;
@@ -400,6 +401,7 @@ static void load_from_image(dfdb_table* t, Column& c, const uint8_t* img, size_t
 // blocks are decoded by ONE K7 launch once the last piece has been queued.
 static void load_from_file(dfdb_table* t, Column& c, int64_t block_first, int64_t block_last, dfdb_sizestats* stats) {
   dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  drop_scan_image(ctx, c);                                                     // (the progressive decode below writes c.data ahead of decode_staged)
   NodeBind bind(ctx);                                                          // the preads and the bounce buffers on the GPU's NUMA node
   set_io_threads(ctx_option(ctx, "io_threads", 8));                            // (process-wide: the last table loaded / stream opened decides)
   const int fd = open(c.file.c_str(), O_RDONLY);
@@ -562,6 +564,7 @@ void table_decode_resident(dfdb_table* t, int32_t ordinal) {
   if (!c.comp_nblocks) fail(DFDB_ERR_ARGUMENT, "column %s holds no compressed blocks (load it with option keep_compressed = 1)", c.name.c_str());
   if (c.comp_only) fail(DFDB_ERR_ARGUMENT, "column %s is compressed-only (keep_compressed = 2): it has no decoded array to decode into", c.name.c_str());
   dfdb_ctx* ctx = t->ctx;
+  drop_scan_image(ctx, c);
   for (dfdb_query* q : t->queries) { q->executed_stages = -1; q->count = -1; q->prefix_valid = false; }
   const int pipe = (int)ctx_option(ctx, "lz4_pipeline", -1);
   const int mode = column_lz4_index(ctx, c, lz4_decode_takes_index((int32_t)c.comp_nblocks, pipe));
@@ -604,6 +607,7 @@ static void transient_decode_checked(dfdb_table* t, Column& c);
 // read right behind the launch: transient_decode_checked)
 const void* column_data(dfdb_table* t, Column& c) {
   if (!c.comp_only || c.data.p) return c.data.p;
+  drop_scan_image(t->ctx, c);
   c.data.ensure((size_t)c.nrows * (size_t)dt_width(c.dtype) + 256);
   c.transient = true;
   transient_decode_checked(t, c);
@@ -638,10 +642,19 @@ static void transient_decode_checked(dfdb_table* t, Column& c) {
     fail(DFDB_ERR_FORMAT, "column %s: %lld of its resident LZ4 blocks do not decode", c.name.c_str(), (long long)bad);
   }
 }
+void drop_scan_image(dfdb_ctx* ctx, Column& c) {
+  if (c.scan_image.p) {
+    (void)hipStreamSynchronize(ctx->stream);                  // a scan that reads it may still be in flight
+    ctx->scan_image_bytes -= (int64_t)c.scan_image.bytes;
+    c.scan_image.release();
+  }
+  c.scan_image_state = Column::kImageNone; c.scan_image_scans = 0;
+}
 void table_resident_bytes(dfdb_table* t, int32_t ordinal, int64_t* decoded, int64_t* compressed) {
   int64_t d = 0, k = 0;
   auto one = [&](const Column& c) {
     if (!c.transient) d += (int64_t)c.data.bytes;
+    d += (int64_t)c.scan_image.bytes;
     d += (int64_t)c.bytes.bytes + (int64_t)c.tile_off.bytes + (int64_t)c.missing.bytes + (int64_t)c.dict_codes.bytes + (int64_t)c.dict_bytes.bytes;
     k += (int64_t)c.comp.bytes + (int64_t)c.comp_blocks.bytes + (int64_t)c.comp_status.bytes + (int64_t)c.comp_index.bytes;
   };

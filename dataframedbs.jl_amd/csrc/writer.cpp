@@ -226,6 +226,7 @@ void table_compress_column(dfdb_table* t, int32_t ordinal, int32_t mode, dfdb_si
   const int w = dt_width(c.dtype);
   if (nb == 0) fail(DFDB_ERR_ARGUMENT, "column %s has no rows", c.name.c_str());
   HIP_CHECK(hipStreamSynchronize(s));
+  drop_scan_image(ctx, c);                             // (a column that keeps LZ4 blocks has no scan image, and mode 2 releases the array it was made from)
   c.comp.release(); c.comp_blocks.release(); c.comp_status.release(); c.comp_index.release();
   c.comp_nblocks = 0; c.comp_index_state = 0; c.comp_blocks_host.clear();
   DevBuf scratch, dblocks, dlens, dpos, image;

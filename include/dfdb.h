@@ -182,7 +182,13 @@ int32_t dfdb_ctx_device_info(dfdb_ctx* ctx, dfdb_device_info* out);
  *   "jit"              1 (default) = an expression the device INTERPRETER evaluates (outside `col OP const` terms, pairs and string matches: configs 2-5 never get here)
  *                      over at least 4 M rows is also compiled by hipRTC in the background — the interpreter's own source specialised for the program's shape — and later
  *                      executions run the compiled kernel; until it is ready, or when libhiprtc is absent, the interpreter answers.  0 = interpret always; 2 = wait for
- *                      the compiler (tests, benchmarks).  Results are identical by construction.  dfdb_shutdown stops the compiler; dfdb_jit_cache_dir is its disk cache */
+ *                      the compiler (tests, benchmarks).  Results are identical by construction.  dfdb_shutdown stops the compiler; dfdb_jit_cache_dir is its disk cache
+ * One default that costs HBM is switched by a key of KNOBS.md, not by one of the twenty: the scan image.  A resident, non-nullable Int64 / UInt64 column of at least
+ * 2^24 rows ("scan_image_min_rows") that is the target of a SECOND lone `col OP const` scan gets a truncated 4-byte copy (Int32 / UInt32, 4 bytes per row more HBM,
+ * counted under `decoded` by dfdb_table_resident_bytes and against "hbm_budget_mb") if every value fits; such scans read the copy from then on whenever their constant
+ * fits too: half the bytes, the same answers.  Option scan_image = 0 turns it off (1 = default, 2 = build at the first scan).  The copy goes wherever the column's
+ * contents go (unload, reload, compress).  dfdb_ctx_profile_get: launches under "scan_image" (not "scan_cmp"), the one-time build under "scan_image.build", and
+ * "scan_image_bytes" reads the HBM the context's images hold right now. */
 int32_t dfdb_ctx_set_option(dfdb_ctx* ctx, const char* key, int64_t value);
 /* HIP-event timing on the engine's own stream (bench.py's roofline leg) */
 int32_t dfdb_ctx_timer_start(dfdb_ctx* ctx);
