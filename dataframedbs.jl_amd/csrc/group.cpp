@@ -1305,6 +1305,12 @@ int32_t dfdb_selftest(const char* name, int64_t arg, int64_t* out, int32_t nout)
       sort_geometry(out);
       return;
     }
+    if (!strcmp(name, "str_gather_form")) {
+      // the rule between the two forms of the String gather at given rows (kernels.hpp): out = [n, nrows, ctx option "str_gather_form"] -> out[0] = the form
+      if (nout < 3) fail(DFDB_ERR_ARGUMENT, "ArgumentError: str_gather_form reads 3 values");
+      out[0] = str_gather_form(out[0], out[1], out[2]);
+      return;
+    }
     fail(DFDB_ERR_ARGUMENT, "ArgumentError: no self-test named %s", name);
   });
 }

@@ -152,6 +152,30 @@ void launch_str_gather_sizes(hipStream_t s, const uint64_t* bitmap, const uint64
 void launch_str_gather_bytes(hipStream_t s, const uint64_t* bitmap, const StrSide& a, const StrFill& fill, const uint64_t* out_tile_off, uint8_t* out_bytes,
                              int64_t nrows, int64_t out_bytes_cap);
 
+// K13 (k_str_rows.hip): String column `col` at the 1-based table rows rows[0 .. n), in that order (any order, repeats allowed): sizes pass, scan, bytes pass.
+// A row's bytes start at tile_off[its tile] + the bytes of the tile's rows before it, and that in-tile prefix comes in two forms:
+//   offsets  launch_str_row_offsets first leaves row_off[nrows] (u32), the sizes pass gathers row_off[r]:  8 B per COLUMN row + 4 B per output
+//   direct   one wave per output sums the sizes of the tile's rows before r:                                at most 4 KB per OUTPUT
+// str_gather_form is the rule: direct when n * 512 <= nrows, which is where the direct form's worst-case bytes (4 KB * n) equal the build's (8 B * nrows).  The
+// constant is derived from those bytes, not from a measurement.  Measured (profiles/str_gather_rows.txt, 5e8 rows of short strings): the forms cross at
+// n = rows / 281, 1.82 x away — within the factor of 2 inside which the derived constant stays.  forced: ctx option "str_gather_form"
+// (1 = offsets, 2 = direct, anything else = the rule).  STR_GATHER_LAYOUT is the sizes pass that writes neither sizes nor offsets: the byte totals alone.
+enum StrGatherForm : int { STR_GATHER_LAYOUT = 0, STR_GATHER_OFFSETS = 1, STR_GATHER_DIRECT = 2 };
+constexpr int64_t kStrGatherDirectRatio = 512;
+inline StrGatherForm str_gather_form(int64_t n, int64_t nrows, int64_t forced = 0) {
+  if (forced == STR_GATHER_OFFSETS || forced == STR_GATHER_DIRECT) return (StrGatherForm)forced;
+  return n <= nrows / kStrGatherDirectRatio ? STR_GATHER_DIRECT : STR_GATHER_OFFSETS;      // (n * 512 <= nrows, without the product)
+}
+// the per-1024-output byte totals are 32-bit and the outputs of a group may all name the longest row: a column whose largest TILE holds this much or more is refused
+constexpr uint32_t kStrGatherMaxTileBytes = 1u << 22;
+struct StrRows { const int64_t* rows; int64_t n; StrSide col; int64_t row_base, nrows; uint32_t* flag; };   // flag: raised (vector atomic OR) by a row outside [0, nrows), which writes nothing
+void launch_str_row_offsets(hipStream_t s, const int32_t* sizes, uint32_t* row_off, int64_t nrows);
+// out_sizes[i] = sizes[r_i], src_off[i] = the arena offset of row r_i (both not in the LAYOUT form), grp_bytes[g] = the bytes of outputs [1024 g, 1024 (g + 1))
+void launch_str_rows_sizes(hipStream_t s, const StrRows& R, StrGatherForm form, const uint32_t* row_off, int32_t* out_sizes, int64_t* src_off, uint32_t* grp_bytes);
+// out_off: launch_scan_counts of grp_bytes; nothing is stored at or beyond out_bytes + out_cap
+void launch_str_rows_bytes(hipStream_t s, const int32_t* out_sizes, const int64_t* src_off, int64_t n, const uint8_t* arena, const uint64_t* out_off, uint8_t* out_bytes,
+                           int64_t out_cap);
+
 // n rows that all hold the same string: sizes[i] = plen, bytes = the pattern (device memory) n times
 void launch_fill_const_strings(hipStream_t s, int32_t* out_sizes, uint8_t* out_bytes, int64_t n, const uint8_t* pat_dev, int32_t plen);
 

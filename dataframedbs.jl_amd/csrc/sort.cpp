@@ -1,5 +1,6 @@
 // sort.cpp — ordering on the device: dfdb_sort_indices (the stable sortperm of the selected rows by one projection column, with a limit), dfdb_sort_indices_n
-// (the same by several columns, the most minor key first) and dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip.
+// (the same by several columns, the most minor key first) and dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip;
+// dfdb_gather_rows_any and dfdb_gather_rows_string_bytes (the same gather with String columns admitted), over those of k_str_rows.hip.
 //
 // Replaces sortperm(collect(col)), partialsortperm and sort over Base.iterate(::DFColumn) (src/tables/column.jl:102-126), which pull every selected value to
 // the host.  The host side here plans: which rows are kept (the top-k cut, found with the radix select of k_select.hip), which key bytes order anything (the
@@ -11,13 +12,15 @@
 
 namespace dfdb {
 
-// the plain fixed-width projection column p of q, resident and decoded — or the refusal that names the form (`what`: "sorting by" / "gathering rows of")
-static const Column& ordered_column(dfdb_query* q, int32_t p, const char* what) {
+// the plain fixed-width projection column p of q, resident and decoded — or the refusal that names the form (`what`: "sorting by" / "gathering rows of").
+// strings: a plain String column is admitted too (its flat form: sizes, arena, tile offsets — a column with a dictionary keeps it)
+static const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool strings = false) {
   if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
   const Node& e = *q->proj[(size_t)p].expr;
-  if (dt_base(e.dtype) == DFDB_STRING) fail(DFDB_ERR_UNSUPPORTED, "%s a String column is not supported", what);
+  const bool str = dt_base(e.dtype) == DFDB_STRING;
+  if (str && !strings) fail(DFDB_ERR_UNSUPPORTED, "%s a String column is not supported", what);
   if (e.op != DFIR_COL) fail(DFDB_ERR_UNSUPPORTED, "%s a computed column is not supported: materialise it as a column first (dfdb_table_add_from_query)", what);
-  if (!dt_isnum(e.dtype)) fail(DFDB_ERR_UNSUPPORTED, "%s a column of %s is not supported", what, dt_name(e.dtype).c_str());
+  if (!str && !dt_isnum(e.dtype)) fail(DFDB_ERR_UNSUPPORTED, "%s a column of %s is not supported", what, dt_name(e.dtype).c_str());
   dfdb_table* t = q->t;
   if (query_out_of_core(q)) fail(DFDB_ERR_UNSUPPORTED, "%s a column of a view that is out of core (its columns are not resident) is not supported: dfdb_table_load the columns first", what);
   if (t->cols[(size_t)e.col].comp_only)
@@ -257,6 +260,35 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
   if (info) memcpy(info, inf, sizeof inf);
 }
 
+// ---- the projection at given rows --------------------------------------------------------------------------------------------------------------------------
+// rows[0 .. n) in device memory: the caller's own, or a copy of a host list in `hold`
+static const int64_t* rows_on_device(hipStream_t s, const int64_t* rows, int64_t n, int32_t rows_memkind, DevBuf& hold) {
+  if (rows_memkind == DFDB_MEM_DEVICE) return rows;
+  hold.ensure((size_t)n * 8);
+  HIP_CHECK(hipMemcpyAsync(hold.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  return hold.as<int64_t>();
+}
+[[noreturn]] static void fail_row_outside(const dfdb_table* t) { fail(DFDB_ERR_BOUNDS, "BoundsError: a row outside 1..%lld", (long long)(t->row_base + t->nrows)); }
+
+// fixed-width column `col` at drows[0 .. n) into o (device output: in place; host output: through stage / mstage, queued, not waited for)
+static void gather_fixed_column(dfdb_table* t, const Column& col, dfdb_outcol& o, const int64_t* drows, int64_t n, uint32_t* flag, DevBuf& stage, DevBuf& mstage) {
+  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const bool dev = o.memkind == DFDB_MEM_DEVICE, want_missing = dt_nullable(col.dtype) && o.missing;
+  const int w = dt_width(col.dtype);
+  void* dst = o.data; uint8_t* md = want_missing ? o.missing : nullptr;
+  if (!dev) {
+    stage.ensure((size_t)n * w); dst = stage.p;
+    HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)n * w, s));           // (a refused row writes nothing: the host copy must not carry pool bytes)
+    if (want_missing) { mstage.ensure((size_t)n); md = mstage.as<uint8_t>(); HIP_CHECK(hipMemsetAsync(md, 0, (size_t)n, s)); }
+  }
+  { LaunchTimer lt(ctx, "gather_rows");
+    launch_gather_rows(s, drows, n, col.data.p, w, dst, dt_nullable(col.dtype) ? col.missing.as<uint64_t>() : nullptr, md, t->row_base, t->nrows, flag); }
+  if (!dev) {
+    HIP_CHECK(hipMemcpyAsync(o.data, dst, (size_t)n * w, hipMemcpyDeviceToHost, s));
+    if (want_missing) HIP_CHECK(hipMemcpyAsync(o.missing, md, (size_t)n, hipMemcpyDeviceToHost, s));
+  }
+}
+
 void query_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
   if (ncols != (int32_t)q->proj.size()) fail(DFDB_ERR_ARGUMENT, "ArgumentError: view has %zu columns, %d outputs given", q->proj.size(), ncols);
   if (n < 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %lld rows", (long long)n);
@@ -269,35 +301,123 @@ void query_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t ro
   }
   if (n == 0) return;
   DevBuf rows_dev, flag;
-  const int64_t* drows = rows;
-  if (rows_memkind != DFDB_MEM_DEVICE) {
-    rows_dev.ensure((size_t)n * 8);
-    HIP_CHECK(hipMemcpyAsync(rows_dev.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    drows = rows_dev.as<int64_t>();
-  }
+  const int64_t* drows = rows_on_device(s, rows, n, rows_memkind, rows_dev);
   flag.ensure(64);
   HIP_CHECK(hipMemsetAsync(flag.p, 0, 8, s));
   std::vector<DevBuf> stages((size_t)ncols * 2);
-  for (int32_t p = 0; p < ncols; p++) {
-    const Column& col = *cols[(size_t)p]; dfdb_outcol& o = outs[p];
-    const bool dev = o.memkind == DFDB_MEM_DEVICE, want_missing = dt_nullable(col.dtype) && o.missing;
-    const int w = dt_width(col.dtype);
-    void* dst = o.data; uint8_t* md = want_missing ? o.missing : nullptr;
-    if (!dev) {
-      stages[(size_t)p * 2].ensure((size_t)n * w); dst = stages[(size_t)p * 2].p;
-      HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)n * w, s));           // (a refused row writes nothing: the host copy must not carry pool bytes)
-      if (want_missing) { stages[(size_t)p * 2 + 1].ensure((size_t)n); md = stages[(size_t)p * 2 + 1].as<uint8_t>(); HIP_CHECK(hipMemsetAsync(md, 0, (size_t)n, s)); }
-    }
-    { LaunchTimer lt(ctx, "gather_rows");
-      launch_gather_rows(s, drows, n, col.data.p, w, dst, dt_nullable(col.dtype) ? col.missing.as<uint64_t>() : nullptr, md, t->row_base, t->nrows, flag.as<uint32_t>()); }
-    if (!dev) {
-      HIP_CHECK(hipMemcpyAsync(o.data, dst, (size_t)n * w, hipMemcpyDeviceToHost, s));
-      if (want_missing) HIP_CHECK(hipMemcpyAsync(o.missing, md, (size_t)n, hipMemcpyDeviceToHost, s));
-    }
-  }
+  for (int32_t p = 0; p < ncols; p++) gather_fixed_column(t, *cols[(size_t)p], outs[p], drows, n, flag.as<uint32_t>(), stages[(size_t)p * 2], stages[(size_t)p * 2 + 1]);
   HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, flag.p, 8, hipMemcpyDeviceToHost, s));
   stream_wait(ctx);                                  // (also: the staging buffers and a pageable `rows` die with this call)
-  if (ctx->pinned_scalar[0] != 0) fail(DFDB_ERR_BOUNDS, "BoundsError: a row outside 1..%lld", (long long)(t->row_base + t->nrows));
+  if (ctx->pinned_scalar[0] != 0) fail_row_outside(t);
+}
+
+// ---- the same with String columns (k_str_rows.hip): offsets of the gathered sizes, then the bytes -------------------------------------------------------------
+namespace {
+// the String gather's device memory, and the staging of host outputs: from the pool, back to it when the call ends (the stream drained first)
+struct RowsScratch {
+  dfdb_ctx* ctx;
+  DevBuf rows, flag, row_off, src_off, grp_bytes, out_off, scan_scratch;
+  std::vector<DevBuf> stages;                       // per column: data (a String column: sizes), missing bytes (a String column: bytes)
+  RowsScratch(dfdb_ctx* c, int32_t ncols) : ctx(c), stages((size_t)ncols * 2) {}
+  ~RowsScratch() {
+    (void)hipStreamSynchronize(ctx->stream);
+    RecycleScope rs;
+    for (DevBuf* b : {&rows, &flag, &row_off, &src_off, &grp_bytes, &out_off, &scan_scratch}) b->release();
+    for (DevBuf& b : stages) b.release();
+  }
+};
+}  // namespace
+
+// a plain column of the view for a gather at given rows, String admitted — or the refusal that names the form, or the column
+static const Column& rows_column(dfdb_query* q, int32_t p) {
+  const Column& col = ordered_column(q, p, "gathering rows of", true);
+  if (dt_base(col.dtype) == DFDB_STRING && col.max_tile_bytes >= kStrGatherMaxTileBytes)
+    fail(DFDB_ERR_UNSUPPORTED, "gathering rows of the String column %s is not supported: a 1024-row tile of it holds %u bytes, the limit is below %u (1024 outputs may repeat its longest row, and "
+         "their byte total is kept in 32 bits)", col.name.c_str(), col.max_tile_bytes, kStrGatherMaxTileBytes);
+  return col;
+}
+
+// The sizes pass and the scan of String column `col` at drows[0 .. n): S.out_off[groups + 1], and the bytes the rows need (the scan's last entry) — read back
+// together with the flag word, whose refusal comes first.  form LAYOUT: totals only; else out_sizes (device memory, n entries) and S.src_off are written too
+static int64_t rows_string_layout(dfdb_table* t, const Column& col, RowsScratch& S, const int64_t* drows, int64_t n, StrGatherForm form, int32_t* out_sizes) {
+  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  const int64_t ngroups = ceil_div(n, kTileRows);
+  S.grp_bytes.ensure((size_t)(ngroups + 8) * 4); S.out_off.ensure((size_t)(ngroups + 8) * 8); S.scan_scratch.ensure(scan_counts_scratch_bytes(ngroups));
+  if (form != STR_GATHER_LAYOUT) S.src_off.ensure((size_t)n * 8);
+  if (form == STR_GATHER_OFFSETS) {
+    S.row_off.ensure((size_t)std::max<int64_t>(t->nrows, 1) * 4);
+    LaunchTimer lt(ctx, "str_row_offsets"); launch_str_row_offsets(s, col.data.as<int32_t>(), S.row_off.as<uint32_t>(), t->nrows);
+  }
+  const StrRows R{drows, n, str_side(col), t->row_base, t->nrows, S.flag.as<uint32_t>()};
+  { LaunchTimer lt(ctx, "str_rows_sizes"); launch_str_rows_sizes(s, R, form, S.row_off.as<uint32_t>(), out_sizes, S.src_off.as<int64_t>(), S.grp_bytes.as<uint32_t>()); }
+  { LaunchTimer lt(ctx, "scan_counts"); launch_scan_counts(s, S.grp_bytes.as<uint32_t>(), S.out_off.as<uint64_t>(), ngroups, S.scan_scratch.as<uint64_t>()); }
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, S.flag.p, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar + 1, S.out_off.as<uint64_t>() + ngroups, 8, hipMemcpyDeviceToHost, s));
+  stream_wait(ctx);
+  if (ctx->pinned_scalar[0] != 0) fail_row_outside(t);
+  return ctx->pinned_scalar[1];
+}
+
+static void rows_scratch_begin(dfdb_table* t, RowsScratch& S, const int64_t* rows, int64_t n, int32_t rows_memkind, const int64_t** drows) {
+  hipStream_t s = t->ctx->stream;
+  *drows = rows_on_device(s, rows, n, rows_memkind, S.rows);
+  S.flag.ensure(64);
+  HIP_CHECK(hipMemsetAsync(S.flag.p, 0, 8, s));
+}
+
+int64_t query_gather_rows_string_bytes(dfdb_query* q, int32_t i, const int64_t* rows, int64_t n, int32_t rows_memkind) {
+  if (n < 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %lld rows", (long long)n);
+  const Column& col = rows_column(q, i);
+  if (dt_base(col.dtype) != DFDB_STRING || n == 0) return 0;
+  dfdb_table* t = q->t;
+  RowsScratch S(t->ctx, 0);
+  const int64_t* drows;
+  rows_scratch_begin(t, S, rows, n, rows_memkind, &drows);
+  return rows_string_layout(t, col, S, drows, n, STR_GATHER_LAYOUT, nullptr);
+}
+
+void query_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
+  if (ncols != (int32_t)q->proj.size()) fail(DFDB_ERR_ARGUMENT, "ArgumentError: view has %zu columns, %d outputs given", q->proj.size(), ncols);
+  if (n < 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %lld rows", (long long)n);
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  std::vector<const Column*> cols;
+  for (int32_t p = 0; p < ncols; p++) cols.push_back(&rows_column(q, p));
+  for (int32_t p = 0; p < ncols; p++) {
+    outs[p].dtype = q->proj[(size_t)p].expr->dtype; outs[p].count = n; outs[p].nbytes = 0;
+    if (n > 0 && !outs[p].data) fail(DFDB_ERR_ARGUMENT, "output column %d has no data buffer", p);
+  }
+  if (n == 0) return;
+  RowsScratch S(ctx, ncols);
+  const int64_t* drows;
+  rows_scratch_begin(t, S, rows, n, rows_memkind, &drows);
+  const StrGatherForm form = str_gather_form(n, t->nrows, ctx_option(ctx, "str_gather_form", 0));
+  for (int32_t p = 0; p < ncols; p++) {
+    const Column& col = *cols[(size_t)p]; dfdb_outcol& o = outs[p];
+    DevBuf& stage0 = S.stages[(size_t)p * 2]; DevBuf& stage1 = S.stages[(size_t)p * 2 + 1];
+    if (dt_base(col.dtype) != DFDB_STRING) { gather_fixed_column(t, col, o, drows, n, S.flag.as<uint32_t>(), stage0, stage1); continue; }
+    const bool dev = o.memkind == DFDB_MEM_DEVICE;
+    int32_t* sizes = (int32_t*)o.data;
+    if (!dev) {
+      stage0.ensure((size_t)n * 4); sizes = stage0.as<int32_t>();
+      HIP_CHECK(hipMemsetAsync(sizes, 0, (size_t)n * 4, s));           // (a refused row writes nothing: the host copy must not carry pool bytes)
+    }
+    // the rows' sizes and where their bytes start, then — on the host, before a byte moves — whether the bytes fit
+    const int64_t total = rows_string_layout(t, col, S, drows, n, form, sizes);
+    const int64_t cap = o.bytes ? o.bytes_cap : 0;
+    if (total > cap) fail(DFDB_ERR_BOUNDS, "BoundsError: output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)cap);
+    uint8_t* bytes = o.bytes;
+    if (!dev && total > 0) { stage1.ensure((size_t)total + 64); bytes = stage1.as<uint8_t>(); }
+    prof_note(ctx, form == STR_GATHER_DIRECT ? "str_rows_sizes.direct" : "str_rows_sizes.offsets");
+    if (total > 0) { LaunchTimer lt(ctx, "str_rows_bytes"); launch_str_rows_bytes(s, sizes, S.src_off.as<int64_t>(), n, col.bytes.as<uint8_t>(), S.out_off.as<uint64_t>(), bytes, total); }
+    if (!dev) {
+      HIP_CHECK(hipMemcpyAsync(o.data, sizes, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+      if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, bytes, (size_t)total, hipMemcpyDeviceToHost, s));
+    }
+    o.nbytes = total;
+  }
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, S.flag.p, 8, hipMemcpyDeviceToHost, s));
+  stream_wait(ctx);                                  // (also: the staging buffers and a pageable `rows` die with this call)
+  if (ctx->pinned_scalar[0] != 0) fail_row_outside(t);
 }
 
 }  // namespace dfdb

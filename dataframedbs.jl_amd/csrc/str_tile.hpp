@@ -51,6 +51,21 @@ __device__ __forceinline__ void tile_sizes(const int32_t* sizes, int64_t base, i
   for (int j = 0; j < 16; j++) { const int64_t i = base + j * 64 + lane; sz[j] = i < nrows ? (NT ? __builtin_nontemporal_load(sizes + i) : sizes[i]) : past; }
 }
 
+// Where the tile's rows start, counted in bytes from the tile's first: pre[j] of a lane = the exclusive prefix of the clamped sizes over the tile's rows in
+// front of row j * 64 + lane — sixteen in-register wave scans and a running total.  Returns the tile's bytes.  (k_str_gather_bytes states the same loop in place,
+// between its own loads and its LDS stores, and stays as it was measured.)
+__device__ __forceinline__ uint32_t tile_prefix(const int32_t (&sz)[16], uint32_t (&pre)[16]) {
+  uint32_t run = 0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const uint32_t c = clamp_size(sz[j]);
+    const uint32_t incl = wave_incl_scan(c);
+    pre[j] = run + incl - c;
+    run += __shfl(incl, 63, 64);
+  }
+  return run;
+}
+
 // The tile's byte range in the arena, from the 16-byte boundary below its first byte: o0 = tile_off[tile], a0 the boundary, lead = o0 - a0 (0..15), and
 // span = the bytes from a0 that the staging moves: up to 31 bytes past the tile's end (a reader may look 15 bytes behind its string, and every arena is
 // allocated with 64 bytes of slack).  Wave-uniform.

@@ -883,6 +883,59 @@ class _Query:
         N.check(L.dfdb_gather_rows(self._h, ptr, n, kind, outs, ncols))
         return [np.ma.masked_array(a[:n].copy(), mask=m[:n].astype(bool)) if m is not None else a[:n].copy() for _, a, m in keep]
 
+    def gather_rows_string_bytes(self, col: int, rows=None, dev_ptr: Optional[int] = None, n: Optional[int] = None) -> int:
+        """dfdb_gather_rows_string_bytes: the string bytes projection column `col` needs at the 1-based table `rows` (0 for a fixed-width column)"""
+        if dev_ptr is None:
+            rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
+            n, ptr, kind = len(rows), (rows.ctypes.data if len(rows) else None), N.MEM_HOST
+        else:
+            n, ptr, kind = int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
+        nb = C.c_int64()
+        N.check(N.load().dfdb_gather_rows_string_bytes(self._h, col, ptr, n, kind, C.byref(nb)))
+        return nb.value
+
+    def gather_rows_any(self, rows=None, dev_ptr: Optional[int] = None, n: Optional[int] = None) -> List[Any]:
+        """dfdb_gather_rows_any: gather_rows for every plain column of the view, String columns included: a String column comes back as (int32 sizes with -1
+        for missing, concatenated bytes) in the order of `rows`, as materialize returns it, its buffer sized by dfdb_gather_rows_string_bytes; a nullable
+        fixed-width column comes back masked.  dev_ptr / n: the rows lie in device memory"""
+        L = N.load()
+        if dev_ptr is None:
+            rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
+            n, ptr, kind = len(rows), (rows.ctypes.data if len(rows) else None), N.MEM_HOST
+        else:
+            n, ptr, kind = int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
+        ncols = len(self.view.projection)
+        outs = (N.OutCol * max(ncols, 1))()
+        keep = []
+        for i in range(ncols):
+            dt = self.coltype(i)
+            o = outs[i]
+            o.memkind = N.MEM_HOST
+            if (dt & ir.DTYPE_MASK) == ir.STRING:
+                nb = C.c_int64()
+                N.check(L.dfdb_gather_rows_string_bytes(self._h, i, ptr, n, kind, C.byref(nb)))
+                sizes = np.empty(max(n, 1), np.int32)
+                data = np.empty(max(nb.value, 1), np.uint8)
+                keep.append((dt, sizes, data, None))
+                o.data, o.bytes, o.bytes_cap = sizes.ctypes.data, data.ctypes.data, nb.value
+                continue
+            arr = np.empty(max(n, 1), ir.numpy_of_dtype(dt))
+            miss = np.zeros(max(n, 1), np.uint8) if dt & ir.NULLABLE else None
+            keep.append((dt, arr, None, miss))
+            o.data = arr.ctypes.data
+            if miss is not None:
+                o.missing = miss.ctypes.data
+        N.check(L.dfdb_gather_rows_any(self._h, ptr, n, kind, outs, ncols))
+        res = []
+        for i, (dt, a, b, m) in enumerate(keep):
+            if (dt & ir.DTYPE_MASK) == ir.STRING:
+                res.append((a[:n].copy(), b[:outs[i].nbytes].copy()))
+            elif m is not None:
+                res.append(np.ma.masked_array(a[:n].copy(), mask=m[:n].astype(bool)))
+            else:
+                res.append(a[:n].copy())
+        return res
+
 
 class _ChunkQuery(_Query):
     """One chunk of a streamed view: the engine owns the handle (valid until the stream advances)."""
@@ -1326,8 +1379,9 @@ def sortperm_by(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] =
 
 
 def sort_view(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] = None):
-    """sort!(materialize(v), by; rev) (first(.., limit) when given): the view's projection columns — fixed-width ones — in the order of its column `by`, or
-    of its columns `by` when that is a list of names (the first one major; `rev` a bool or one per column)"""
+    """sort!(materialize(v), by; rev) (first(.., limit) when given): the view's projection columns, String columns included, in the order of its column `by`,
+    or of its columns `by` when that is a list of names (the first one major; `rev` a bool or one per column).  The keys are fixed-width columns (sorting BY a
+    String column is refused); every column follows them through dfdb_gather_rows_any"""
     if isinstance(v, DFTable):
         v = DFView(v)
     import pandas as pd
@@ -1337,7 +1391,17 @@ def sort_view(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] = N
     else:
         rows, _ = q.sort_indices_n(*_sort_keys(v, by, rev), limit)
     lg = _logicals(v)
-    return pd.DataFrame({k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(v.projection.keys(), q.gather_rows(rows)))})
+    return pd.DataFrame({k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(v.projection.keys(), q.gather_rows_any(rows)))})
+
+
+def take(v: Union[DFView, DFTable], rows):
+    """materialize(v)'s columns at given rows: the view's projection at the 1-based TABLE `rows` — any order, repeats allowed, whatever the view selects — as a
+    DataFrame (dfdb_gather_rows_any)"""
+    if isinstance(v, DFTable):
+        v = DFView(v)
+    import pandas as pd
+    lg = _logicals(v)
+    return pd.DataFrame({k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(v.projection.keys(), v._query().gather_rows_any(rows)))})
 
 
 def col_equal(a: DFColumn, b: DFColumn) -> bool:

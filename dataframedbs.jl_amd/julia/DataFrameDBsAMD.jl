@@ -761,6 +761,31 @@ function gpu_sort(c::DFColumn{T}; rev::Bool = false, limit::Integer = -1) where 
     end
 end
 
+"""
+    gpu_sort(v::DFView, cols::Vector{Symbol}; rev = false, limit = -1) -> DataFrame
+
+`sort!(materialize(v), cols; rev)` (its first `limit` rows when limit >= 0) on the device: the rows of `gpu_sortperm(v, cols; rev, limit)`, then every
+projection column of `v` at those rows through dfdb_gather_rows_any — String columns included, their buffers sized by dfdb_gather_rows_string_bytes and
+finished as `materialize` finishes them.  The keys are fixed-width columns; a computed column of `v` is `Unsupported`.
+"""
+function gpu_sort(v::DFView, cols::Vector{Symbol}; rev::Union{Bool,AbstractVector{Bool}} = false, limit::Integer = -1)
+    rows = gpu_sortperm(v, cols; rev = rev, limit = limit)
+    n = length(rows)
+    columns = with_query(v) do q
+        outs, bufs = alloc_outputs(v, n, i -> begin
+            dt = Ref{Int32}(0)
+            check(ccall((:dfdb_query_coltype, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), q, i, dt)); dt[]
+        end, i -> begin
+            nb = Ref{Int64}(0)
+            GC.@preserve rows check(ccall((:dfdb_gather_rows_string_bytes, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int64}, Int64, Int32, Ptr{Int64}), q, i, rows, n, 0, nb)); nb[]
+        end)
+        GC.@preserve bufs outs rows check(ccall((:dfdb_gather_rows_any, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64, Int32, Ptr{OutCol}, Int32),
+                                                q, rows, n, 0, outs, length(outs)))
+        finish_columns(v, bufs)
+    end
+    DataFrames.DataFrame(collect(columns), collect(keys(v.projection)), copycols = false)
+end
+
 # the stock path of the three overrides in enable!(): the column collected through the reference's own iteration, sorted on the host.  Defined with the module,
 # so they exist in the world age the fallback dispatches in
 stock_sort(c, rev) = sort(collect(c); rev = rev)

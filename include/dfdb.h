@@ -120,6 +120,8 @@ int32_t dfdb_jit_cache_dir(char* buf, size_t cap);
  *   4 int_lo, 5 int_hi and 6 wrap_int (parameter: dtype; 4 and 5 ignore the operand), 7 value_kind (dtype), 8 kind_dtype (kind), 9 the reduction identity of
  *   the DFDB_AGG_* operator in the operand (parameter: kind).
  *   "sort_geometry": the chunk geometry of dfdb_sort_indices' passes (csrc/k_sort.hip): out[0..1] = pairs per chunk, threads per workgroup.
+ *   "str_gather_form": the rule between the two forms of dfdb_gather_rows_any's String gather (csrc/kernels.hpp: str_gather_form): out[0..2] = rows asked
+ *   for, rows of the column, value of the context option "str_gather_form" (csrc/KNOBS.md); out[0] becomes the form, 1 = offsets, 2 = direct.
  * An unknown name is ArgumentError. */
 int32_t dfdb_selftest(const char* name, int64_t arg, int64_t* out, int32_t nout);
 int32_t dfdb_device_count(int32_t* n);   /* visible HIP devices (0 without a GPU: no error); the Julia shim forms a group when n > 1 */
@@ -462,6 +464,24 @@ int32_t dfdb_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32
  * out-of-core and compressed-only forms are DFDB_ERR_UNSUPPORTED with a message that names the form.  A row outside 1..nrows is DFDB_ERR_BOUNDS, and nothing
  * is written for that row. */
 int32_t dfdb_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols);
+/* string bytes projection column i needs for rows[0..n): sum of max(size, 0) of those rows; 0 for a fixed-width column (what sizes the `bytes` buffers of
+ * dfdb_gather_rows_any, as dfdb_result_string_bytes sizes dfdb_materialize's; with it: sort!(materialize(v), cols) over Base.iterate(::DFColumn),
+ * column.jl:102-126).  i is checked as dfdb_result_string_bytes checks it, the column as dfdb_gather_rows_any checks it (the same refusals); a row outside
+ * 1..nrows is DFDB_ERR_BOUNDS.  One pass over the rows' sizes and a scan; the query's selection is left as it was found. */
+int32_t dfdb_gather_rows_string_bytes(dfdb_query* q, int32_t i, const int64_t* rows, int64_t n, int32_t rows_memkind, int64_t* nbytes);
+/* dfdb_gather_rows for every plain column, String columns included (sort!(materialize(v), cols) over Base.iterate(::DFColumn), column.jl:102-126, for the
+ * ordinary view: String columns beside the key).  A fixed-width column is gathered exactly as dfdb_gather_rows gathers it.  For a String column (String or
+ * Union{String,Missing}) outs[i] is filled as dfdb_materialize fills it: data = n int32 sizes in the order of `rows` (-1 = missing), bytes = the rows' bytes
+ * concatenated in that order, count = n, nbytes = the bytes written, dtype; `missing` is ignored, memkind is per column.  `rows` as in dfdb_gather_rows: any
+ * order, repeats, independent of the selection, host or device memory.  A column with a dictionary is read through its flat form.  On the device
+ * (csrc/k_str_rows.hip): the rows' sizes and arena offsets, a scan of the per-1024-output byte totals, then the bytes; the offsets come from a per-row offset
+ * array built over the column for the call, or — few rows of a long column, n * 512 <= nrows — from a sum over the row's own tile.
+ * A row outside 1..nrows is DFDB_ERR_BOUNDS; it adds no byte and its size slot is not written.  Bytes beyond bytes_cap are DFDB_ERR_BOUNDS ("BoundsError:
+ * ... string bytes, capacity ..."), decided after the scan and before the bytes pass: nothing is written to `bytes`.  DFDB_ERR_UNSUPPORTED, with
+ * dfdb_gather_rows' messages: a computed column (a coalesce of String columns too), a view that is out of core, a compressed-only column; and a String column
+ * one 1024-row tile of which holds 2^22 bytes or more (the byte total of 1024 outputs is kept in 32 bits and they may all name the longest row).  Every
+ * argument and every column is checked before the first launch; the query's selection is left as it was found. */
+int32_t dfdb_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols);
 
 /* ---- out of core behind the ordinary entry points (round 6) ----
  * The reference never holds more than one block per column (src/io/blocksiterator.jl:98-121, src/io/BlockStreams.jl:9-15; "memory use is O(block)",
