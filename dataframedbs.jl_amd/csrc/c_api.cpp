@@ -528,13 +528,13 @@ int32_t dfdb_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32
   return guard([&] { NEEDQT(q); query_sort_indices_n(q, proj_cols, flags, nkeys, limit, out, cap, memkind, n, info); });
 }
 int32_t dfdb_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
-  return guard([&] { NEEDQT(q); if (n > 0) NEED(rows); if (ncols > 0) NEED(outs); query_gather_rows(q, rows, n, rows_memkind, outs, ncols); });
+  return guard([&] { NEEDQT(q); if (n > 0) NEED(rows); if (ncols > 0) NEED(outs); query_gather_rows(q, rows, n, rows_memkind, outs, ncols, false); });
 }
 int32_t dfdb_gather_rows_string_bytes(dfdb_query* q, int32_t i, const int64_t* rows, int64_t n, int32_t rows_memkind, int64_t* nbytes) {
   return guard([&] { NEEDQT(q); NEED(nbytes); if (n > 0) NEED(rows); *nbytes = query_gather_rows_string_bytes(q, i, rows, n, rows_memkind); });
 }
 int32_t dfdb_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
-  return guard([&] { NEEDQT(q); if (n > 0) NEED(rows); if (ncols > 0) NEED(outs); query_gather_rows_any(q, rows, n, rows_memkind, outs, ncols); });
+  return guard([&] { NEEDQT(q); if (n > 0) NEED(rows); if (ncols > 0) NEED(outs); query_gather_rows(q, rows, n, rows_memkind, outs, ncols, true); });
 }
 
 

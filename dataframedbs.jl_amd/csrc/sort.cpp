@@ -1,6 +1,7 @@
 // sort.cpp — ordering on the device: dfdb_sort_indices (the stable sortperm of the selected rows by one projection column, with a limit), dfdb_sort_indices_n
 // (the same by several columns, the most minor key first) and dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip;
-// dfdb_gather_rows_any and dfdb_gather_rows_string_bytes (the same gather with String columns admitted), over those of k_str_rows.hip.
+// dfdb_gather_rows_any and dfdb_gather_rows_string_bytes (the same gather with String columns admitted), over those of k_str_rows.hip.  ONE sort driver
+// (query_sort_indices_n: a single key is its n = 1 case) and ONE gather driver (query_gather_rows) stand behind them.
 //
 // Replaces sortperm(collect(col)), partialsortperm and sort over Base.iterate(::DFColumn) (src/tables/column.jl:102-126), which pull every selected value to
 // the host.  The host side here plans: which rows are kept (the top-k cut, found with the radix select of k_select.hip), which key bytes order anything (the
@@ -13,7 +14,7 @@
 namespace dfdb {
 
 // the plain fixed-width projection column p of q, resident and decoded — or the refusal that names the form (`what`: "sorting by" / "gathering rows of").
-// strings: a plain String column is admitted too (its flat form: sizes, arena, tile offsets — a column with a dictionary keeps it)
+// strings: a plain String column is admitted too (its flat form: sizes, arena, tile offsets — a column with a dictionary keeps it) when its tiles are short enough
 static const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool strings = false) {
   if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
   const Node& e = *q->proj[(size_t)p].expr;
@@ -25,7 +26,11 @@ static const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, 
   if (query_out_of_core(q)) fail(DFDB_ERR_UNSUPPORTED, "%s a column of a view that is out of core (its columns are not resident) is not supported: dfdb_table_load the columns first", what);
   if (t->cols[(size_t)e.col].comp_only)
     fail(DFDB_ERR_UNSUPPORTED, "%s the compressed-only column %s (keep_compressed = 2) is not supported: dfdb_table_decode_resident it first", what, t->cols[(size_t)e.col].name.c_str());
-  return need_resident(t, e.col);
+  const Column& col = need_resident(t, e.col);
+  if (str && col.max_tile_bytes >= kStrGatherMaxTileBytes)
+    fail(DFDB_ERR_UNSUPPORTED, "%s the String column %s is not supported: a 1024-row tile of it holds %u bytes, the limit is below %u (1024 outputs may repeat its longest row, and "
+         "their byte total is kept in 32 bits)", what, col.name.c_str(), col.max_tile_bytes, kStrGatherMaxTileBytes);
+  return col;
 }
 
 namespace {
@@ -66,6 +71,25 @@ static void check_sort_rows(const dfdb_table* t) {
   if (t->nrows >= (int64_t)1 << 31) fail(DFDB_ERR_UNSUPPORTED, "sorting a table of 2^31 rows or more is not supported: the pairs carry rows in 32 bits");
 }
 
+// The count phase of a build (Rec: SortBuild) or a rekey (SortRekey) over ntiles tiles: `count` launches the kernel that fills R.live_cnt / R.miss_cnt, both are
+// scanned into R.live_base / R.miss_base and their totals read back: {the pairs, the missing rows}
+struct SortCounts { int64_t npairs, nmiss; };
+template <class Rec, class Count> static SortCounts sort_count_phase(dfdb_ctx* ctx, SortScratch& S, int64_t ntiles, Rec& R, Count&& count) {
+  hipStream_t s = ctx->stream;
+  S.tile_cnt.ensure((size_t)(ntiles + 8) * 4 * 2); S.tile_base.ensure((size_t)(ntiles + 8) * 8 * 2); S.scan_scratch.ensure(scan_counts_scratch_bytes(ntiles));
+  R.live_cnt = S.tile_cnt.as<uint32_t>(); R.miss_cnt = R.live_cnt + (ntiles + 8);
+  count();
+  uint64_t* lb = S.tile_base.as<uint64_t>(); uint64_t* mb = lb + (ntiles + 8);
+  { LaunchTimer lt(ctx, "scan_counts");
+    launch_scan_counts(s, R.live_cnt, lb, ntiles, S.scan_scratch.as<uint64_t>());
+    launch_scan_counts(s, R.miss_cnt, mb, ntiles, S.scan_scratch.as<uint64_t>()); }
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, lb + ntiles, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar + 1, mb + ntiles, 8, hipMemcpyDeviceToHost, s));
+  stream_wait(ctx);
+  R.live_base = lb; R.miss_base = mb;
+  return {ctx->pinned_scalar[0], ctx->pinned_scalar[1]};
+}
+
 // The build from the selection: the pairs of the selected rows `col` keeps (not missing; P.cut: key <= the cut; P.L == 0: none) into S.keys[0] / S.rows[0]
 // and the selected missing rows into S.miss_rows, both in table order; the kept keys' per-byte histograms into S.hist.  Returns the pairs; *nmiss: the
 // missing rows.  check: the counts must agree with the plan's
@@ -81,21 +105,12 @@ static int64_t sort_build_pairs(dfdb_query* q, const Column& col, SortScratch& S
   *nmiss = 0;
   if (!dt_nullable(col.dtype) && !P.cut) B.live_base = q->prefix.as<uint64_t>();     // every selected row is kept: the selection's own scan places them
   else {                                                                // count the kept and the missing rows per tile, scan both
-    S.tile_cnt.ensure((size_t)(ntiles + 8) * 4 * 2); S.tile_base.ensure((size_t)(ntiles + 8) * 8 * 2); S.scan_scratch.ensure(scan_counts_scratch_bytes(ntiles));
-    B.live_cnt = S.tile_cnt.as<uint32_t>(); B.miss_cnt = B.live_cnt + (ntiles + 8);
-    HIP_CHECK(hipMemsetAsync(S.tile_cnt.p, 0, (size_t)(ntiles + 8) * 4 * 2, s));
-    { LaunchTimer lt(ctx, "sort_build"); launch_sort_build(s, col_ref(col), B, true); }
-    uint64_t* lb = S.tile_base.as<uint64_t>(); uint64_t* mb = lb + (ntiles + 8);
-    { LaunchTimer lt(ctx, "scan_counts");
-      launch_scan_counts(s, B.live_cnt, lb, ntiles, S.scan_scratch.as<uint64_t>());
-      launch_scan_counts(s, B.miss_cnt, mb, ntiles, S.scan_scratch.as<uint64_t>()); }
-    HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, lb + ntiles, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar + 1, mb + ntiles, 8, hipMemcpyDeviceToHost, s));
-    stream_wait(ctx);
-    npairs = ctx->pinned_scalar[0]; *nmiss = ctx->pinned_scalar[1];
+    const SortCounts c = sort_count_phase(ctx, S, ntiles, B, [&] {
+      HIP_CHECK(hipMemsetAsync(B.live_cnt, 0, (size_t)(ntiles + 8) * 4 * 2, s));       // (a tile with no selected row writes no count)
+      LaunchTimer lt(ctx, "sort_build"); launch_sort_build(s, col_ref(col), B, true); });
+    npairs = c.npairs; *nmiss = c.nmiss;
     if (check && (*nmiss != P.nmiss || npairs < P.L)) fail(DFDB_ERR_DEVICE, "sort: the build counted %lld kept and %lld missing rows, the plan has %lld and %lld",
                                                            (long long)npairs, (long long)*nmiss, (long long)P.L, (long long)P.nmiss);
-    B.live_base = lb; B.miss_base = mb;
   }
   S.keys[0].ensure((size_t)std::max<int64_t>(npairs, 1) * 8); S.rows[0].ensure((size_t)std::max<int64_t>(npairs, 1) * 4);
   S.miss_rows.ensure((size_t)std::max<int64_t>(*nmiss, 1) * 4);
@@ -151,46 +166,15 @@ static void sort_emit_rows(dfdb_table* t, SortScratch& S, const uint32_t* first,
   if (memkind != DFDB_MEM_DEVICE && m > 0) { HIP_CHECK(hipMemcpyAsync(out, dst, (size_t)m * 8, hipMemcpyDeviceToHost, s)); stream_wait(ctx); }
 }
 
-void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
-  check_sort_flags(flags);
-  const Column& col = ordered_column(q, p, "sorting by");
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
-  check_sort_rows(t);
-  ensure_executed_checked(q);
-  const bool rev = (flags & DFDB_SORT_REV) != 0;
-  const int nbytes = select_key_bits(dt_base(col.dtype), false) / 8;
-  const int64_t sel = query_count(q, -1);
-  const int64_t total = limit < 0 ? sel : std::min(limit, sel);
-  int64_t inf[4] = {sel, 0, 0, nbytes};
-  if (n) *n = total;
-  const int64_t m = std::min(total, std::max<int64_t>(cap, 0));
-  if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
-  if (total == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
-
-  SortScratch S(ctx);
-  const SortPlan P = plan_sort(q, col, rev, limit, sel);
-  int64_t nmiss = 0;
-  const int64_t npairs = sort_build_pairs(q, col, S, rev, P, true, sel, &nmiss);
-  inf[1] = npairs;
-  const int cur = sort_run_passes(ctx, S, npairs, npairs, nbytes, &inf[2]);
-  inf[3] = nbytes - inf[2];
-
-  // the first `total` of: the sorted live rows, the missing rows behind them (REV: before them) in table order; `m` of them fit the caller's buffer
-  const int64_t miss_out = rev ? std::min(total, P.nmiss) : total - std::min(total, P.nlive), live_out = total - miss_out;
-  const int64_t first_n = std::min(m, rev ? miss_out : live_out), second_n = m - first_n;
-  const uint32_t* live_rows = S.rows[cur].as<uint32_t>();
-  sort_emit_rows(t, S, rev ? S.miss_rows.as<uint32_t>() : live_rows, first_n, rev ? live_rows : S.miss_rows.as<uint32_t>(), second_n, out, memkind);
-  if (info) memcpy(info, inf, sizeof inf);
-}
-
-// The sort by several keys, least significant first: the most minor key is sorted from the selection like a single key; every further key towards the
-// major one is built from the ORDER the keys behind it left (k_sort_rekey) and sorted by the same stable passes, so rows equal in it keep that order.
-// After each key its sorted live rows and its missing rows (behind them, REV: before them) are laid into S.order — the next key's input
+// THE sort driver, the keys taken least significant first: the most minor key is built from the selection; every further key towards the major one is built
+// from the ORDER the keys behind it left (k_sort_rekey) and sorted by the same stable passes, so rows equal in it keep that order.  After each key its sorted
+// live rows and its missing rows (behind them, REV: before them) are laid into S.order — the next key's input; the last key's two lists are the answer.
+// A single key is the n = 1 case, different in its plan alone: its build keeps no more than the limit needs (plan_sort's top-k cut) and its scratch is sized
+// by what is kept, where several keys sort every selected row and the limit only cuts what comes back
 void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
                           int64_t* n, int64_t* info) {
   if (nkeys < 1 || nkeys > DFDB_SORT_MAX_KEYS) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %d sort keys (1 to %d)", nkeys, (int)DFDB_SORT_MAX_KEYS);
   if (!proj_cols || !flags) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no sort %s", proj_cols ? "flags" : "columns");
-  if (nkeys == 1) return query_sort_indices(q, proj_cols[0], flags[0], limit, out, cap, memkind, n, info);
   for (int32_t j = 0; j < nkeys; j++) check_sort_flags(flags[j]);
   const Column* cols[DFDB_SORT_MAX_KEYS];
   for (int32_t j = 0; j < nkeys; j++) cols[j] = &ordered_column(q, proj_cols[j], "sorting by");
@@ -204,10 +188,13 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
   if (n) *n = total;
   const int64_t m = std::min(total, std::max<int64_t>(cap, 0));
   if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
-  if (sel == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
+  // nothing to do: one key with nothing to return (limit = 0 too: the cut would keep no pair); several keys sort whatever the limit is and report that sort
+  // in info, so only an empty selection ends them here
+  const bool one = nkeys == 1;
+  if (one ? total == 0 : sel == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
 
   SortScratch S(ctx);
-  S.keys[0].ensure((size_t)sel * 8); S.rows[0].ensure((size_t)sel * 4); S.miss_rows.ensure((size_t)sel * 4); S.order.ensure((size_t)sel * 4);
+  if (!one) { S.keys[0].ensure((size_t)sel * 8); S.rows[0].ensure((size_t)sel * 4); S.miss_rows.ensure((size_t)sel * 4); S.order.ensure((size_t)sel * 4); }
   const int64_t otiles = ceil_div(sel, kTileRows);
   const uint32_t *first = nullptr, *second = nullptr;      // the key's two lists in output order, first_len rows in the first
   int64_t first_len = 0;
@@ -217,8 +204,9 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
     const int nbits = select_key_bits(dt_base(col.dtype), false), nbytes = nbits / 8;
     int64_t npairs = sel, nmiss = 0;
     if (j == nkeys - 1) {
-      SortPlan all; all.L = sel;                            // no cut: every selected row that is not missing is kept
-      npairs = sort_build_pairs(q, col, S, rev, all, false, sel, &nmiss);
+      SortPlan P; P.L = sel;                                // several keys: no cut, every selected row that is not missing is kept
+      if (one) P = plan_sort(q, col, rev, limit, sel);
+      npairs = sort_build_pairs(q, col, S, rev, P, one, sel, &nmiss);       // (one key: sized by the pairs kept)
     } else {
       // lay the key behind into the order this one starts from
       uint32_t* order = S.order.as<uint32_t>();
@@ -228,19 +216,9 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
       SortRekey R{};
       R.order = order; R.n = sel; R.nrows = t->nrows; R.flip = flip_of(nbits, rev);
       if (dt_nullable(col.dtype)) {                         // count the live and the missing entries per 1024 entries of the order, scan both
-        S.tile_cnt.ensure((size_t)(otiles + 8) * 4 * 2); S.tile_base.ensure((size_t)(otiles + 8) * 8 * 2); S.scan_scratch.ensure(scan_counts_scratch_bytes(otiles));
-        R.live_cnt = S.tile_cnt.as<uint32_t>(); R.miss_cnt = R.live_cnt + (otiles + 8);
-        { LaunchTimer lt(ctx, "sort_rekey"); launch_sort_rekey(s, col_ref(col), R, true); }
-        uint64_t* lb = S.tile_base.as<uint64_t>(); uint64_t* mb = lb + (otiles + 8);
-        { LaunchTimer lt(ctx, "scan_counts");
-          launch_scan_counts(s, R.live_cnt, lb, otiles, S.scan_scratch.as<uint64_t>());
-          launch_scan_counts(s, R.miss_cnt, mb, otiles, S.scan_scratch.as<uint64_t>()); }
-        HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, lb + otiles, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar + 1, mb + otiles, 8, hipMemcpyDeviceToHost, s));
-        stream_wait(ctx);
-        npairs = ctx->pinned_scalar[0]; nmiss = ctx->pinned_scalar[1];
+        const SortCounts c = sort_count_phase(ctx, S, otiles, R, [&] { LaunchTimer lt(ctx, "sort_rekey"); launch_sort_rekey(s, col_ref(col), R, true); });
+        npairs = c.npairs; nmiss = c.nmiss;
         if (npairs + nmiss != sel) fail(DFDB_ERR_DEVICE, "sort: the rekey counted %lld live and %lld missing rows of %lld", (long long)npairs, (long long)nmiss, (long long)sel);
-        R.live_base = lb; R.miss_base = mb;
       }
       R.keys = S.keys[0].as<uint64_t>(); R.rows = S.rows[0].as<uint32_t>(); R.cap = npairs;
       R.miss_rows = S.miss_rows.as<uint32_t>(); R.miss_cap = nmiss;
@@ -249,25 +227,49 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
       { LaunchTimer lt(ctx, "sort_rekey"); launch_sort_rekey(s, col_ref(col), R, false); }
     }
     int64_t run = 0;
-    const int cur = sort_run_passes(ctx, S, npairs, sel, nbytes, &run);
+    const int cur = sort_run_passes(ctx, S, npairs, one ? npairs : sel, nbytes, &run);
     inf[1] += npairs; inf[2] += run; inf[3] -= run;
     const uint32_t* live_rows = S.rows[cur].as<uint32_t>();
     first = rev ? S.miss_rows.as<uint32_t>() : live_rows; second = rev ? live_rows : S.miss_rows.as<uint32_t>();
     first_len = rev ? nmiss : npairs;
   }
+  // the first m of the two lists (a cut keeps every pair up to the cut key: no fewer than the limit takes of the live rows)
   const int64_t first_n = std::min(m, first_len);
   sort_emit_rows(t, S, first, first_n, second, m - first_n, out, memkind);
   if (info) memcpy(info, inf, sizeof inf);
 }
 
-// ---- the projection at given rows --------------------------------------------------------------------------------------------------------------------------
-// rows[0 .. n) in device memory: the caller's own, or a copy of a host list in `hold`
-static const int64_t* rows_on_device(hipStream_t s, const int64_t* rows, int64_t n, int32_t rows_memkind, DevBuf& hold) {
-  if (rows_memkind == DFDB_MEM_DEVICE) return rows;
-  hold.ensure((size_t)n * 8);
-  HIP_CHECK(hipMemcpyAsync(hold.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  return hold.as<int64_t>();
+void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
+  query_sort_indices_n(q, &p, &flags, 1, limit, out, cap, memkind, n, info);
 }
+
+// ---- the projection at given rows: a fixed-width column by one kernel; a String column (k_str_rows.hip) by the offsets of the gathered sizes, then the bytes -------
+namespace {
+// A gather's device memory — the rows, the flag word a row outside raises, the String passes' arrays, the staging of host outputs: from the pool, back to it
+// when the call ends, the stream drained first.  A call that ends with a wait of its own makes it through wait(), and the destructor does not wait again
+struct RowsScratch {
+  dfdb_ctx* ctx;
+  DevBuf rows, flag, row_off, src_off, grp_bytes, out_off, scan_scratch;
+  std::vector<DevBuf> stages;                       // per column: data (a String column: sizes), missing bytes (a String column: bytes)
+  const int64_t* drows;                             // r[0 .. n) in device memory: the caller's own, or the copy of a host list in `rows`
+  bool drained = false;
+  RowsScratch(dfdb_ctx* c, int32_t ncols, const int64_t* r, int64_t n, int32_t rows_memkind) : ctx(c), stages((size_t)ncols * 2), drows(r) {
+    if (rows_memkind != DFDB_MEM_DEVICE) {
+      rows.ensure((size_t)n * 8); drows = rows.as<int64_t>();
+      HIP_CHECK(hipMemcpyAsync(rows.p, r, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    flag.ensure(64);
+    HIP_CHECK(hipMemsetAsync(flag.p, 0, 8, ctx->stream));
+  }
+  void wait() { stream_wait(ctx); drained = true; }
+  ~RowsScratch() {
+    if (!drained) (void)hipStreamSynchronize(ctx->stream);
+    RecycleScope rs;
+    for (DevBuf* b : {&rows, &flag, &row_off, &src_off, &grp_bytes, &out_off, &scan_scratch}) b->release();
+    for (DevBuf& b : stages) b.release();
+  }
+};
+}  // namespace
 [[noreturn]] static void fail_row_outside(const dfdb_table* t) { fail(DFDB_ERR_BOUNDS, "BoundsError: a row outside 1..%lld", (long long)(t->row_base + t->nrows)); }
 
 // fixed-width column `col` at drows[0 .. n) into o (device output: in place; host output: through stage / mstage, queued, not waited for)
@@ -289,57 +291,9 @@ static void gather_fixed_column(dfdb_table* t, const Column& col, dfdb_outcol& o
   }
 }
 
-void query_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
-  if (ncols != (int32_t)q->proj.size()) fail(DFDB_ERR_ARGUMENT, "ArgumentError: view has %zu columns, %d outputs given", q->proj.size(), ncols);
-  if (n < 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %lld rows", (long long)n);
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  std::vector<const Column*> cols;
-  for (int32_t p = 0; p < ncols; p++) cols.push_back(&ordered_column(q, p, "gathering rows of"));
-  for (int32_t p = 0; p < ncols; p++) {
-    outs[p].dtype = q->proj[(size_t)p].expr->dtype; outs[p].count = n; outs[p].nbytes = 0;
-    if (n > 0 && !outs[p].data) fail(DFDB_ERR_ARGUMENT, "output column %d has no data buffer", p);
-  }
-  if (n == 0) return;
-  DevBuf rows_dev, flag;
-  const int64_t* drows = rows_on_device(s, rows, n, rows_memkind, rows_dev);
-  flag.ensure(64);
-  HIP_CHECK(hipMemsetAsync(flag.p, 0, 8, s));
-  std::vector<DevBuf> stages((size_t)ncols * 2);
-  for (int32_t p = 0; p < ncols; p++) gather_fixed_column(t, *cols[(size_t)p], outs[p], drows, n, flag.as<uint32_t>(), stages[(size_t)p * 2], stages[(size_t)p * 2 + 1]);
-  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, flag.p, 8, hipMemcpyDeviceToHost, s));
-  stream_wait(ctx);                                  // (also: the staging buffers and a pageable `rows` die with this call)
-  if (ctx->pinned_scalar[0] != 0) fail_row_outside(t);
-}
-
-// ---- the same with String columns (k_str_rows.hip): offsets of the gathered sizes, then the bytes -------------------------------------------------------------
-namespace {
-// the String gather's device memory, and the staging of host outputs: from the pool, back to it when the call ends (the stream drained first)
-struct RowsScratch {
-  dfdb_ctx* ctx;
-  DevBuf rows, flag, row_off, src_off, grp_bytes, out_off, scan_scratch;
-  std::vector<DevBuf> stages;                       // per column: data (a String column: sizes), missing bytes (a String column: bytes)
-  RowsScratch(dfdb_ctx* c, int32_t ncols) : ctx(c), stages((size_t)ncols * 2) {}
-  ~RowsScratch() {
-    (void)hipStreamSynchronize(ctx->stream);
-    RecycleScope rs;
-    for (DevBuf* b : {&rows, &flag, &row_off, &src_off, &grp_bytes, &out_off, &scan_scratch}) b->release();
-    for (DevBuf& b : stages) b.release();
-  }
-};
-}  // namespace
-
-// a plain column of the view for a gather at given rows, String admitted — or the refusal that names the form, or the column
-static const Column& rows_column(dfdb_query* q, int32_t p) {
-  const Column& col = ordered_column(q, p, "gathering rows of", true);
-  if (dt_base(col.dtype) == DFDB_STRING && col.max_tile_bytes >= kStrGatherMaxTileBytes)
-    fail(DFDB_ERR_UNSUPPORTED, "gathering rows of the String column %s is not supported: a 1024-row tile of it holds %u bytes, the limit is below %u (1024 outputs may repeat its longest row, and "
-         "their byte total is kept in 32 bits)", col.name.c_str(), col.max_tile_bytes, kStrGatherMaxTileBytes);
-  return col;
-}
-
-// The sizes pass and the scan of String column `col` at drows[0 .. n): S.out_off[groups + 1], and the bytes the rows need (the scan's last entry) — read back
+// The sizes pass and the scan of String column `col` at S.drows[0 .. n): S.out_off[groups + 1], and the bytes the rows need (the scan's last entry) — read back
 // together with the flag word, whose refusal comes first.  form LAYOUT: totals only; else out_sizes (device memory, n entries) and S.src_off are written too
-static int64_t rows_string_layout(dfdb_table* t, const Column& col, RowsScratch& S, const int64_t* drows, int64_t n, StrGatherForm form, int32_t* out_sizes) {
+static int64_t rows_string_layout(dfdb_table* t, const Column& col, RowsScratch& S, int64_t n, StrGatherForm form, int32_t* out_sizes) {
   dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const int64_t ngroups = ceil_div(n, kTileRows);
   S.grp_bytes.ensure((size_t)(ngroups + 8) * 4); S.out_off.ensure((size_t)(ngroups + 8) * 8); S.scan_scratch.ensure(scan_counts_scratch_bytes(ngroups));
@@ -348,7 +302,7 @@ static int64_t rows_string_layout(dfdb_table* t, const Column& col, RowsScratch&
     S.row_off.ensure((size_t)std::max<int64_t>(t->nrows, 1) * 4);
     LaunchTimer lt(ctx, "str_row_offsets"); launch_str_row_offsets(s, col.data.as<int32_t>(), S.row_off.as<uint32_t>(), t->nrows);
   }
-  const StrRows R{drows, n, str_side(col), t->row_base, t->nrows, S.flag.as<uint32_t>()};
+  const StrRows R{S.drows, n, str_side(col), t->row_base, t->nrows, S.flag.as<uint32_t>()};
   { LaunchTimer lt(ctx, "str_rows_sizes"); launch_str_rows_sizes(s, R, form, S.row_off.as<uint32_t>(), out_sizes, S.src_off.as<int64_t>(), S.grp_bytes.as<uint32_t>()); }
   { LaunchTimer lt(ctx, "scan_counts"); launch_scan_counts(s, S.grp_bytes.as<uint32_t>(), S.out_off.as<uint64_t>(), ngroups, S.scan_scratch.as<uint64_t>()); }
   HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, S.flag.p, 8, hipMemcpyDeviceToHost, s));
@@ -358,65 +312,60 @@ static int64_t rows_string_layout(dfdb_table* t, const Column& col, RowsScratch&
   return ctx->pinned_scalar[1];
 }
 
-static void rows_scratch_begin(dfdb_table* t, RowsScratch& S, const int64_t* rows, int64_t n, int32_t rows_memkind, const int64_t** drows) {
-  hipStream_t s = t->ctx->stream;
-  *drows = rows_on_device(s, rows, n, rows_memkind, S.rows);
-  S.flag.ensure(64);
-  HIP_CHECK(hipMemsetAsync(S.flag.p, 0, 8, s));
+// String column `col` at S.drows[0 .. n) into o, the view's output p (device output: in place; host output: through the column's two stages, queued, not waited for)
+static void gather_string_column(dfdb_table* t, const Column& col, dfdb_outcol& o, int32_t p, RowsScratch& S, int64_t n) {
+  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  DevBuf& stage0 = S.stages[(size_t)p * 2]; DevBuf& stage1 = S.stages[(size_t)p * 2 + 1];
+  const StrGatherForm form = str_gather_form(n, t->nrows, ctx_option(ctx, "str_gather_form", 0));
+  const bool dev = o.memkind == DFDB_MEM_DEVICE;
+  int32_t* sizes = (int32_t*)o.data;
+  if (!dev) {
+    stage0.ensure((size_t)n * 4); sizes = stage0.as<int32_t>();
+    HIP_CHECK(hipMemsetAsync(sizes, 0, (size_t)n * 4, s));           // (a refused row writes nothing: the host copy must not carry pool bytes)
+  }
+  // the rows' sizes and where their bytes start, then — on the host, before a byte moves — whether the bytes fit
+  const int64_t total = rows_string_layout(t, col, S, n, form, sizes);
+  const int64_t cap = o.bytes ? o.bytes_cap : 0;
+  if (total > cap) fail(DFDB_ERR_BOUNDS, "BoundsError: output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)cap);
+  uint8_t* bytes = o.bytes;
+  if (!dev && total > 0) { stage1.ensure((size_t)total + 64); bytes = stage1.as<uint8_t>(); }
+  prof_note(ctx, form == STR_GATHER_DIRECT ? "str_rows_sizes.direct" : "str_rows_sizes.offsets");
+  if (total > 0) { LaunchTimer lt(ctx, "str_rows_bytes"); launch_str_rows_bytes(s, sizes, S.src_off.as<int64_t>(), n, col.bytes.as<uint8_t>(), S.out_off.as<uint64_t>(), bytes, total); }
+  if (!dev) {
+    HIP_CHECK(hipMemcpyAsync(o.data, sizes, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, bytes, (size_t)total, hipMemcpyDeviceToHost, s));
+  }
+  o.nbytes = total;
 }
 
 int64_t query_gather_rows_string_bytes(dfdb_query* q, int32_t i, const int64_t* rows, int64_t n, int32_t rows_memkind) {
   if (n < 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %lld rows", (long long)n);
-  const Column& col = rows_column(q, i);
+  const Column& col = ordered_column(q, i, "gathering rows of", true);
   if (dt_base(col.dtype) != DFDB_STRING || n == 0) return 0;
-  dfdb_table* t = q->t;
-  RowsScratch S(t->ctx, 0);
-  const int64_t* drows;
-  rows_scratch_begin(t, S, rows, n, rows_memkind, &drows);
-  return rows_string_layout(t, col, S, drows, n, STR_GATHER_LAYOUT, nullptr);
+  RowsScratch S(q->t->ctx, 0, rows, n, rows_memkind);
+  return rows_string_layout(q->t, col, S, n, STR_GATHER_LAYOUT, nullptr);
 }
 
-void query_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
+// THE gather driver.  strings: String columns are admitted (dfdb_gather_rows_any); else one is refused by name (dfdb_gather_rows)
+void query_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols, bool strings) {
   if (ncols != (int32_t)q->proj.size()) fail(DFDB_ERR_ARGUMENT, "ArgumentError: view has %zu columns, %d outputs given", q->proj.size(), ncols);
   if (n < 0) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %lld rows", (long long)n);
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
+  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
   std::vector<const Column*> cols;
-  for (int32_t p = 0; p < ncols; p++) cols.push_back(&rows_column(q, p));
+  for (int32_t p = 0; p < ncols; p++) cols.push_back(&ordered_column(q, p, "gathering rows of", strings));
   for (int32_t p = 0; p < ncols; p++) {
     outs[p].dtype = q->proj[(size_t)p].expr->dtype; outs[p].count = n; outs[p].nbytes = 0;
     if (n > 0 && !outs[p].data) fail(DFDB_ERR_ARGUMENT, "output column %d has no data buffer", p);
   }
   if (n == 0) return;
-  RowsScratch S(ctx, ncols);
-  const int64_t* drows;
-  rows_scratch_begin(t, S, rows, n, rows_memkind, &drows);
-  const StrGatherForm form = str_gather_form(n, t->nrows, ctx_option(ctx, "str_gather_form", 0));
+  RowsScratch S(ctx, ncols, rows, n, rows_memkind);
   for (int32_t p = 0; p < ncols; p++) {
-    const Column& col = *cols[(size_t)p]; dfdb_outcol& o = outs[p];
-    DevBuf& stage0 = S.stages[(size_t)p * 2]; DevBuf& stage1 = S.stages[(size_t)p * 2 + 1];
-    if (dt_base(col.dtype) != DFDB_STRING) { gather_fixed_column(t, col, o, drows, n, S.flag.as<uint32_t>(), stage0, stage1); continue; }
-    const bool dev = o.memkind == DFDB_MEM_DEVICE;
-    int32_t* sizes = (int32_t*)o.data;
-    if (!dev) {
-      stage0.ensure((size_t)n * 4); sizes = stage0.as<int32_t>();
-      HIP_CHECK(hipMemsetAsync(sizes, 0, (size_t)n * 4, s));           // (a refused row writes nothing: the host copy must not carry pool bytes)
-    }
-    // the rows' sizes and where their bytes start, then — on the host, before a byte moves — whether the bytes fit
-    const int64_t total = rows_string_layout(t, col, S, drows, n, form, sizes);
-    const int64_t cap = o.bytes ? o.bytes_cap : 0;
-    if (total > cap) fail(DFDB_ERR_BOUNDS, "BoundsError: output column %d needs %lld string bytes, capacity is %lld", p, (long long)total, (long long)cap);
-    uint8_t* bytes = o.bytes;
-    if (!dev && total > 0) { stage1.ensure((size_t)total + 64); bytes = stage1.as<uint8_t>(); }
-    prof_note(ctx, form == STR_GATHER_DIRECT ? "str_rows_sizes.direct" : "str_rows_sizes.offsets");
-    if (total > 0) { LaunchTimer lt(ctx, "str_rows_bytes"); launch_str_rows_bytes(s, sizes, S.src_off.as<int64_t>(), n, col.bytes.as<uint8_t>(), S.out_off.as<uint64_t>(), bytes, total); }
-    if (!dev) {
-      HIP_CHECK(hipMemcpyAsync(o.data, sizes, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-      if (total > 0) HIP_CHECK(hipMemcpyAsync(o.bytes, bytes, (size_t)total, hipMemcpyDeviceToHost, s));
-    }
-    o.nbytes = total;
+    const Column& col = *cols[(size_t)p];
+    if (dt_base(col.dtype) == DFDB_STRING) gather_string_column(t, col, outs[p], p, S, n);
+    else gather_fixed_column(t, col, outs[p], S.drows, n, S.flag.as<uint32_t>(), S.stages[(size_t)p * 2], S.stages[(size_t)p * 2 + 1]);
   }
-  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, S.flag.p, 8, hipMemcpyDeviceToHost, s));
-  stream_wait(ctx);                                  // (also: the staging buffers and a pageable `rows` die with this call)
+  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, S.flag.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  S.wait();                                          // (also: the staging buffers and a pageable `rows` die with this call)
   if (ctx->pinned_scalar[0] != 0) fail_row_outside(t);
 }
 

@@ -748,25 +748,25 @@ class _Query:
     def hint_materialize(self, on: bool = True):
         N.check(N.load().dfdb_query_hint_materialize(self._h, 1 if on else 0))
 
-    def materialize(self) -> List[Any]:
-        L = N.load()
-        self.hint_materialize(True)       # count() below is the scan: let it keep projected predicate columns
-        n = self.count()
+    def _columns_out(self, n: int, fill, string_bytes=None) -> List[Any]:
+        """n rows of every projection column through host outputs that fill(outs, ncols) has the library write: a String column as (int32 sizes, bytes), its
+        buffer sized by string_bytes(i) (None: it gets no buffer — the library refuses it by name), a nullable fixed-width column masked"""
         ncols = len(self.view.projection)
         outs = (N.OutCol * max(ncols, 1))()
         keep = []
         for i in range(ncols):
             dt = self.coltype(i)
-            base = dt & ir.DTYPE_MASK
             o = outs[i]
             o.memkind = N.MEM_HOST
-            if base == ir.STRING:
-                nb = C.c_int64()
-                N.check(L.dfdb_result_string_bytes(self._h, i, C.byref(nb)))
+            if (dt & ir.DTYPE_MASK) == ir.STRING:
+                if string_bytes is None:
+                    keep.append((dt, None, None, None))
+                    continue
+                nb = string_bytes(i)
                 sizes = np.empty(max(n, 1), np.int32)
-                data = np.empty(max(nb.value, 1), np.uint8)
+                data = np.empty(max(nb, 1), np.uint8)
                 keep.append((dt, sizes, data, None))
-                o.data, o.bytes, o.bytes_cap = sizes.ctypes.data, data.ctypes.data, nb.value
+                o.data, o.bytes, o.bytes_cap = sizes.ctypes.data, data.ctypes.data, nb
             else:
                 arr = np.empty(max(n, 1), ir.numpy_of_dtype(dt))
                 miss = np.zeros(max(n, 1), np.uint8) if dt & ir.NULLABLE else None
@@ -774,8 +774,7 @@ class _Query:
                 o.data = arr.ctypes.data
                 if miss is not None:
                     o.missing = miss.ctypes.data
-        if ncols:
-            N.check(L.dfdb_materialize(self._h, outs, ncols))
+        fill(outs, ncols)
         res = []
         for i, (dt, a, b, m) in enumerate(keep):
             if (dt & ir.DTYPE_MASK) == ir.STRING:
@@ -785,6 +784,17 @@ class _Query:
             else:
                 res.append(a[:n].copy())
         return res
+
+    def materialize(self) -> List[Any]:
+        L = N.load()
+        self.hint_materialize(True)       # count() below is the scan: let it keep projected predicate columns
+
+        def string_bytes(i):
+            nb = C.c_int64()
+            N.check(L.dfdb_result_string_bytes(self._h, i, C.byref(nb)))
+            return nb.value
+
+        return self._columns_out(self.count(), lambda outs, ncols: N.check(L.dfdb_materialize(self._h, outs, ncols)) if ncols else None, string_bytes)
 
     def hint_aggregate(self, op: int, col: int = 0):
         N.check(N.load().dfdb_query_hint_aggregate(self._h, op, col))
@@ -822,16 +832,21 @@ class _Query:
         """dfdb_sort_indices: (rows, info) — the 1-based table rows of the selected rows in the stable order of projection column `col` (rev: descending;
         ties keep ascending row order both ways; missing rows last, first under rev), cut to the first `limit`; info = (selected rows, pairs sorted,
         digit passes run, digit passes skipped).  dev_ptr: write into device memory holding `cap` entries instead, without a count: (None, info)"""
-        L = N.load()
-        flags, lim = (N.SORT_REV if rev else 0), (-1 if limit is None else int(limit))
+        L, flags = N.load(), (N.SORT_REV if rev else 0)
+        return self._sorted_rows(lambda *out: L.dfdb_sort_indices(self._h, col, flags, *out), limit, dev_ptr, cap)
+
+    def _sorted_rows(self, sort, limit, dev_ptr, cap):
+        """sort(limit, out, cap, memkind, n, info) — the tail of both sort entry points — into device memory at dev_ptr (`cap` entries, no count read back) or
+        into a host array of the count: (rows or None, info)"""
+        lim = -1 if limit is None else int(limit)
         info = np.zeros(4, np.int64)
         if dev_ptr is not None:
-            N.check(L.dfdb_sort_indices(self._h, col, flags, lim, C.c_void_p(dev_ptr), int(cap), N.MEM_DEVICE, None, info.ctypes.data))
+            N.check(sort(lim, C.c_void_p(dev_ptr), int(cap), N.MEM_DEVICE, None, info.ctypes.data))
             return None, tuple(int(x) for x in info)
         n = self.count() if lim < 0 else min(lim, self.count())
         out = np.empty(n, np.int64)
         got = C.c_int64()
-        N.check(L.dfdb_sort_indices(self._h, col, flags, lim, out.ctypes.data if n else None, n, N.MEM_HOST, C.byref(got), info.ctypes.data))
+        N.check(sort(lim, out.ctypes.data if n else None, n, N.MEM_HOST, C.byref(got), info.ctypes.data))
         return out[:got.value], tuple(int(x) for x in info)
 
     def sort_indices_n(self, cols, revs=None, limit: Optional[int] = None, dev_ptr: Optional[int] = None, cap: Optional[int] = None):
@@ -844,52 +859,25 @@ class _Query:
         fl = np.zeros(len(ci), np.int32) if revs is None else np.array([N.SORT_REV if r else 0 for r in revs], np.int32)
         if len(fl) != len(ci):
             raise ValueError(f"ArgumentError: {len(fl)} rev flags for {len(ci)} sort columns")
-        lim = -1 if limit is None else int(limit)
-        info = np.zeros(4, np.int64)
+        return self._sorted_rows(lambda *out: L.dfdb_sort_indices_n(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), *out), limit, dev_ptr, cap)
+
+    @staticmethod
+    def _rows_arg(rows, dev_ptr, n):
+        """(n, pointer, memkind) of 1-based table rows: a list on the host (the pointer keeps its array alive), or `n` of them in device memory at dev_ptr"""
         if dev_ptr is not None:
-            N.check(L.dfdb_sort_indices_n(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), lim, C.c_void_p(dev_ptr), int(cap), N.MEM_DEVICE, None, info.ctypes.data))
-            return None, tuple(int(x) for x in info)
-        n = self.count() if lim < 0 else min(lim, self.count())
-        out = np.empty(n, np.int64)
-        got = C.c_int64()
-        N.check(L.dfdb_sort_indices_n(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), lim, out.ctypes.data if n else None, n, N.MEM_HOST, C.byref(got), info.ctypes.data))
-        return out[:got.value], tuple(int(x) for x in info)
+            return int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
+        rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
+        return len(rows), (rows.ctypes.data_as(C.c_void_p) if len(rows) else None), N.MEM_HOST
 
     def gather_rows(self, rows=None, dev_ptr: Optional[int] = None, n: Optional[int] = None) -> List[Any]:
         """dfdb_gather_rows: the view's (fixed-width) projection columns at the 1-based table `rows`, in that order — any order, repeats allowed, whatever the
         selection; nullable columns come back masked.  dev_ptr / n: the rows lie in device memory (the device output of sort_indices)"""
-        L = N.load()
-        if dev_ptr is None:
-            rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
-            n, ptr, kind = len(rows), (rows.ctypes.data if len(rows) else None), N.MEM_HOST
-        else:
-            n, ptr, kind = int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
-        ncols = len(self.view.projection)
-        outs = (N.OutCol * max(ncols, 1))()
-        keep = []
-        for i in range(ncols):
-            dt = self.coltype(i)
-            o = outs[i]
-            o.memkind = N.MEM_HOST
-            if (dt & ir.DTYPE_MASK) == ir.STRING:
-                keep.append((dt, None, None))              # (refused by the library, by name)
-                continue
-            arr = np.empty(max(n, 1), ir.numpy_of_dtype(dt))
-            miss = np.zeros(max(n, 1), np.uint8) if dt & ir.NULLABLE else None
-            keep.append((dt, arr, miss))
-            o.data = arr.ctypes.data
-            if miss is not None:
-                o.missing = miss.ctypes.data
-        N.check(L.dfdb_gather_rows(self._h, ptr, n, kind, outs, ncols))
-        return [np.ma.masked_array(a[:n].copy(), mask=m[:n].astype(bool)) if m is not None else a[:n].copy() for _, a, m in keep]
+        n, ptr, kind = self._rows_arg(rows, dev_ptr, n)
+        return self._columns_out(n, lambda outs, ncols: N.check(N.load().dfdb_gather_rows(self._h, ptr, n, kind, outs, ncols)))
 
     def gather_rows_string_bytes(self, col: int, rows=None, dev_ptr: Optional[int] = None, n: Optional[int] = None) -> int:
         """dfdb_gather_rows_string_bytes: the string bytes projection column `col` needs at the 1-based table `rows` (0 for a fixed-width column)"""
-        if dev_ptr is None:
-            rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
-            n, ptr, kind = len(rows), (rows.ctypes.data if len(rows) else None), N.MEM_HOST
-        else:
-            n, ptr, kind = int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
+        n, ptr, kind = self._rows_arg(rows, dev_ptr, n)
         nb = C.c_int64()
         N.check(N.load().dfdb_gather_rows_string_bytes(self._h, col, ptr, n, kind, C.byref(nb)))
         return nb.value
@@ -899,42 +887,14 @@ class _Query:
         for missing, concatenated bytes) in the order of `rows`, as materialize returns it, its buffer sized by dfdb_gather_rows_string_bytes; a nullable
         fixed-width column comes back masked.  dev_ptr / n: the rows lie in device memory"""
         L = N.load()
-        if dev_ptr is None:
-            rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
-            n, ptr, kind = len(rows), (rows.ctypes.data if len(rows) else None), N.MEM_HOST
-        else:
-            n, ptr, kind = int(n), C.c_void_p(dev_ptr), N.MEM_DEVICE
-        ncols = len(self.view.projection)
-        outs = (N.OutCol * max(ncols, 1))()
-        keep = []
-        for i in range(ncols):
-            dt = self.coltype(i)
-            o = outs[i]
-            o.memkind = N.MEM_HOST
-            if (dt & ir.DTYPE_MASK) == ir.STRING:
-                nb = C.c_int64()
-                N.check(L.dfdb_gather_rows_string_bytes(self._h, i, ptr, n, kind, C.byref(nb)))
-                sizes = np.empty(max(n, 1), np.int32)
-                data = np.empty(max(nb.value, 1), np.uint8)
-                keep.append((dt, sizes, data, None))
-                o.data, o.bytes, o.bytes_cap = sizes.ctypes.data, data.ctypes.data, nb.value
-                continue
-            arr = np.empty(max(n, 1), ir.numpy_of_dtype(dt))
-            miss = np.zeros(max(n, 1), np.uint8) if dt & ir.NULLABLE else None
-            keep.append((dt, arr, None, miss))
-            o.data = arr.ctypes.data
-            if miss is not None:
-                o.missing = miss.ctypes.data
-        N.check(L.dfdb_gather_rows_any(self._h, ptr, n, kind, outs, ncols))
-        res = []
-        for i, (dt, a, b, m) in enumerate(keep):
-            if (dt & ir.DTYPE_MASK) == ir.STRING:
-                res.append((a[:n].copy(), b[:outs[i].nbytes].copy()))
-            elif m is not None:
-                res.append(np.ma.masked_array(a[:n].copy(), mask=m[:n].astype(bool)))
-            else:
-                res.append(a[:n].copy())
-        return res
+        n, ptr, kind = self._rows_arg(rows, dev_ptr, n)
+
+        def string_bytes(i):
+            nb = C.c_int64()
+            N.check(L.dfdb_gather_rows_string_bytes(self._h, i, ptr, n, kind, C.byref(nb)))
+            return nb.value
+
+        return self._columns_out(n, lambda outs, ncols: N.check(L.dfdb_gather_rows_any(self._h, ptr, n, kind, outs, ncols)), string_bytes)
 
 
 class _ChunkQuery(_Query):
