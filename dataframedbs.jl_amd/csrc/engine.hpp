@@ -63,6 +63,13 @@ struct Column {
   DevBuf scan_image;
   int scan_image_state = kImageNone;
   int64_t scan_image_scans = 0;   // single-term scans of this column that could have read an image
+  // the 2-byte coarse copy beside a built image (scan_coarse.hpp; k_image.hip k_scan_coarse_build): (image - min) >> shift per row with the same pad, made right
+  // behind the image when ctx option "scan_coarse" allows and there is room, released with it.  scan_image_min / _max: the bits of the smallest and largest image
+  // value (valid while the image is built); scan_coarse_hist[k]: rows whose coarse value >> 4 is k — what the dense-bucket guard consults
+  DevBuf scan_coarse;
+  uint32_t scan_image_min = 0, scan_image_max = 0;
+  int32_t scan_coarse_shift = 0;
+  std::vector<uint64_t> scan_coarse_hist;
   // dictionary form of a low-cardinality String column (dfdb_table_build_dictionary / ctx option "string_dictionary"; k_dict.hip): one 16-bit code per
   // row beside the flat form, the distinct strings once on the device and on the host (predicates are evaluated on the host copy)
   DevBuf dict_codes, dict_len, dict_off, dict_bytes;

@@ -266,6 +266,115 @@ __global__ __launch_bounds__(kBlock) void k_scan_cmp_narrow(const T* __restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// x OP c over a scan image through its 2-byte coarse copy (scan_coarse.hpp), shift > 0
+// ------------------------------------------------------------------------------------------------
+// k_scan_cmp_narrow<uint16_t>'s trip over the coarse copy — eight 16-byte nontemporal loads per lane before the first is looked at, pieces OR-ed across the 8
+// lanes of a word, one ds_bpermute to lane l0 + j, four tiles per trip, one 512-byte bitmap store, the dead-tile skip — with one addition.  A row whose coarse
+// value differs from cc is decided by the same operator on the coarse values (==: false, !=: true); a row whose coarse value EQUALS cc is undecided.  Besides
+// its 8-bit piece a lane keeps the 8-bit mask of its undecided rows (cleared for rows at or beyond nrows and for dead tiles: their vectors are zero-filled and
+// zero equals cc whenever c shares the minimum's bucket); the pieces and masks of the eight loads sit in two 64-bit registers.  Only a lane with an undecided
+// row, and only after all compares of the batch, walks the set bits: one 4-byte load of image[row] each, compared exactly in the image's signedness, the bit of
+// the piece set or cleared.  Nothing else in the trip depends on it.
+template <bool SIGNED, int OP, bool AND_EXISTING>
+__global__ __launch_bounds__(kBlock) void k_scan_cmp_coarse(const uint16_t* __restrict__ coarse, uint16_t cc, const uint32_t* __restrict__ image, uint32_t cbits,
+                                                            uint64_t* __restrict__ bitmap, uint32_t* __restrict__ tile_counts, int64_t nrows, int64_t ntiles, int wt_store) {
+  constexpr int E = 8;                          // rows per lane per load = words per load
+  constexpr int G = 8;                          // lanes per word
+  constexpr int LOADS = 2;                      // loads per tile
+  constexpr int64_t kSpan = 64 * E;             // rows per wave load
+  constexpr int BATCH = 8;                      // loads per trip: one four-tile group
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  using X = typename std::conditional<SIGNED, int32_t, uint32_t>::type;
+  const X c = (X)cbits;
+  const int lane = lane_id();
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  const int64_t ngroups = (ntiles + 3) / 4;
+  const int j16 = lane & 15;
+  const int src_lane = G * (j16 % E);
+  const int my_load = j16 / E;
+  for (int64_t g = wave; g < ngroups; g += nwaves) {
+    uint64_t existing = ~0ull, live = ~0ull;
+    if (AND_EXISTING) {
+      existing = bitmap[g * 64 + lane];
+      live = __ballot(existing != 0);
+    }
+    const int64_t rb = g * 4 * kTile + (int64_t)E * lane;                      // this lane's first row of load 0; load i starts kSpan * i further
+    u32x4 raw[BATCH];
+#pragma unroll
+    for (int i = 0; i < BATCH; i++) {
+      const int64_t r0 = rb + i * kSpan;
+      const bool dead = AND_EXISTING && ((live >> (16 * (i / LOADS))) & 0xffffull) == 0;
+      if (dead || r0 >= nrows) raw[i] = u32x4{0u, 0u, 0u, 0u};                // (a partly valid vector ends < 16 bytes past the copy: inside its 256-byte pad)
+      else raw[i] = __builtin_nontemporal_load((const u32x4*)(coarse + r0));
+    }
+    uint64_t pieces = 0, und = 0;                                              // bit 8 * i + e: row e of load i — its answer so far, and whether it is undecided
+#pragma unroll
+    for (int i = 0; i < BATCH; i++) {
+      const int64_t r0 = rb + i * kSpan;
+      const bool dead = AND_EXISTING && ((live >> (16 * (i / LOADS))) & 0xffffull) == 0;
+      uint16_t v[E];
+      __builtin_memcpy(v, &raw[i], 16);
+      uint32_t piece = 0, u = 0;
+#pragma unroll
+      for (int e = 0; e < E; e++) { piece |= (cmp_op<OP, uint16_t>(v[e], cc) ? 1u : 0u) << e; u |= (v[e] == cc ? 1u : 0u) << e; }
+      const int64_t left = nrows - r0;                                         // rows of this lane's vector that exist
+      const uint32_t valid = dead || left <= 0 ? 0u : (left >= E ? 0xffu : (1u << left) - 1u);
+      pieces |= (uint64_t)(piece & valid) << (8 * i);
+      und |= (uint64_t)(u & valid) << (8 * i);
+    }
+    while (und != 0ull) {                                                      // (divergent: the lanes without an undecided row wait at the shuffles below)
+      const int b = __builtin_ctzll(und);
+      und &= und - 1ull;
+      const X x = (X)image[rb + (int64_t)(b >> 3) * kSpan + (b & 7)];          // (a row below nrows: `valid` saw to that)
+      pieces = (pieces & ~(1ull << b)) | ((uint64_t)(cmp_op<OP, X>(x, c) ? 1u : 0u) << b);
+    }
+    uint64_t myword = 0;
+#pragma unroll
+    for (int i = 0; i < BATCH; i++) {
+      uint64_t w = ((pieces >> (8 * i)) & 0xffull) << (E * (lane % G));
+#pragma unroll
+      for (int d = G / 2; d >= 1; d >>= 1) w |= __shfl_xor(w, d, 64);
+      const uint64_t t = __shfl(w, src_lane, 64);
+      if (my_load == i % LOADS && (lane >> 4) == i / LOADS) myword = t;
+    }
+    const int64_t t0 = g * 4;
+    if (AND_EXISTING) myword &= existing;
+    uint32_t cnt = (uint32_t)__popcll(myword);
+#pragma unroll
+    for (int d = 8; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if (wt_store) __hip_atomic_store(&bitmap[g * 64 + lane], myword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else bitmap[g * 64 + lane] = myword;
+    if ((lane & 15) == 0 && t0 + (lane >> 4) < ntiles) tile_counts[t0 + (lane >> 4)] = cnt;
+  }
+}
+
+template <bool SIGNED, int OP>
+static void launch_coarse_t(hipStream_t s, const void* coarse, const void* image, uint16_t cc, uint32_t c, uint64_t* bitmap, uint32_t* tc, int64_t nrows, bool ae, bool wt) {
+  const int64_t ntiles = (nrows + kTile - 1) / kTile;
+  if (ntiles == 0) return;
+  const int grid = grid_for_tiles((ntiles + 3) / 4);
+  if (ae) hipLaunchKernelGGL((k_scan_cmp_coarse<SIGNED, OP, true>), dim3(grid), dim3(kBlock), 0, s, (const uint16_t*)coarse, cc, (const uint32_t*)image, c, bitmap, tc, nrows, ntiles, wt ? 1 : 0);
+  else hipLaunchKernelGGL((k_scan_cmp_coarse<SIGNED, OP, false>), dim3(grid), dim3(kBlock), 0, s, (const uint16_t*)coarse, cc, (const uint32_t*)image, c, bitmap, tc, nrows, ntiles, wt ? 1 : 0);
+}
+template <bool SIGNED>
+static void launch_coarse_op(hipStream_t s, const void* coarse, const void* image, int op, uint16_t cc, uint32_t c, uint64_t* bitmap, uint32_t* tc, int64_t nrows, bool ae, bool wt) {
+  switch (op) {
+    case CMP_EQ: launch_coarse_t<SIGNED, CMP_EQ>(s, coarse, image, cc, c, bitmap, tc, nrows, ae, wt); break;
+    case CMP_NE: launch_coarse_t<SIGNED, CMP_NE>(s, coarse, image, cc, c, bitmap, tc, nrows, ae, wt); break;
+    case CMP_LT: launch_coarse_t<SIGNED, CMP_LT>(s, coarse, image, cc, c, bitmap, tc, nrows, ae, wt); break;
+    case CMP_LE: launch_coarse_t<SIGNED, CMP_LE>(s, coarse, image, cc, c, bitmap, tc, nrows, ae, wt); break;
+    case CMP_GT: launch_coarse_t<SIGNED, CMP_GT>(s, coarse, image, cc, c, bitmap, tc, nrows, ae, wt); break;
+    default:     launch_coarse_t<SIGNED, CMP_GE>(s, coarse, image, cc, c, bitmap, tc, nrows, ae, wt); break;
+  }
+}
+void launch_scan_cmp_coarse(hipStream_t s, const void* coarse, const void* image, bool is_signed, int op, uint16_t cc, uint32_t c, uint64_t* bitmap, uint32_t* tile_counts,
+                            int64_t nrows, bool and_existing, bool wt_store) {
+  if (is_signed) launch_coarse_op<true>(s, coarse, image, op, cc, c, bitmap, tile_counts, nrows, and_existing, wt_store);
+  else launch_coarse_op<false>(s, coarse, image, op, cc, c, bitmap, tile_counts, nrows, and_existing, wt_store);
+}
+
 template <typename T, int OP>
 static void launch_cmp_t(hipStream_t s, const void* col, uint64_t cbits, uint64_t* bitmap, uint32_t* tc, int64_t nrows, bool and_existing, bool nt, void* cap, int wt_store) {
   const T c = from_bits<T>(cbits);

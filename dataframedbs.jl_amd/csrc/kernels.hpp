@@ -57,8 +57,16 @@ void launch_scan_cmp(hipStream_t s, const ScanTerm& term, uint64_t* bitmap, uint
 // K1's read stream alone (k_read_probe): an 8-byte column of nrows rows, nothing written (sink: one device word that is never stored to)
 void launch_read_probe(hipStream_t s, const void* col, int64_t nrows, uint64_t* sink);
 // the 4-byte scan image of an Int64 (is_signed) / UInt64 column (k_image.hip; scan_image.hpp): image[i] = the low half of col[i]; *misfit (a device word the caller
-// zeroed) is raised when some value is not its truncation extended back.  col and image are 16-byte aligned and carry the columns' 256-byte pad
+// zeroed) is raised when some value is not its truncation extended back.  col and image are 16-byte aligned and carry the columns' 256-byte pad.
+// misfit[1] (zeroed) and misfit[2] (all ones) receive the largest and the smallest image value as unsigned words of the same order (signed: x ^ 0x80000000)
 void launch_scan_image_build(hipStream_t s, const void* col, bool is_signed, void* image, int64_t nrows, uint32_t* misfit);
+// the 2-byte coarse copy of a scan image (k_image.hip; scan_coarse.hpp): coarse[i] = (image[i] - vmin) >> shift, rows past nrows of the last 8 written as zero;
+// hist: 4096 zeroed 64-bit device words, hist[k] += rows with coarse >> 4 == k.  image and coarse are 16-byte aligned and carry the 256-byte pad
+void launch_scan_coarse_build(hipStream_t s, const void* image, void* coarse, int64_t nrows, uint32_t vmin, int shift, uint64_t* hist);
+// `x OP c` over a scan image through its coarse copy, shift > 0 (k_scan.hip k_scan_cmp_coarse): a row whose coarse value differs from cc is decided by the two,
+// the others are compared exactly as image[row] OP c in the image's signedness.  Same outputs as launch_scan_cmp over the image
+void launch_scan_cmp_coarse(hipStream_t s, const void* coarse, const void* image, bool is_signed, int op, uint16_t cc, uint32_t c, uint64_t* bitmap, uint32_t* tile_counts,
+                            int64_t nrows, bool and_existing, bool wt_store);
 // extra = 1 (capture): the LAST term's 8-byte column at the finally selected rows, compacted per tile at extra_out[tile*1024 + rank];
 // extra = 2 (sum): one partial sum of that column per 1024-row tile in extra_out[tile] (double, or wrapping 64-bit integer).  AND only.
 // extra = 5 (capture two): the last term's column like extra = 1, and the 8-byte column of the term before it into extra_out2, same layout.

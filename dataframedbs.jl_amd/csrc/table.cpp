@@ -645,8 +645,10 @@ static void transient_decode_checked(dfdb_table* t, Column& c) {
 void drop_scan_image(dfdb_ctx* ctx, Column& c) {
   if (c.scan_image.p) {
     (void)hipStreamSynchronize(ctx->stream);                  // a scan that reads it may still be in flight
-    ctx->scan_image_bytes -= (int64_t)c.scan_image.bytes;
+    ctx->scan_image_bytes -= (int64_t)c.scan_image.bytes + (int64_t)c.scan_coarse.bytes;
     c.scan_image.release();
+    c.scan_coarse.release();                                  // (exists only beside a built image)
+    c.scan_coarse_hist.clear();
   }
   c.scan_image_state = Column::kImageNone; c.scan_image_scans = 0;
 }
@@ -654,7 +656,7 @@ void table_resident_bytes(dfdb_table* t, int32_t ordinal, int64_t* decoded, int6
   int64_t d = 0, k = 0;
   auto one = [&](const Column& c) {
     if (!c.transient) d += (int64_t)c.data.bytes;
-    d += (int64_t)c.scan_image.bytes;
+    d += (int64_t)c.scan_image.bytes + (int64_t)c.scan_coarse.bytes;
     d += (int64_t)c.bytes.bytes + (int64_t)c.tile_off.bytes + (int64_t)c.missing.bytes + (int64_t)c.dict_codes.bytes + (int64_t)c.dict_bytes.bytes;
     k += (int64_t)c.comp.bytes + (int64_t)c.comp_blocks.bytes + (int64_t)c.comp_status.bytes + (int64_t)c.comp_index.bytes;
   };

@@ -190,7 +190,12 @@ int32_t dfdb_ctx_device_info(dfdb_ctx* ctx, dfdb_device_info* out);
  * counted under `decoded` by dfdb_table_resident_bytes and against "hbm_budget_mb") if every value fits; such scans read the copy from then on whenever their constant
  * fits too: half the bytes, the same answers.  Option scan_image = 0 turns it off (1 = default, 2 = build at the first scan).  The copy goes wherever the column's
  * contents go (unload, reload, compress).  dfdb_ctx_profile_get: launches under "scan_image" (not "scan_cmp"), the one-time build under "scan_image.build", and
- * "scan_image_bytes" reads the HBM the context's images hold right now. */
+ * "scan_image_bytes" reads the HBM the context's images hold right now.
+ * Beside the 4-byte copy the column gets a 2-byte COARSE copy ((value - min) >> shift, 16 significant bits; KNOBS.md "scan_coarse", 0 = off), built right behind it
+ * under "scan_image.coarse_build": up to 6 bytes per row sit beside the column, all counted as above.  A scan whose constant lies inside the column's [min, max] reads
+ * the 2-byte copy and settles the few rows it leaves undecided from the 4-byte one — still one launch under "scan_image", with one of the notes
+ * "scan_image.coarse" (the coarse kernel), "scan_image.coarse_exact" (max - min < 65536: the 2-byte values are exact, nothing is refined) or
+ * "scan_image.coarse_dense" (too many rows share the constant's bucket: the 4-byte copy was scanned instead).  The answers never differ. */
 int32_t dfdb_ctx_set_option(dfdb_ctx* ctx, const char* key, int64_t value);
 /* HIP-event timing on the engine's own stream (bench.py's roofline leg) */
 int32_t dfdb_ctx_timer_start(dfdb_ctx* ctx);
