@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "expr.hpp"
 #include "kernels.hpp"
+#include "scan_image.hpp"
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -20,6 +21,23 @@ struct BlockIndex {
   std::vector<BlockLoc> v;                     // guarded by mu: readers copy the slice they need
   int64_t next_pos = -1;                       // where the next header lies (-1: not started)
   bool complete = false;
+};
+
+// The copies of an Int64 / UInt64 column that lone `col OP const` scans read instead of Column::data (scan_image.cpp builds, routes and drops them; scan_route.hpp is
+// the rule; k_image.hip the build kernels).  image: the column truncated to 4 bytes per row in row order with the same 256-byte pad, for a column whose values all
+// fit 32 bits; made at the column's second such scan (ctx option "scan_image"), read by those scans from then on: half the bytes.  Holds exactly while `data` holds
+// the contents it was made from — whoever releases, refills or re-decodes `data` calls drop_scan_image; a swap of `data` for another allocation with the same contents
+// (placement calibration) keeps it.  Never made for a nullable column, one that keeps LZ4 blocks (comp / comp_only / transient), or a stream slot's chunk.  coarse:
+// (image - min) >> shift in 2 bytes per row, same pad (scan_coarse.hpp), made right behind the image when ctx option "scan_coarse" allows and there is room.
+struct ScanCopies {
+  DevBuf image, coarse;
+  int state = kImageNone;            // scan_image.hpp
+  int64_t scans = 0;                 // single-term scans of this column that could have read an image
+  uint32_t min = 0, max = 0;         // the bits of the smallest and largest image value (state == kImageBuilt)
+  int32_t shift = 0;                 // the coarse copy's
+  std::vector<uint64_t> hist;        // [k]: rows whose coarse value >> 4 is k — what the dense-bucket guard consults (kCoarseHistBins words beside a coarse copy)
+  int64_t bytes() const { return (int64_t)image.bytes + (int64_t)coarse.bytes; }   // HBM held: counted under `decoded`, ctx->scan_image_bytes and "hbm_budget_mb"
+  void clear() { image.release(); coarse.release(); state = kImageNone; scans = 0; min = max = 0; shift = 0; hist.clear(); }
 };
 
 // one column of a table, decoded and resident in HBM as ONE contiguous array over all resident blocks
@@ -54,22 +72,7 @@ struct Column {
   DevBuf mask_pref;
   bool mask_calibrated = false, mask_lent = false;
   float mask_ms_best = 0, mask_ms_worst = 0;   // per scanned sample, for dfdb_ctx_profile / the bench's JSON
-  // scan image (query.cpp: scan_image_for; scan_image.hpp; k_image.hip): an Int64 / UInt64 column whose values all fit 32 bits, truncated to 4 bytes per row in
-  // row order with the same 256-byte pad.  Made at the column's second single-term `col OP const` scan (ctx option "scan_image"), read by those scans instead of
-  // `data` from then on: half the bytes.  Holds exactly while `data` holds the contents it was made from — whoever releases, refills or re-decodes `data` calls
-  // drop_scan_image; a swap of `data` for another allocation with the same contents (placement calibration) keeps it.  Never made for a nullable column, one that
-  // keeps LZ4 blocks (comp / comp_only / transient), or a stream slot's chunk.
-  enum : int { kImageNone = 0, kImageBuilt = 1, kImageMisfit = 2 /* some value needs more than 32 bits: never tried again */, kImageNoRoom = 3 /* did not fit the budget */ };
-  DevBuf scan_image;
-  int scan_image_state = kImageNone;
-  int64_t scan_image_scans = 0;   // single-term scans of this column that could have read an image
-  // the 2-byte coarse copy beside a built image (scan_coarse.hpp; k_image.hip k_scan_coarse_build): (image - min) >> shift per row with the same pad, made right
-  // behind the image when ctx option "scan_coarse" allows and there is room, released with it.  scan_image_min / _max: the bits of the smallest and largest image
-  // value (valid while the image is built); scan_coarse_hist[k]: rows whose coarse value >> 4 is k — what the dense-bucket guard consults
-  DevBuf scan_coarse;
-  uint32_t scan_image_min = 0, scan_image_max = 0;
-  int32_t scan_coarse_shift = 0;
-  std::vector<uint64_t> scan_coarse_hist;
+  ScanCopies scan;              // its 4-byte scan image and the 2-byte coarse copy beside it (above)
   // dictionary form of a low-cardinality String column (dfdb_table_build_dictionary / ctx option "string_dictionary"; k_dict.hip): one 16-bit code per
   // row beside the flat form, the distinct strings once on the device and on the host (predicates are evaluated on the host copy)
   DevBuf dict_codes, dict_len, dict_off, dict_bytes;
@@ -294,9 +297,17 @@ void table_drop_transient(dfdb_table* t);
 struct TransientScope { dfdb_table* t; explicit TransientScope(dfdb_table* t_) : t(t_) {} ~TransientScope() { if (t) table_drop_transient(t); } };
 uint8_t* ctx_hist_scratch(dfdb_ctx* ctx, int* waves);       // the history rings of K7's HIST forms (one buffer per context, made on first use)
 void table_resident_bytes(dfdb_table* t, int32_t ordinal, int64_t* decoded, int64_t* compressed);
-// table.cpp: the column's scan image goes (and may be built again: state none, scans counted from 0).  Called wherever Column::data is released or gets new
+// table.cpp: what `t` may still take into HBM — ctx option "hbm_budget_mb" less what the table holds (INT64_MAX: no bound of its own), and 80 % of what the device
+// has free right now.  Returns hipMemGetInfo's status: what a failure means is the caller's business
+struct HbmRoom { int64_t budget = 0, free_now = 0; };
+hipError_t table_hbm_room(dfdb_table* t, HbmRoom* room);
+// scan_image.cpp: the column's scan copies go (and may be built again: state none, scans counted from 0).  Called wherever Column::data is released or gets new
 // contents; waits for the stream only when there is an image to free
 void drop_scan_image(dfdb_ctx* ctx, Column& c);
+// scan_image.cpp: the lone plain term `tm` over table column `ord` answered from the column's scan copies (profile key "scan_image"); false: the flat scan must
+bool run_image_scan(dfdb_query* q, int ord, const ScanTerm& tm, bool have);
+// the store-mode word of launch_scan_cmp: bit 0 = ctx option "scan_wt_store", bits 1-2 = "scan_narrow"
+inline int scan_store_flags(const dfdb_ctx* ctx) { return (ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0) | (int)((ctx_option(ctx, "scan_narrow", 1) & 3) << 1); }
 int64_t table_decode_status(dfdb_table* t, int32_t ordinal);   // table.cpp: blocks of the last resident decode whose status is not 0 (synchronises)
 int column_lz4_index(dfdb_ctx* ctx, Column& c, bool form_takes_index);   // table.cpp: 0 / 1 (record) / 2 (use) for launch_lz4_decode*
 int32_t ctx_create_like(const dfdb_ctx* like, dfdb_ctx** out);   // c_api.cpp

@@ -549,12 +549,8 @@ int32_t query_prepare(dfdb_query* q) {
   HIP_CHECK(hipSetDevice(ctx->device));
   // two bounds: what the TABLE may hold (ctx option "hbm_budget_mb"; 0 = no bound of its own) and what the device has free right now (the load's staging of
   // one column file and, for the compressed-only form, the context's history rings come out of that too)
-  size_t free_b = 0, total_b = 0;
-  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  const int64_t free_now = (int64_t)((double)free_b * 0.8);
-  int64_t budget = ctx_option(ctx, "hbm_budget_mb", 0) << 20;
-  if (budget > 0) { int64_t d = 0, k = 0; table_resident_bytes(t, -1, &d, &k); budget -= d + k; }
-  else budget = INT64_MAX;
+  HbmRoom room;
+  HIP_CHECK(table_hbm_room(t, &room));
   int64_t dec = 0, comp = 0, comp_max = 0; bool plain = true;
   for (int32_t o : need) {
     dfdb_sizestats st{0, 0, 0};
@@ -566,14 +562,14 @@ int32_t query_prepare(dfdb_query* q) {
   auto unload = [&] { for (int32_t o : need) { Column& c = t->cols[(size_t)o]; if (!c.resident) { drop_scan_image(ctx, c); c.data.release(); c.bytes.release(); c.missing.release(); c.tile_off.release(); c.comp.release(); c.comp_blocks.release(); c.comp_status.release(); c.comp_index.release(); c.comp_nblocks = 0; c.comp_only = false; } } };
   const int64_t kc_old = ctx_option(ctx, "keep_compressed", 0);
   struct Restore { dfdb_ctx* c; int64_t v; ~Restore() { c->options["keep_compressed"] = v; } } restore{ctx, kc_old};
-  if (dec <= budget && dec + comp_max + (64 << 20) <= free_now) {           // decoded arrays (+ the staging of one column file at a time)
+  if (dec <= room.budget && dec + comp_max + (64 << 20) <= room.free_now) {           // decoded arrays (+ the staging of one column file at a time)
     if (kc_old == 2) ctx->options["keep_compressed"] = 0;
     try { table_load(t, need.data(), (int32_t)need.size(), 0, -1, nullptr); return 1; }
     catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); unload(); }
   }
   const int64_t held = comp + comp / 8;                                      // the blocks + their sequence-start index
   int waves = 0; const bool rings = ctx->hist.p != nullptr; (void)waves;
-  if (plain && held <= budget && held + comp_max + (rings ? 0 : (int64_t)lz4_hist_scratch_bytes(lz4_hist_default_waves(ctx->prop.multiProcessorCount))) + (64 << 20) <= free_now) {
+  if (plain && held <= room.budget && held + comp_max + (rings ? 0 : (int64_t)lz4_hist_scratch_bytes(lz4_hist_default_waves(ctx->prop.multiProcessorCount))) + (64 << 20) <= room.free_now) {
     ctx->options["keep_compressed"] = 2;
     try { table_load(t, need.data(), (int32_t)need.size(), 0, -1, nullptr); return 2; }
     catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); unload(); }

@@ -11,8 +11,6 @@
 // dfdb_count reads the scan total, dfdb_materialize reuses the same bitmap.
 #include "engine.hpp"
 #include "ooc.hpp"
-#include "scan_image.hpp"
-#include "scan_coarse.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -571,7 +569,7 @@ static void place_first_batch(dfdb_query* q, PredPlan& plan) {
   const ScanTerms tb0 = plan.term_batches[0].terms;
   const int ord0 = plan.term_batches[0].ords[0];
   const bool nt = true;                 // nontemporal column loads (the A/B knob "scan_nt" went in round 6: plain loads were never faster)
-  const int wt0 = (ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0) | (int)((ctx_option(ctx, "scan_narrow", 1) & 3) << 1);
+  const int wt0 = scan_store_flags(ctx);
   const void* const col_before = t->cols[(size_t)ord0].data.p;
   place_mask(q, ord0, [&](uint64_t* bm, int64_t rows, const void* colp) {
     ScanTerms tbx = tb0;                                          // the calibration may be trying another allocation of the first term's column
@@ -615,130 +613,18 @@ static bool run_decode_on_scan(dfdb_query* q, const ScanTerm& tm, int ord) {
                          LzScan{q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), tm.cbits, fdt, tm.op}, fc.comp_index.as<uint32_t>(), imode);
   return true;
 }
-// ---- the 4-byte scan image (engine.hpp Column::scan_image, scan_image.hpp, k_image.hip)
-// A lone `col OP const` scan is bound by the column's bytes, and an Int64 / UInt64 column whose values all fit 32 bits carries four bytes per row the
-// comparison does not need.  The column does not change between queries — only the constant does — so its truncated copy is made once and every later such scan reads
-// 4 bytes per row through the shipped k_scan_cmp<int32 / uint32>.  ctx option "scan_image": 1 (default) = the column's SECOND such scan builds it (a one-off query never
-// pays: the build moves 12 bytes per row, a scan saves 4), 2 = the first does (tests), 0 = never built, never read; "scan_image_min_rows" (default 2^24): below it a
-// scan is launch-bound and there is nothing to win.  The image is counted like the decoded form against "hbm_budget_mb" and 80 % of the free HBM; a column that does
-// not fit 32 bits, or the budget, is not tried again until it is reloaded.
-// is there room for `bytes` more beside the table's columns: inside "hbm_budget_mb" and 80 % of the free HBM?
-static bool scan_image_room(dfdb_table* t, size_t bytes) {
-  dfdb_ctx* ctx = t->ctx;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-  int64_t budget = ctx_option(ctx, "hbm_budget_mb", 0) << 20;
-  if (budget > 0) { int64_t d = 0, k = 0; table_resident_bytes(t, -1, &d, &k); budget -= d + k; }
-  else budget = INT64_MAX;
-  return (int64_t)bytes <= budget && (int64_t)bytes + (64 << 20) <= (int64_t)((double)free_b * 0.8);
-}
-static_assert(CMP_EQ == kCoarseEq && CMP_NE == kCoarseNe && CMP_LT == kCoarseLt && CMP_LE == kCoarseLe && CMP_GT == kCoarseGt && CMP_GE == kCoarseGe, "scan_coarse.hpp numbers the operators as CmpOp does");
-constexpr size_t kImageFlagHist = 256;                 // ctx->image_flag: the misfit, max and min words, then (from this byte on) the coarse build's 4096 histogram words
-// The 2-byte coarse copy beside the image just built (scan_coarse.hpp): laid out from the image's min and max, written by one more kernel under its own profile key,
-// counted and budgeted like the image.  ctx option "scan_coarse": 1 (default) = made and read, 0 = never made, never read, 2 = read whatever the dense-bucket guard
-// says (tests).  No room for it means no coarse copy: the 4-byte image works as before.
-static void build_scan_coarse(dfdb_table* t, Column& c) {
-  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  if (ctx_option(ctx, "scan_coarse", 1) == 0 || t->nrows <= 0) return;
-  const size_t bytes = (size_t)t->nrows * 2 + 256;
-  if (!scan_image_room(t, bytes)) { prof_note(ctx, "scan_image.coarse_no_room"); return; }
-  try { c.scan_coarse.ensure(bytes); }
-  catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); c.scan_coarse.release(); prof_note(ctx, "scan_image.coarse_no_room"); return; }
-  const CoarsePlan plan = scan_coarse_plan(c.scan_image_min, c.scan_image_max);
-  c.scan_coarse_shift = plan.shift;
-  uint64_t* const hist = (uint64_t*)((uint8_t*)ctx->image_flag.p + kImageFlagHist);
-  HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)kCoarseHistBins * 8, s));
-  { LaunchTimer lt(ctx, "scan_image.coarse_build");
-    launch_scan_coarse_build(s, c.scan_image.p, c.scan_coarse.p, t->nrows, plan.min, plan.shift, hist); }
-  c.scan_coarse_hist.assign((size_t)kCoarseHistBins, 0);
-  HIP_CHECK(hipMemcpyAsync(c.scan_coarse_hist.data(), hist, (size_t)kCoarseHistBins * 8, hipMemcpyDeviceToHost, s));
-  stream_wait(ctx);                                     // one more wait, once per column (the histogram lands in pageable memory)
-  ctx->scan_image_bytes += (int64_t)c.scan_coarse.bytes;
-}
-static void build_scan_image(dfdb_table* t, Column& c) {
-  dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
-  const size_t bytes = (size_t)t->nrows * 4 + 256;
-  c.scan_image_state = Column::kImageNoRoom;
-  if (!scan_image_room(t, bytes)) { prof_note(ctx, "scan_image.no_room"); return; }
-  try { c.scan_image.ensure(bytes); ctx->image_flag.ensure(kImageFlagHist + (size_t)kCoarseHistBins * 8); }
-  catch (const Error& e) { if (e.code != DFDB_ERR_NOMEM) throw; (void)hipGetLastError(); c.scan_image.release(); prof_note(ctx, "scan_image.no_room"); return; }
-  HIP_CHECK(hipMemsetAsync(ctx->image_flag.p, 0, 8, s));                              // the misfit word and the maximum
-  HIP_CHECK(hipMemsetAsync((uint8_t*)ctx->image_flag.p + 8, 0xff, 4, s));             // the minimum
-  const bool is_signed = dt_issigned(c.dtype);
-  { LaunchTimer lt(ctx, "scan_image.build");
-    launch_scan_image_build(s, c.data.p, is_signed, c.scan_image.p, t->nrows, ctx->image_flag.as<uint32_t>()); }
-  // the image is read only after the flag has been: one small copy and one wait, once per column (the min and max words ride in the same copy)
-  HIP_CHECK(hipMemcpyAsync(ctx->pinned_scalar, ctx->image_flag.p, 12, hipMemcpyDeviceToHost, s));
-  stream_wait(ctx);
-  uint32_t words[3];
-  std::memcpy(words, ctx->pinned_scalar, 12);
-  if (words[0] != 0) { c.scan_image.release(); c.scan_image_state = Column::kImageMisfit; prof_note(ctx, "scan_image.misfit"); return; }
-  c.scan_image_state = Column::kImageBuilt;
-  ctx->scan_image_bytes += (int64_t)c.scan_image.bytes;
-  const uint32_t unbias = is_signed ? 0x80000000u : 0u;                               // (the kernel reduces the words in unsigned order: k_image.hip image_ordered)
-  c.scan_image_max = words[1] ^ unbias; c.scan_image_min = words[2] ^ unbias;
-  if (words[2] <= words[1]) build_scan_coarse(t, c);
-}
-// May this lone plain term (no transform, no second comparison, nothing captured) over table column `ord` read the column's image?  Then *out is the term as
-// launch_scan_cmp takes it: the image, its 4-byte dtype, the truncated constant.  Counts the scan and builds the image when this scan is the one that does.  A
-// constant outside the image type's range takes the flat column like everything else — nothing is folded.
-static bool scan_image_term(dfdb_query* q, int ord, const ScanTerm& tm, ScanTerm* out) {
-  dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx;
-  const int64_t opt = ctx_option(ctx, "scan_image", 1);
-  if (opt == 0) return false;
-  Column& c = t->cols[(size_t)ord];
-  const int32_t idt = scan_image_dtype(tm.dtype);
-  if (!idt || dt_nullable(c.dtype) || dt_base(c.dtype) != tm.dtype || tm.col != c.data.p || c.comp.p || c.comp_only || c.transient || t->keep_load_scratch) return false;
-  if (c.scan_image_scans < INT64_MAX) c.scan_image_scans++;
-  if (c.scan_image_state == Column::kImageNone && (opt == 2 || c.scan_image_scans >= 2) && t->nrows >= ctx_option(ctx, "scan_image_min_rows", (int64_t)1 << 24))
-    build_scan_image(t, c);
-  uint64_t cb = 0;
-  if (c.scan_image_state != Column::kImageBuilt || !scan_image_const(tm.dtype, tm.cbits, &cb)) return false;
-  *out = tm; out->col = c.scan_image.p; out->dtype = idt; out->cbits = cb;
-  return true;
-}
-
 // one batch of AND-ed simple terms; ex: the rider (the plan's, on its last batch).  fresh_first: this launch writes the first mask of the query's first stage
 static void run_term_batch(dfdb_query* q, const TermBatch& b, int ex, bool have, bool fresh_first) {
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   const ScanTerms& tb = b.terms;
   const bool one_plain = tb.n == 1 && tb.t[0].op2 < 0 && tb.t[0].pre == 0;
   if (one_plain && ex == EX_NONE && fresh_first && ctx_option(ctx, "decode_on_scan", 0) != 0 && run_decode_on_scan(q, tb.t[0], b.ords[0])) return;
-  ScanTerm img;
-  if (one_plain && ex == EX_NONE && scan_image_term(q, b.ords[0], tb.t[0], &img)) {      // the same launch over the column's 4-byte image, under its own profile key
-    LaunchTimer lt(ctx, "scan_image");
-    const int wt = ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0;
-    // the same answer from the column's 2-byte coarse copy where it has one, the constant lies inside the column's [min, max], and the constant's bucket is not
-    // a dense one (scan_coarse.hpp): still one launch under this key
-    const Column& c = t->cols[(size_t)b.ords[0]];
-    const int64_t coarse_opt = ctx_option(ctx, "scan_coarse", 1);
-    uint16_t cc = 0;
-    if (coarse_opt != 0 && c.scan_coarse.p && scan_coarse_const(img.dtype == DFDB_I32, c.scan_image_min, c.scan_image_max, (uint32_t)img.cbits, &cc)) {
-      if (c.scan_coarse_shift == 0) {                  // the coarse value is the biased exact value: the shipped 2-byte scan, in its 16-byte-per-lane form
-        prof_note(ctx, "scan_image.coarse_exact");
-        ScanTerm ct = img; ct.col = c.scan_coarse.p; ct.dtype = DFDB_U16; ct.cbits = cc;
-        launch_scan_cmp(s, ct, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have, true, nullptr, wt | (2 << 1));
-        return;
-      }
-      if (coarse_opt == 2 || scan_coarse_guard(c.scan_coarse_hist[(size_t)(cc >> 4)], t->nrows)) {
-        prof_note(ctx, "scan_image.coarse");
-        launch_scan_cmp_coarse(s, c.scan_coarse.p, c.scan_image.p, img.dtype == DFDB_I32, img.op, cc, (uint32_t)img.cbits, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(),
-                               t->nrows, have, wt != 0);
-        return;
-      }
-      prof_note(ctx, "scan_image.coarse_dense");       // every row of that bucket would be refined: the 4-byte scan below
-    }
-    prof_note(ctx, img.dtype == DFDB_I32 ? "scan_image.int32" : "scan_image.uint32");
-    launch_scan_cmp(s, img, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have, true, nullptr,
-                    (ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0) | (int)((ctx_option(ctx, "scan_narrow", 1) & 3) << 1));
-    return;
-  }
+  if (one_plain && ex == EX_NONE && run_image_scan(q, b.ords[0], tb.t[0], have)) return;      // answered from the column's scan copies (scan_image.cpp)
   if (one_plain && (ex == EX_NONE || (ex == EX_CAPTURE && !have))) {      // (k_scan_cmp captures over a fresh mask only)
     LaunchTimer lt(ctx, "scan_cmp");
     prof_note(ctx, ctx_option(ctx, "scan_wt_store", 1) ? "scan_cmp.wt_store" : "scan_cmp.plain_store");
     launch_scan_cmp(s, tb.t[0], q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), t->nrows, have,
-                    true, ex == EX_CAPTURE ? q->cap_buf.p : nullptr,
-                    (ctx_option(ctx, "scan_wt_store", 1) ? 1 : 0) | (int)((ctx_option(ctx, "scan_narrow", 1) & 3) << 1));
+                    true, ex == EX_CAPTURE ? q->cap_buf.p : nullptr, scan_store_flags(ctx));
     return;
   }
   LaunchTimer lt(ctx, "scan_terms");

@@ -41,7 +41,7 @@ inline bool scan_coarse_const(bool is_signed, uint32_t min, uint32_t max, uint32
   return true;
 }
 
-// the comparison operators as the scan terms number them (kernels.hpp CmpOp; query.cpp asserts that the two agree)
+// the comparison operators as the scan terms number them (kernels.hpp CmpOp; scan_image.cpp asserts that the two agree)
 enum : int32_t { kCoarseEq = 0, kCoarseNe = 1, kCoarseLt = 2, kCoarseLe = 3, kCoarseGt = 4, kCoarseGe = 5 };
 
 // what the coarse values decide about x OP c: 0 = false, 1 = true, 2 = undecided (compare image[row] OP c exactly)

@@ -11,6 +11,8 @@
 
 namespace dfdb {
 
+// where a column stands with its image (engine.hpp ScanCopies::state; scan_route.hpp: only kImageNone is ever built from, only kImageBuilt is ever read)
+enum : int { kImageNone = 0, kImageBuilt = 1, kImageMisfit = 2 /* some value needs more than 32 bits: never tried again */, kImageNoRoom = 3 /* did not fit the budget */ };
 // the image's dtype for a column of base dtype `dtype` (0: this dtype gets no image)
 inline int32_t scan_image_dtype(int32_t dtype) { return dtype == DFDB_I64 ? (int32_t)DFDB_I32 : dtype == DFDB_U64 ? (int32_t)DFDB_U32 : 0; }
 

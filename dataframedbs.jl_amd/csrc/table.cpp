@@ -642,21 +642,11 @@ static void transient_decode_checked(dfdb_table* t, Column& c) {
     fail(DFDB_ERR_FORMAT, "column %s: %lld of its resident LZ4 blocks do not decode", c.name.c_str(), (long long)bad);
   }
 }
-void drop_scan_image(dfdb_ctx* ctx, Column& c) {
-  if (c.scan_image.p) {
-    (void)hipStreamSynchronize(ctx->stream);                  // a scan that reads it may still be in flight
-    ctx->scan_image_bytes -= (int64_t)c.scan_image.bytes + (int64_t)c.scan_coarse.bytes;
-    c.scan_image.release();
-    c.scan_coarse.release();                                  // (exists only beside a built image)
-    c.scan_coarse_hist.clear();
-  }
-  c.scan_image_state = Column::kImageNone; c.scan_image_scans = 0;
-}
 void table_resident_bytes(dfdb_table* t, int32_t ordinal, int64_t* decoded, int64_t* compressed) {
   int64_t d = 0, k = 0;
   auto one = [&](const Column& c) {
     if (!c.transient) d += (int64_t)c.data.bytes;
-    d += (int64_t)c.scan_image.bytes + (int64_t)c.scan_coarse.bytes;
+    d += c.scan.bytes();
     d += (int64_t)c.bytes.bytes + (int64_t)c.tile_off.bytes + (int64_t)c.missing.bytes + (int64_t)c.dict_codes.bytes + (int64_t)c.dict_bytes.bytes;
     k += (int64_t)c.comp.bytes + (int64_t)c.comp_blocks.bytes + (int64_t)c.comp_status.bytes + (int64_t)c.comp_index.bytes;
   };
@@ -664,6 +654,15 @@ void table_resident_bytes(dfdb_table* t, int32_t ordinal, int64_t* decoded, int6
   else { if ((size_t)ordinal >= t->cols.size()) fail(DFDB_ERR_KEY, "KeyError: column ordinal %d", ordinal); one(t->cols[(size_t)ordinal]); }
   if (decoded) *decoded = d;
   if (compressed) *compressed = k;
+}
+hipError_t table_hbm_room(dfdb_table* t, HbmRoom* room) {
+  size_t free_b = 0, total_b = 0;
+  if (const hipError_t e = hipMemGetInfo(&free_b, &total_b)) return e;
+  room->free_now = (int64_t)((double)free_b * 0.8);
+  room->budget = ctx_option(t->ctx, "hbm_budget_mb", 0) << 20;
+  if (room->budget > 0) { int64_t d = 0, k = 0; table_resident_bytes(t, -1, &d, &k); room->budget -= d + k; }
+  else room->budget = INT64_MAX;
+  return hipSuccess;
 }
 
 // The sequence-start index of a column's resident LZ4 blocks (k_decode.hip INDEX): the first decode that can take it records it, the later ones decode with it.

@@ -1,4 +1,4 @@
-"""The 4-byte scan image of Int64 / UInt64 columns whose values fit 32 bits (csrc/scan_image.hpp, k_image.hip, query.cpp scan_image_term): a lone
+"""The 4-byte scan image of Int64 / UInt64 columns whose values fit 32 bits (csrc/scan_image.hpp, k_image.hip, scan_image.cpp run_image_scan): a lone
 `col OP const` scan reads the truncated copy through the shipped 4-byte scan kernel.  Every answer must be the flat column's bit for bit, and the oracle's;
 the image must exist only for the columns, terms and constants it is valid for, be built when the options say, and go when the column's contents go."""
 import operator

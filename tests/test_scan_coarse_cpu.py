@@ -20,3 +20,17 @@ def test_scan_coarse_rule_edge_grid_under_sanitizers(tmp_path):
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     assert " 0 wrong" in r.stdout, r.stdout
+
+
+def test_scan_route_and_build_trigger_edge_grid_under_sanitizers(tmp_path):
+    """which form a lone `col OP const` scan takes and when it builds the image (csrc/scan_route.hpp, the composition of scan_image.hpp and scan_coarse.hpp)
+    against the rule of DESIGN.md §3 restated in plain 64-bit arithmetic (tests/scan_route_main.cpp): the same stand-alone pattern as above"""
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler found")
+    exe = str(tmp_path / "scan_route")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "scan_route_main.cpp"), "-o", exe])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    assert " 0 wrong" in r.stdout, r.stdout

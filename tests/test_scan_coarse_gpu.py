@@ -1,4 +1,4 @@
-"""The 2-byte coarse copy kept beside the 4-byte scan image (csrc/scan_coarse.hpp, k_image.hip k_scan_coarse_build, k_scan.hip k_scan_cmp_coarse, query.cpp): a
+"""The 2-byte coarse copy kept beside the 4-byte scan image (csrc/scan_coarse.hpp, k_image.hip k_scan_coarse_build, k_scan.hip k_scan_cmp_coarse, scan_route.hpp, scan_image.cpp): a
 lone `col OP const` scan of an Int64 / UInt64 column that has an image reads 2 bytes per row and settles the rows its coarse value leaves undecided from the
 4-byte image.  Every answer must be the flat column's bit for bit, and numpy's, as a fresh mask and behind a range stage; and the profile notes must say WHICH
 form ran — the coarse kernel, the exact 2-byte scan (span below 65536), or the 4-byte scan (constant outside [min, max], or a dense bucket) — so that a
@@ -249,3 +249,74 @@ def test_coarse_copy_lives_and_goes_with_the_image(oracle, dfdb_mod, coarse_ctx,
     finally:
         t.close()
     assert image_bytes(ctx) == before
+
+
+def test_no_room_for_the_image_or_for_the_coarse_copy_is_noted_and_the_scan_still_answers(dfdb_mod, coarse_ctx):
+    """(e) ctx option hbm_budget_mb (whole megabytes) leaves room beside the loaded column (a) for less than the image: one scan_image.no_room, nothing built or
+    held, the flat scan_cmp answers, and the column is not tried again; (b) for the image but not the coarse copy behind it: one scan_image.coarse_no_room, the
+    scan runs under scan_image with none of the coarse notes and 4 to 6 bytes per row are held.  The row count is taken from what the loaded table reports as
+    resident: the first candidate for which a whole number of megabytes falls into both windows (image = 4 B/row + 256, coarse copy = 2 B/row + 256)."""
+    from dfdb import ir
+    ctx = coarse_ctx
+    keys = KEYS + ("scan_image.no_room", "scan_image.coarse_no_room")
+    mb = 1 << 20
+
+    def whole_mb(held, lo, hi):
+        """the budget in MB that leaves at least lo and fewer than hi bytes beside `held` (None: no whole number of megabytes does)"""
+        b = -(-(held + lo) // mb)
+        return b if b * mb - held < hi else None
+
+    def scan(dv):
+        ctx.profile(True)
+        q = dv._query()
+        q.reset()
+        got = (q.count(), q.bitmap(), q.indices())
+        prof = {k: ctx.profile_get(k)[0] for k in keys}
+        ctx.profile(False)
+        return got, prof
+
+    before = image_bytes(ctx)
+    tried = []
+    for n in range(300_000, 360_000, 10_000):
+        x = spread_column(n, np.random.default_rng(n))
+        t = dfdb_mod.DFTable.from_columns({"x": x}, block_size=65536)
+        try:
+            held = sum(t.resident_bytes().values())
+            image, coarse = 4 * n + 256, 2 * n + 256
+            budget_a, budget_b = whole_mb(held, 0, image), whole_mb(held, image, image + coarse)
+            tried.append((n, held, budget_a, budget_b))
+            if budget_a is None or budget_b is None:
+                continue
+            dv = view(dfdb_mod, t, [("pred", ir.col(0) >= K16)])
+            want = numpy_answer(x, operator.ge, K16, None)
+            try:
+                ctx.set_option("hbm_budget_mb", budget_a)
+                got, prof = scan(dv)
+                assert prof["scan_image.no_room"] == 1 and prof["scan_image.coarse_no_room"] == 0, prof
+                assert prof["scan_image"] == 0 and prof["scan_image.build"] == 0 and prof["scan_image.coarse_build"] == 0 and prof["scan_cmp"] == 1, prof
+                assert image_bytes(ctx) == before and same(got, want)
+                got, prof = scan(dv)                       # refused once: not tried again while the column stays as it is
+                assert prof["scan_image.no_room"] == 0 and prof["scan_image"] == 0 and prof["scan_cmp"] == 1 and same(got, want), prof
+            finally:
+                ctx.set_option("hbm_budget_mb", 0)
+        finally:
+            t.close()
+        assert image_bytes(ctx) == before
+        t = dfdb_mod.DFTable.from_columns({"x": x}, block_size=65536)
+        try:
+            assert sum(t.resident_bytes().values()) == held
+            dv = view(dfdb_mod, t, [("pred", ir.col(0) >= K16)])
+            try:
+                ctx.set_option("hbm_budget_mb", budget_b)
+                got, prof = scan(dv)
+                assert prof["scan_image.coarse_no_room"] == 1 and prof["scan_image.no_room"] == 0, prof
+                assert prof["scan_image.build"] == 1 and prof["scan_image.coarse_build"] == 0 and prof["scan_image"] == 1 and prof["scan_cmp"] == 0, prof
+                assert all(prof[key] == 0 for key in FORMS["image"]), prof
+                assert n * 4 <= image_bytes(ctx) - before < n * 6 and same(got, want)
+            finally:
+                ctx.set_option("hbm_budget_mb", 0)
+        finally:
+            t.close()
+        assert image_bytes(ctx) == before
+        return
+    pytest.fail(f"no row count with a whole-megabyte budget for both cases: {tried}")
