@@ -525,7 +525,11 @@ int32_t dfdb_sort_indices(dfdb_query* q, int32_t proj_col, int32_t flags, int64_
 }
 int32_t dfdb_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
                             int64_t* n, int64_t* info) {
-  return guard([&] { NEEDQT(q); query_sort_indices_n(q, proj_cols, flags, nkeys, limit, out, cap, memkind, n, info); });
+  return guard([&] { NEEDQT(q); query_sort_indices_n(q, proj_cols, flags, nkeys, limit, out, cap, memkind, n, info, false); });
+}
+int32_t dfdb_sort_indices_any(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
+                              int64_t* n, int64_t* info) {
+  return guard([&] { NEEDQT(q); query_sort_indices_n(q, proj_cols, flags, nkeys, limit, out, cap, memkind, n, info, true); });
 }
 int32_t dfdb_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
   return guard([&] { NEEDQT(q); if (n > 0) NEED(rows); if (ncols > 0) NEED(outs); query_gather_rows(q, rows, n, rows_memkind, outs, ncols, false); });

@@ -246,9 +246,10 @@ void query_aggregate(dfdb_query* q, int32_t op, int32_t i, int64_t* out_i, doubl
 struct SelectRanks { int n; int64_t rank[kSelectMaxRanks]; };
 int select_keys(dfdb_query* q, const Column& col, bool full, bool count, int max_ranks, int64_t cnt[3], const std::function<void(SelectRanks&)>& choose, uint64_t* keys);
 void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts);   // project.cpp over k_select.hip
-// sort.cpp over k_sort.hip: the stable sortperm of the selected rows by projection columns proj_cols[0] (major) .. [nkeys - 1]; one column p: its n = 1 case
+// sort.cpp over k_sort.hip: the stable sortperm of the selected rows by projection columns proj_cols[0] (major) .. [nkeys - 1]; one column p: its n = 1 case.
+// strings: String keys are admitted (dfdb_sort_indices_any) — else refused by name
 void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
-                          int64_t* n, int64_t* info);
+                          int64_t* n, int64_t* info, bool strings);
 void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info);
 // the projection at given rows (strings: String columns are admitted, k_str_rows.hip — else refused), and the string bytes projection column i needs at those rows
 void query_gather_rows(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols, bool strings);

@@ -1,5 +1,5 @@
-// k_sort.hip — K12: stable sortperm of the selected rows by one fixed-width column (by several: one key after another, k_sort_rekey below), and the gather that
-// follows a row list (gfx950).
+// k_sort.hip — K12: stable sortperm of the selected rows by one fixed-width column (by several: one key after another, k_sort_rekey below; by a String column:
+// its 8-byte sub-keys one after another, k_sort_strkey below), and the gather that follows a row list (gfx950).
 //
 // Replaces sortperm(collect(col)) / partialsortperm / sort over Base.iterate(::DFColumn) (src/tables/column.jl:102-126): the reference collects the selected
 // values one element at a time and sorts them on the host.
@@ -30,6 +30,7 @@
 #include "device_utils.hpp"
 #include "value_rules.hpp"
 #include "select_key.hpp"
+#include "str_tile.hpp"
 #include "kernels.hpp"
 #include "launch_dispatch.hpp"
 #include "../../include/dfdb_ir.h"
@@ -246,6 +247,162 @@ void launch_sort_rekey(hipStream_t s, const ColRef& col, const SortRekey& R, boo
     if (count_phase) hipLaunchKernelGGL((k_sort_rekey<DT, 0>), dim3(grid), dim3(kSortBlock), 0, s, (const T*)col.data, col.missing, R);
     else hipLaunchKernelGGL((k_sort_rekey<DT, 1>), dim3(grid), dim3(kSortBlock), 0, s, (const T*)col.data, col.missing, R);
   });
+}
+
+// STRING KEY (k_sort_strkey): the rekey over a flat String column (sizes, one arena, one byte offset per 1024-row tile: k_strings.hip).  isless on Strings
+// compares bytes unsigned and calls the shorter of two that tie the smaller: the lexicographic order of (chunk_0, .., chunk_{m-1}, length), chunk_c = bytes
+// [8c, 8c + 8) read big-endian, zero beyond the string's end.  The host runs those m + 1 sub-keys through the rekey's sequence, `length` first; one launch
+// keys ONE of them (R.chunk; < 0: the length).  The skeleton is the rekey's: one wave per 1024 entries of `order`, 16 coalesced loads of the entries, the 16
+// gathers of their sizes (negative: the row is missing), and — a chunk, write phase — the 16 gathers of row_off[r] and tile_off[r >> 10] and then the 16
+// 8-byte arena loads, each round 16 deep.  An entry whose string ends at or before the chunk issues none of the three and keys 0.  The arena load may look
+// up to 7 bytes past its string: the arenas' padding covers it, as it covers copy_string's tail load.  Same placement arithmetic, same guards, 8 KB of LDS
+// histograms (8 key bytes).  The length's write phase also leaves the largest live length in *R.max_len: a wave maximum, then one vector atomic per wave.
+//   algorithmic bytes / entry: 4 (order) + 4 (size) [+ 4 (row_off) + 8 (arena) for a chunk the string reaches] + 12 written; what it MOVES is a 128-byte
+//   line per gather when the rows are scattered: the size, the in-tile offset and the arena line (tile_off is one line per 1024 rows)
+template <int PHASE>
+__global__ __launch_bounds__(kSortBlock) void k_sort_strkey(StrSide a, const uint32_t* __restrict__ row_off, SortStrKey R) {
+  __shared__ uint32_t hist[PHASE == 1 ? 8 * 256 : 1];
+  if (PHASE == 1) {
+    for (int i = threadIdx.x; i < 8 * 256; i += kSortBlock) hist[i] = 0;
+    __syncthreads();
+  }
+  const int lane = lane_id();
+  const uint64_t below = (1ull << lane) - 1ull;
+  const int64_t wave = (int64_t)blockIdx.x * kSortWaves + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * kSortWaves;
+  const int64_t ntiles = (R.n + 1023) / 1024;
+  const bool by_len = R.chunk < 0;                               // wave-uniform
+  const uint32_t cb = by_len ? 0u : 8u * (uint32_t)R.chunk;      // the chunk's first byte
+  uint32_t lmax = 0;                                             // the longest live string this lane has seen
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    const int64_t e0 = tile * 1024 + lane;
+    uint32_t r[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const int64_t i = e0 + j * 64;
+      r[j] = i < R.n ? __builtin_nontemporal_load(R.order + i) : 0xffffffffu;
+    }
+    int32_t sz[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      sz[j] = 0;
+      if ((int64_t)r[j] < R.nrows) sz[j] = a.sizes[r[j]];
+    }
+    uint32_t pres = 0, miss = 0;                                 // bit j: entry j of this lane is there / is missing in this column
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      if ((int64_t)r[j] < R.nrows) pres |= 1u << j;
+      if (sz[j] < 0) miss |= 1u << j;
+    }
+    const uint32_t livem = pres & ~miss;
+    uint64_t v[PHASE == 1 ? 16 : 1];
+    if (PHASE == 1) {
+      if (by_len) {
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          const uint32_t len = (livem >> j) & 1u ? (uint32_t)sz[j] : 0u;
+          v[j] = len;
+          lmax = len > lmax ? len : lmax;
+        }
+      } else {
+        uint32_t need = 0;                                       // bit j: entry j is live and its string reaches into the chunk
+#pragma unroll
+        for (int j = 0; j < 16; j++) if (((livem >> j) & 1u) && (uint32_t)sz[j] > cb) need |= 1u << j;
+        uint32_t ro[16]; int64_t to[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          ro[j] = 0; to[j] = 0;
+          if ((need >> j) & 1u) { ro[j] = row_off[r[j]]; to[j] = a.tile_off[r[j] >> 10]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          v[j] = 0;
+          if ((need >> j) & 1u) v[j] = load_u64_unaligned(a.bytes + to[j] + (int64_t)ro[j] + (int64_t)cb);      // (inside the row: cb < its length)
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+          const uint32_t rem = (uint32_t)sz[j] - cb;             // the string's bytes from the chunk's first on (used under `need` only: >= 1)
+          uint64_t k = __builtin_bswap64(v[j]);                  // the first byte of the chunk becomes the key's top byte
+          if (rem - 1u < 7u) k &= ~0ull << (8u * (8u - rem));    // 1..7 bytes left: the bytes behind the string's end are not its own
+          v[j] = (need >> j) & 1u ? k : 0ull;
+        }
+      }
+    }
+    uint32_t lrun = 0, mrun = 0;                                 // wave-uniform: live / missing entries of the tile so far
+    uint64_t lbase = 0, mbase = 0;
+    if (PHASE == 1) { lbase = R.live_base ? R.live_base[tile] : (uint64_t)tile * 1024; mbase = R.miss_base ? R.miss_base[tile] : 0ull; }
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const bool live = (livem >> j) & 1u;
+      const uint64_t kmask = __ballot(live), mmask = __ballot((miss >> j) & 1u);
+      if (PHASE == 1) {
+        const uint64_t key = v[j] ^ R.flip;
+        if (live) {
+          const uint64_t pos = lbase + lrun + (uint32_t)__popcll(kmask & below);
+          if (pos < (uint64_t)R.cap) { R.keys[pos] = key; R.rows[pos] = r[j]; }
+        }
+        if ((mmask >> lane) & 1ull) {
+          const uint64_t pos = mbase + mrun + (uint32_t)__popcll(mmask & below);
+          if (pos < (uint64_t)R.miss_cap) R.miss_rows[pos] = r[j];
+        }
+        hist_add_keys<8>(hist, key, live, kmask, lane);
+      }
+      lrun += (uint32_t)__popcll(kmask); mrun += (uint32_t)__popcll(mmask);
+    }
+    if (PHASE == 0 && lane == 0) { R.live_cnt[tile] = lrun; R.miss_cnt[tile] = mrun; }
+  }
+  if (PHASE == 1) {
+    if (by_len && R.max_len) {
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)lmax, d, 64); lmax = o > lmax ? o : lmax; }
+      if (lane == 0 && lmax) atomicMax(R.max_len, lmax);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 8 * 256; i += kSortBlock) { const uint32_t h = hist[i]; if (h) atomicAdd(&R.ghist[i], (unsigned long long)h); }
+  }
+}
+
+void launch_sort_strkey(hipStream_t s, const StrSide& col, const uint32_t* row_off, const SortStrKey& R, bool count_phase) {
+  const int64_t ntiles = (R.n + 1023) / 1024;
+  if (ntiles < 1) return;
+  int grid = (int)((ntiles + kSortWaves - 1) / kSortWaves);
+  if (grid > kSortBuildBlocks) grid = kSortBuildBlocks;
+  if (count_phase) hipLaunchKernelGGL((k_sort_strkey<0>), dim3(grid), dim3(kSortBlock), 0, s, col, row_off, R);
+  else hipLaunchKernelGGL((k_sort_strkey<1>), dim3(grid), dim3(kSortBlock), 0, s, col, row_off, R);
+}
+
+// the selected rows, ascending and 0-based, at live_base[tile] + their rank in the tile: the build's walk and placement, no column and no key
+__global__ __launch_bounds__(kSortBlock) void k_sort_rows(const uint64_t* __restrict__ bitmap, const uint32_t* __restrict__ tile_counts,
+                                                          const uint64_t* __restrict__ live_base, int64_t nrows, uint32_t* __restrict__ order, int64_t cap) {
+  const int lane = lane_id();
+  const uint64_t below = (1ull << lane) - 1ull;
+  const int64_t wave = (int64_t)blockIdx.x * kSortWaves + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * kSortWaves;
+  const int64_t nwords = (nrows + 63) / 64, ntiles = (nwords + 15) / 16;
+  for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
+    if (tile_counts[tile] == 0) continue;                        // wave-uniform: dead tiles do not touch the bitmap
+    const int64_t wi = tile * 16 + lane;
+    const uint64_t myw = (lane < 16 && wi < nwords) ? bitmap[wi] : 0ull;
+    const uint64_t base = live_base[tile];
+    uint32_t run = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const uint64_t ws = __shfl(myw, j, 64);
+      const int64_t row = tile * 1024 + j * 64 + lane;
+      if (((ws >> lane) & 1ull) && row < nrows) {
+        const uint64_t pos = base + run + (uint32_t)__popcll(ws & below);
+        if (pos < (uint64_t)cap) order[pos] = (uint32_t)row;
+      }
+      run += (uint32_t)__popcll(ws);
+    }
+  }
+}
+void launch_sort_rows(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const uint64_t* live_base, int64_t nrows, uint32_t* order, int64_t cap) {
+  const int64_t nwords = (nrows + 63) / 64, ntiles = (nwords + 15) / 16;
+  if (ntiles < 1) return;
+  int grid = (int)((ntiles + kSortWaves - 1) / kSortWaves);
+  if (grid > kSortBuildBlocks) grid = kSortBuildBlocks;
+  hipLaunchKernelGGL(k_sort_rows, dim3(grid), dim3(kSortBlock), 0, s, bitmap, tile_counts, live_base, nrows, order, cap);
 }
 
 // one workgroup per chunk: counts[bin * nchunks + chunk] =the chunk's pairs whose key bits [shift, shift + 8) are `bin`

@@ -253,6 +253,24 @@ struct SortRekey {
   unsigned long long* ghist;
 };
 void launch_sort_rekey(hipStream_t s, const ColRef& col, const SortRekey& R, bool count_phase);
+// The rekey over a flat String column: ONE 8-byte sub-key of it per launch.  A String key orders as the tuple (chunk_0, .., chunk_{m-1}, length) of such
+// sub-keys (isless on Strings: bytes unsigned, the shorter of two that tie is smaller):  chunk >= 0: bytes [8 chunk, 8 chunk + 8) of the row's string read
+// big-endian, zero beyond its end (a row of at most 8 chunk bytes loads nothing from the arena);  chunk < 0: the row's byte length, and the write phase also
+// leaves the largest live length in *max_len (a zeroed word; one vector atomic max per wave).  A row whose size is negative is missing.  row_off: the in-tile
+// byte offset of every row of the column (launch_str_row_offsets).  Positions, phases, guards and ghist (8 key bytes) as SortRekey's
+struct SortStrKey {
+  const uint32_t* order; int64_t n; int64_t nrows;
+  const uint64_t* live_base; const uint64_t* miss_base;
+  uint64_t flip; int32_t chunk;
+  uint64_t* keys; uint32_t* rows; int64_t cap; uint32_t* miss_rows; int64_t miss_cap;
+  uint32_t* live_cnt; uint32_t* miss_cnt;
+  unsigned long long* ghist;
+  uint32_t* max_len;
+};
+void launch_sort_strkey(hipStream_t s, const StrSide& col, const uint32_t* row_off, const SortStrKey& R, bool count_phase);
+// order[live_base[tile] + rank] = the 0-based selected rows, ascending (the build's placement without a key): the order a String key that is the most minor
+// key of a call starts from.  live_base: the selection's own per-tile scan; nothing is written at or beyond cap
+void launch_sort_rows(hipStream_t s, const uint64_t* bitmap, const uint32_t* tile_counts, const uint64_t* live_base, int64_t nrows, uint32_t* order, int64_t cap);
 void sort_geometry(int64_t out[2]);                  // {pairs per chunk of a pass, threads per workgroup}
 int64_t sort_chunks(int64_t npairs);
 // one pass over key bits [shift, shift + 8): counts [256 * sort_chunks(n)] bin-major, their exclusive scan `starts` (launch_scan_counts), the stable scatter

@@ -1,5 +1,6 @@
 // sort.cpp — ordering on the device: dfdb_sort_indices (the stable sortperm of the selected rows by one projection column, with a limit), dfdb_sort_indices_n
-// (the same by several columns, the most minor key first) and dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip;
+// (the same by several columns, the most minor key first), dfdb_sort_indices_any (the same with String keys admitted: a String key is m + 1 eight-byte
+// sub-keys of the same driver) and dfdb_gather_rows (the projection at given rows, in the given order), over the kernels of k_sort.hip;
 // dfdb_gather_rows_any and dfdb_gather_rows_string_bytes (the same gather with String columns admitted), over those of k_str_rows.hip.  ONE sort driver
 // (query_sort_indices_n: a single key is its n = 1 case) and ONE gather driver (query_gather_rows) stand behind them.
 //
@@ -37,12 +38,12 @@ namespace {
 // the sort's device memory: taken from the pool, back to it when the call ends (the stream drained first)
 struct SortScratch {
   dfdb_ctx* ctx;
-  DevBuf keys[2], rows[2], miss_rows, order, tile_cnt, tile_base, scan_scratch, counts, starts, hist, stage;
+  DevBuf keys[2], rows[2], miss_rows, order, tile_cnt, tile_base, scan_scratch, counts, starts, hist, stage, row_off;     // row_off: a String key's in-tile offsets
   explicit SortScratch(dfdb_ctx* c) : ctx(c) {}
   ~SortScratch() {
     (void)hipStreamSynchronize(ctx->stream);
     RecycleScope rs;
-    for (DevBuf* b : {&keys[0], &keys[1], &rows[0], &rows[1], &miss_rows, &order, &tile_cnt, &tile_base, &scan_scratch, &counts, &starts, &hist, &stage}) b->release();
+    for (DevBuf* b : {&keys[0], &keys[1], &rows[0], &rows[1], &miss_rows, &order, &tile_cnt, &tile_base, &scan_scratch, &counts, &starts, &hist, &stage, &row_off}) b->release();
   }
 };
 struct SortPlan { int64_t nlive = 0, nmiss = 0, L = 0; bool cut = false; uint64_t cutkey = 0; };
@@ -125,15 +126,18 @@ static int64_t sort_build_pairs(dfdb_query* q, const Column& col, SortScratch& S
 
 // The passes over the npairs pairs of S.keys[0] / S.rows[0], by the histograms a build left in S.hist: a byte whose histogram has a single non-zero bin
 // orders nothing and its pass is not run.  Returns the half that holds the sorted pairs; *run: the passes run.  pair_cap >= npairs: the pairs the second half
-// is made for (the most any key of the call has)
-static int sort_run_passes(dfdb_ctx* ctx, SortScratch& S, int64_t npairs, int64_t pair_cap, int nbytes, int64_t* run) {
+// is made for (the most any key of the call has).  tail: the word the build left behind its histograms (a String key's longest live length) is read back
+// with them, whatever npairs is
+static int sort_run_passes(dfdb_ctx* ctx, SortScratch& S, int64_t npairs, int64_t pair_cap, int nbytes, int64_t* run, uint64_t* tail = nullptr) {
   hipStream_t s = ctx->stream;
   int cur = 0;
   *run = 0;
-  if (npairs <= 1) return cur;
-  std::vector<uint64_t> gh((size_t)nbytes * 256);
+  if (npairs <= 1 && !tail) return cur;
+  std::vector<uint64_t> gh((size_t)nbytes * 256 + (tail ? 1 : 0));
   HIP_CHECK(hipMemcpyAsync(gh.data(), S.hist.p, gh.size() * 8, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));              // (`gh` is pageable host memory)
+  if (tail) *tail = gh[(size_t)nbytes * 256];
+  if (npairs <= 1) return cur;
   const int64_t nchunks = sort_chunks(npairs), cchunks = sort_chunks(pair_cap);
   for (int b = 0; b < nbytes; b++) {
     int used = 0;
@@ -170,27 +174,31 @@ static void sort_emit_rows(dfdb_table* t, SortScratch& S, const uint32_t* first,
 // from the ORDER the keys behind it left (k_sort_rekey) and sorted by the same stable passes, so rows equal in it keep that order.  After each key its sorted
 // live rows and its missing rows (behind them, REV: before them) are laid into S.order — the next key's input; the last key's two lists are the answer.
 // A single key is the n = 1 case, different in its plan alone: its build keeps no more than the limit needs (plan_sort's top-k cut) and its scratch is sized
-// by what is kept, where several keys sort every selected row and the limit only cuts what comes back
+// by what is kept, where several keys sort every selected row and the limit only cuts what comes back.
+// strings (dfdb_sort_indices_any): a key may be a plain String column.  It IS m + 1 keys of this driver — (chunk_0, .., chunk_{m-1}, length), 8 key bytes each,
+// the length first (k_sort_strkey) — over row_off built once for the key; m is known when the length has been keyed.  A call with a String key takes the
+// several-keys plan whatever nkeys is, and a String key that is the most minor one starts from the selected rows laid ascending into S.order
 void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
-                          int64_t* n, int64_t* info) {
+                          int64_t* n, int64_t* info, bool strings) {
   if (nkeys < 1 || nkeys > DFDB_SORT_MAX_KEYS) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %d sort keys (1 to %d)", nkeys, (int)DFDB_SORT_MAX_KEYS);
   if (!proj_cols || !flags) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no sort %s", proj_cols ? "flags" : "columns");
   for (int32_t j = 0; j < nkeys; j++) check_sort_flags(flags[j]);
   const Column* cols[DFDB_SORT_MAX_KEYS];
-  for (int32_t j = 0; j < nkeys; j++) cols[j] = &ordered_column(q, proj_cols[j], "sorting by");
+  bool any_str = false;
+  for (int32_t j = 0; j < nkeys; j++) { cols[j] = &ordered_column(q, proj_cols[j], "sorting by", strings); any_str = any_str || dt_base(cols[j]->dtype) == DFDB_STRING; }
   dfdb_table* t = q->t; dfdb_ctx* ctx = t->ctx; hipStream_t s = ctx->stream;
   check_sort_rows(t);
   ensure_executed_checked(q);
   const int64_t sel = query_count(q, -1);
   const int64_t total = limit < 0 ? sel : std::min(limit, sel);
   int64_t inf[4] = {sel, 0, 0, 0};
-  for (int32_t j = 0; j < nkeys; j++) inf[3] += select_key_bits(dt_base(cols[j]->dtype), false) / 8;
+  for (int32_t j = 0; j < nkeys; j++) inf[3] += dt_base(cols[j]->dtype) == DFDB_STRING ? 8 : select_key_bits(dt_base(cols[j]->dtype), false) / 8;   // (a String key: its length; its chunks when they are known)
   if (n) *n = total;
   const int64_t m = std::min(total, std::max<int64_t>(cap, 0));
   if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
   // nothing to do: one key with nothing to return (limit = 0 too: the cut would keep no pair); several keys sort whatever the limit is and report that sort
   // in info, so only an empty selection ends them here
-  const bool one = nkeys == 1;
+  const bool one = nkeys == 1 && !any_str;
   if (one ? total == 0 : sel == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
 
   SortScratch S(ctx);
@@ -198,9 +206,65 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
   const int64_t otiles = ceil_div(sel, kTileRows);
   const uint32_t *first = nullptr, *second = nullptr;      // the key's two lists in output order, first_len rows in the first
   int64_t first_len = 0;
+  // lay the key behind into the order the next one starts from
+  auto lay_order = [&] {
+    uint32_t* order = S.order.as<uint32_t>();
+    LaunchTimer lt(ctx, "sort_order");
+    if (first_len > 0) HIP_CHECK(hipMemcpyAsync(order, first, (size_t)first_len * 4, hipMemcpyDeviceToDevice, s));
+    if (sel > first_len) HIP_CHECK(hipMemcpyAsync(order + first_len, second, (size_t)(sel - first_len) * 4, hipMemcpyDeviceToDevice, s));
+    return order;
+  };
+  // the sorted pairs of half `cur` and the missing rows are the key's two lists
+  auto key_done = [&](int cur, bool rev, int64_t npairs, int64_t nmiss, int64_t run) {
+    inf[1] += npairs; inf[2] += run; inf[3] -= run;
+    const uint32_t* live_rows = S.rows[cur].as<uint32_t>();
+    first = rev ? S.miss_rows.as<uint32_t>() : live_rows; second = rev ? live_rows : S.miss_rows.as<uint32_t>();
+    first_len = rev ? nmiss : npairs;
+  };
   for (int32_t j = nkeys - 1; j >= 0; j--) {
     const Column& col = *cols[j];
     const bool rev = (flags[j] & DFDB_SORT_REV) != 0;
+    if (dt_base(col.dtype) == DFDB_STRING) {
+      S.row_off.ensure((size_t)std::max<int64_t>(t->nrows, 1) * 4);
+      { LaunchTimer lt(ctx, "str_row_offsets"); launch_str_row_offsets(s, col.data.as<int32_t>(), S.row_off.as<uint32_t>(), t->nrows); }
+      S.hist.ensure((size_t)(kSelectMaxRanks * 256 + 8) * 8);
+      uint64_t* max_len = S.hist.as<uint64_t>() + 8 * 256;      // the word behind the eight histograms: read back with them
+      int64_t nchunks = 0;                                        // m: known after the length
+      for (int64_t k = 0; k <= nchunks; k++) {                  // the length, then chunk m - 1 .. chunk 0: the most minor sub-key first
+        const int64_t c = k == 0 ? -1 : nchunks - k;
+        uint32_t* order = S.order.as<uint32_t>();
+        if (j == nkeys - 1 && c == -1) {                          // no order yet: the selected rows, ascending
+          LaunchTimer lt(ctx, "sort_rows");
+          launch_sort_rows(s, q->bitmap.as<uint64_t>(), q->tile_counts.as<uint32_t>(), q->prefix.as<uint64_t>(), t->nrows, order, sel);
+        } else order = lay_order();
+        SortStrKey R{};
+        R.order = order; R.n = sel; R.nrows = t->nrows; R.flip = flip_of(64, rev); R.chunk = (int32_t)c;
+        int64_t npairs = sel, nmiss = 0;
+        if (dt_nullable(col.dtype)) {                             // count the live and the missing entries per 1024 entries of the order, scan both
+          const SortCounts cn = sort_count_phase(ctx, S, otiles, R, [&] { LaunchTimer lt(ctx, "sort_strkey"); launch_sort_strkey(s, str_side(col), S.row_off.as<uint32_t>(), R, true); });
+          npairs = cn.npairs; nmiss = cn.nmiss;
+          if (npairs + nmiss != sel) fail(DFDB_ERR_DEVICE, "sort: the String key counted %lld live and %lld missing rows of %lld", (long long)npairs, (long long)nmiss, (long long)sel);
+        }
+        R.keys = S.keys[0].as<uint64_t>(); R.rows = S.rows[0].as<uint32_t>(); R.cap = npairs;
+        R.miss_rows = S.miss_rows.as<uint32_t>(); R.miss_cap = nmiss;
+        R.ghist = (unsigned long long*)S.hist.p;
+        R.max_len = c == -1 ? (uint32_t*)max_len : nullptr;
+        HIP_CHECK(hipMemsetAsync(S.hist.p, 0, (size_t)(8 * 256 + 1) * 8, s));
+        { LaunchTimer lt(ctx, c == -1 ? "sort_strkey_len" : "sort_strkey"); launch_sort_strkey(s, str_side(col), S.row_off.as<uint32_t>(), R, false); }   // (the length's launch loads no offset and no arena byte: timed apart)
+        int64_t run = 0;
+        uint64_t longest = 0;
+        const int cur = sort_run_passes(ctx, S, npairs, sel, 8, &run, c == -1 ? &longest : nullptr);
+        key_done(cur, rev, npairs, nmiss, run);
+        if (c == -1) {
+          if (longest > (uint64_t)DFDB_SORT_MAX_STRING_BYTES)
+            fail(DFDB_ERR_UNSUPPORTED, "sorting by the String column %s is not supported: a selected row of it holds %llu bytes, the limit is %d (DFDB_SORT_MAX_STRING_BYTES)",
+                 col.name.c_str(), (unsigned long long)longest, (int)DFDB_SORT_MAX_STRING_BYTES);
+          nchunks = (int64_t)(longest + 7) / 8;
+          inf[3] += 8 * nchunks;
+        }
+      }
+      continue;
+    }
     const int nbits = select_key_bits(dt_base(col.dtype), false), nbytes = nbits / 8;
     int64_t npairs = sel, nmiss = 0;
     if (j == nkeys - 1) {
@@ -208,13 +272,8 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
       if (one) P = plan_sort(q, col, rev, limit, sel);
       npairs = sort_build_pairs(q, col, S, rev, P, one, sel, &nmiss);       // (one key: sized by the pairs kept)
     } else {
-      // lay the key behind into the order this one starts from
-      uint32_t* order = S.order.as<uint32_t>();
-      { LaunchTimer lt(ctx, "sort_order");
-        if (first_len > 0) HIP_CHECK(hipMemcpyAsync(order, first, (size_t)first_len * 4, hipMemcpyDeviceToDevice, s));
-        if (sel > first_len) HIP_CHECK(hipMemcpyAsync(order + first_len, second, (size_t)(sel - first_len) * 4, hipMemcpyDeviceToDevice, s)); }
       SortRekey R{};
-      R.order = order; R.n = sel; R.nrows = t->nrows; R.flip = flip_of(nbits, rev);
+      R.order = lay_order(); R.n = sel; R.nrows = t->nrows; R.flip = flip_of(nbits, rev);
       if (dt_nullable(col.dtype)) {                         // count the live and the missing entries per 1024 entries of the order, scan both
         const SortCounts c = sort_count_phase(ctx, S, otiles, R, [&] { LaunchTimer lt(ctx, "sort_rekey"); launch_sort_rekey(s, col_ref(col), R, true); });
         npairs = c.npairs; nmiss = c.nmiss;
@@ -228,10 +287,7 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
     }
     int64_t run = 0;
     const int cur = sort_run_passes(ctx, S, npairs, one ? npairs : sel, nbytes, &run);
-    inf[1] += npairs; inf[2] += run; inf[3] -= run;
-    const uint32_t* live_rows = S.rows[cur].as<uint32_t>();
-    first = rev ? S.miss_rows.as<uint32_t>() : live_rows; second = rev ? live_rows : S.miss_rows.as<uint32_t>();
-    first_len = rev ? nmiss : npairs;
+    key_done(cur, rev, npairs, nmiss, run);
   }
   // the first m of the two lists (a cut keeps every pair up to the cut key: no fewer than the limit takes of the live rows)
   const int64_t first_n = std::min(m, first_len);
@@ -240,7 +296,7 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
 }
 
 void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
-  query_sort_indices_n(q, &p, &flags, 1, limit, out, cap, memkind, n, info);
+  query_sort_indices_n(q, &p, &flags, 1, limit, out, cap, memkind, n, info, false);
 }
 
 // ---- the projection at given rows: a fixed-width column by one kernel; a String column (k_str_rows.hip) by the offsets of the gathered sizes, then the bytes -------

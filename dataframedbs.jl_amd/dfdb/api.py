@@ -861,6 +861,22 @@ class _Query:
             raise ValueError(f"ArgumentError: {len(fl)} rev flags for {len(ci)} sort columns")
         return self._sorted_rows(lambda *out: L.dfdb_sort_indices_n(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), *out), limit, dev_ptr, cap)
 
+    def sort_indices_any(self, cols, revs=None, limit: Optional[int] = None, dev_ptr: Optional[int] = None, cap: Optional[int] = None):
+        """dfdb_sort_indices_any: sort_indices_n with String keys admitted — any key may be a plain String column (bytes compared unsigned, the shorter of two
+        strings that tie is smaller; missing last, first under rev), of at most SORT_MAX_STRING_BYTES bytes per selected live row.  A String key is m + 1
+        sub-keys of 8 bytes on the device and info's last three entries are summed over keys and sub-keys; with a String key `limit` only cuts what comes
+        back.  With numeric keys only it is sort_indices_n"""
+        L = N.load()
+        ci = np.ascontiguousarray(cols, np.int32).reshape(-1)
+        fl = np.zeros(len(ci), np.int32) if revs is None else np.array([N.SORT_REV if r else 0 for r in revs], np.int32)
+        if len(fl) != len(ci):
+            raise ValueError(f"ArgumentError: {len(fl)} rev flags for {len(ci)} sort columns")
+        return self._sorted_rows(lambda *out: L.dfdb_sort_indices_any(self._h, ci.ctypes.data, fl.ctypes.data, len(ci), *out), limit, dev_ptr, cap)
+
+    def _string_keys(self, cols) -> bool:
+        """whether one of the projection columns `cols` is a String column: the sorts over it go through sort_indices_any"""
+        return any((self.coltype(int(c)) & ir.DTYPE_MASK) == ir.STRING for c in cols)
+
     @staticmethod
     def _rows_arg(rows, dev_ptr, n):
         """(n, pointer, memkind) of 1-based table rows: a list on the host (the pointer keeps its array alive), or `n` of them in device memory at dev_ptr"""
@@ -1257,11 +1273,15 @@ class DFColumn:
     def sortperm(self, rev: bool = False, limit: Optional[int] = None) -> np.ndarray:
         """the 1-based TABLE rows of the selected rows in sorted order (stable; rev reverses the ordering, not the ties; missing last, first under rev),
         the first `limit` of them when given"""
-        return self.view._query().sort_indices(0, rev, limit)[0]
+        q = self.view._query()
+        return (q.sort_indices_any([0], [rev], limit) if q._string_keys([0]) else q.sort_indices(0, rev, limit))[0]
 
     def sort(self, rev: bool = False, limit: Optional[int] = None):
         """sort(collect(col); rev) — the first `limit` values of it when given —, missing values as materialize gives them"""
         q = self.view._query()
+        if q._string_keys([0]):                         # a String column: sorted by its bytes (dfdb_sort_indices_any), gathered through dfdb_gather_rows_any
+            rows, _ = q.sort_indices_any([0], [rev], limit)
+            return _to_user(q.gather_rows_any(rows)[0], _logicals(self.view)[0])
         rows, _ = q.sort_indices(0, rev, limit)
         return _to_user(q.gather_rows(rows)[0], _logicals(self.view)[0])
 
@@ -1335,19 +1355,24 @@ def sortperm_by(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] =
     if isinstance(by, str):
         by = [by]
     cols, revs = _sort_keys(v, by, rev)
-    return v._query().sort_indices_n(cols, revs, limit)[0]
+    q = v._query()
+    return (q.sort_indices_any(cols, revs, limit) if q._string_keys(cols) else q.sort_indices_n(cols, revs, limit))[0]
 
 
 def sort_view(v: Union[DFView, DFTable], by, rev=False, limit: Optional[int] = None):
     """sort!(materialize(v), by; rev) (first(.., limit) when given): the view's projection columns, String columns included, in the order of its column `by`,
-    or of its columns `by` when that is a list of names (the first one major; `rev` a bool or one per column).  The keys are fixed-width columns (sorting BY a
-    String column is refused); every column follows them through dfdb_gather_rows_any"""
+    or of its columns `by` when that is a list of names (the first one major; `rev` a bool or one per column).  A key is a fixed-width column or a plain
+    String column (sorted by its bytes, at most SORT_MAX_STRING_BYTES per selected row: dfdb_sort_indices_any); every column follows the keys through
+    dfdb_gather_rows_any"""
     if isinstance(v, DFTable):
         v = DFView(v)
     import pandas as pd
     q = v._query()
-    if isinstance(by, str):
-        rows, _ = q.sort_indices(list(v.projection.keys()).index(by), rev, limit)
+    names = list(v.projection.keys())
+    if q._string_keys([names.index(b) for b in ([by] if isinstance(by, str) else by)]):
+        rows, _ = q.sort_indices_any(*_sort_keys(v, [by] if isinstance(by, str) else by, rev), limit)
+    elif isinstance(by, str):
+        rows, _ = q.sort_indices(names.index(by), rev, limit)
     else:
         rows, _ = q.sort_indices_n(*_sort_keys(v, by, rev), limit)
     lg = _logicals(v)

@@ -698,8 +698,25 @@ function sorted_length(q, limit::Integer)
     limit < 0 ? n[] : min(limit, n[])
 end
 
-# the sorted table rows of query q's projection column 0 (dfdb_sort_indices): limit < 0 = all of them
+# whether projection column i (0-based) of query q is a String column: its sorts go through dfdb_sort_indices_any
+function string_key(q, i::Integer)
+    dt = Ref{Int32}(0)
+    check(ccall((:dfdb_query_coltype, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), q, i, dt))
+    (dt[] & 0x3f) == 12
+end
+
+# the sorted table rows of query q by its projection columns kidx (0-based, major first) with String keys admitted (dfdb_sort_indices_any)
+function sort_rows_any(q, kidx::Vector{Int32}, flags::Vector{Int32}, limit::Integer)
+    m = sorted_length(q, limit)
+    rows = Vector{Int64}(undef, m); got = Ref{Int64}(0)
+    check(ccall((:dfdb_sort_indices_any, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}),
+                q, kidx, flags, length(kidx), limit < 0 ? -1 : limit, rows, m, 0, got, C_NULL))
+    rows
+end
+
+# the sorted table rows of query q's projection column 0 (dfdb_sort_indices; a String column: dfdb_sort_indices_any): limit < 0 = all of them
 function sort_rows(q, rev::Bool, limit::Integer)
+    string_key(q, 0) && return sort_rows_any(q, Int32[0], Int32[rev ? 1 : 0], limit)
     m = sorted_length(q, limit)
     rows = Vector{Int64}(undef, m); got = Ref{Int64}(0)
     check(ccall((:dfdb_sort_indices, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}),
@@ -712,11 +729,12 @@ end
 
 The 1-based TABLE rows of the selected rows of `c` in the order `sortperm(collect(c); rev)` gives them — the first `limit` of them when limit >= 0
 (`partialsortperm`) —: dfdb_sort_indices, a stable radix sort of {key, row} pairs on the device.  `isless` order (floats -Inf .. -0.0 < 0.0 .. Inf < NaN),
-ties in ascending row order in both directions, `missing` last (first under `rev`).  The reference collects the column through Base.iterate(::DFColumn)
+ties in ascending row order in both directions, `missing` last (first under `rev`).  A String column goes through dfdb_sort_indices_any: bytes compared
+unsigned, the shorter of two strings that tie is smaller, at most 256 bytes per selected row.  The reference collects the column through Base.iterate(::DFColumn)
 (column.jl:102-126) and sorts on the host.  The sharded form, a view that stays on disk and a compressed-only column are `Unsupported`.
 """
 function gpu_sortperm(c::DFColumn{T}; rev::Bool = false, limit::Integer = -1) where {T}
-    Base.nonmissingtype(T) <: SORTABLE || throw(Unsupported("sorting by a column of $(T)"))
+    Base.nonmissingtype(T) <: Union{SORTABLE,String} || throw(Unsupported("sorting by a column of $(T)"))
     sharded() && throw(Unsupported("sorting over a sharded table"))
     with_query(q -> sort_rows(q, rev, limit), c.view)
 end
@@ -726,7 +744,8 @@ end
 
 The 1-based TABLE rows of the selected rows of `v` in the order `sort(df, cols; rev)` gives them: lexicographic by `cols[1]` (major) .. `cols[end]`, `rev` a
 Bool or one Bool per column, every key ordered as `gpu_sortperm(::DFColumn)` orders it, rows equal in every key in ascending row order
-(dfdb_sort_indices_n: the device sorts by the most minor key first and rekeys the order it has for every further key).  1 to 8 fixed-width columns.
+(dfdb_sort_indices_n: the device sorts by the most minor key first and rekeys the order it has for every further key).  1 to 8 fixed-width columns — or
+String columns among them, and then the call is dfdb_sort_indices_any.
 """
 function gpu_sortperm(v::DFView, cols::Vector{Symbol}; rev::Union{Bool,AbstractVector{Bool}} = false, limit::Integer = -1)
     sharded() && throw(Unsupported("sorting over a sharded table"))
@@ -737,6 +756,7 @@ function gpu_sortperm(v::DFView, cols::Vector{Symbol}; rev::Union{Bool,AbstractV
     kidx = Int32.(0:nk-1)
     flags = Int32[r ? 1 : 0 for r in revs]
     with_query(v[:, cols]) do q
+        any(i -> string_key(q, i), kidx) && return sort_rows_any(q, kidx, flags, limit)
         m = sorted_length(q, limit)
         rows = Vector{Int64}(undef, m); got = Ref{Int64}(0)
         check(ccall((:dfdb_sort_indices_n, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Int32, Int64, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Int64}),
@@ -747,6 +767,7 @@ end
 
 "`sort(collect(c); rev)` (its first `limit` values when limit >= 0): the values gathered on the device in the order of gpu_sortperm (dfdb_gather_rows)"
 function gpu_sort(c::DFColumn{T}; rev::Bool = false, limit::Integer = -1) where {T}
+    Base.nonmissingtype(T) === String && return gpu_sort(c.view, collect(keys(c.view.projection)); rev = rev, limit = limit)[!, 1]   # sorted by its bytes, gathered by dfdb_gather_rows_any
     Base.nonmissingtype(T) <: SORTABLE || throw(Unsupported("sorting a column of $(T)"))
     sharded() && throw(Unsupported("sorting over a sharded table"))
     with_query(c.view) do q
@@ -766,7 +787,7 @@ end
 
 `sort!(materialize(v), cols; rev)` (its first `limit` rows when limit >= 0) on the device: the rows of `gpu_sortperm(v, cols; rev, limit)`, then every
 projection column of `v` at those rows through dfdb_gather_rows_any — String columns included, their buffers sized by dfdb_gather_rows_string_bytes and
-finished as `materialize` finishes them.  The keys are fixed-width columns; a computed column of `v` is `Unsupported`.
+finished as `materialize` finishes them.  The keys are fixed-width or String columns; a computed column of `v` is `Unsupported`.
 """
 function gpu_sort(v::DFView, cols::Vector{Symbol}; rev::Union{Bool,AbstractVector{Bool}} = false, limit::Integer = -1)
     rows = gpu_sortperm(v, cols; rev = rev, limit = limit)

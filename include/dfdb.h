@@ -462,6 +462,29 @@ int32_t dfdb_sort_indices(dfdb_query* q, int32_t proj_col, int32_t flags, int64_
 enum { DFDB_SORT_MAX_KEYS = 8 };
 int32_t dfdb_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
                             int64_t* n, int64_t* info);
+/* dfdb_sort_indices_n with String keys admitted (sortperm(collect(col)) / sort(df, [:brand, :price]) over String columns): dfdb_sort_indices_n's contract,
+ * and every key may also be a plain String or Union{String,Missing} column — in any position, more than once, mixed with numeric keys.  A column with a
+ * dictionary is read through its flat form.
+ *   order    a String key orders as isless orders Strings: bytes compared as unsigned values, the shorter of two strings that tie is the smaller, an
+ *            embedded NUL is a byte like any other; descending under that key's DFDB_SORT_REV, ties in ascending row order both ways; rows missing in the key
+ *            (size -1) after its live rows, before them under REV.  On the device a String key IS m + 1 sub-keys of the same driver, each 8 key bytes:
+ *            (chunk_0, .., chunk_{m-1}, length), chunk_c = bytes [8c, 8c + 8) read big-endian and zero beyond the string's end, m = ceil(L / 8) for the
+ *            longest selected live string of L bytes; the length is keyed first, then chunk m-1 .. chunk 0 (k_sort_strkey, csrc/k_sort.hip), over a per-row
+ *            offset array built once per String key per call.
+ *   limit    with a String key in the call `limit` only truncates what is written, whatever nkeys is: every selected row is sorted (no top-k cut for a String
+ *            key yet: DESIGN.md section 10).
+ *   info     [4] (may be NULL): selected rows; pairs keyed, summed over keys AND sub-keys (a String key with m chunks counts its live rows m + 1 times);
+ *            digit passes run, summed the same way; digit passes skipped, summed the same way (a sub-key has 8 key bytes).
+ *   With numeric keys only the answer and info are dfdb_sort_indices_n's.
+ * Refusals: dfdb_sort_indices_n's argument, bounds and flag errors with the same messages; DFDB_ERR_UNSUPPORTED with the existing messages for a computed
+ * column (a coalesce of String columns too), a view that is out of core, a compressed-only column, and a String column one 1024-row tile of which holds 2^22
+ * bytes or more; DFDB_ERR_UNSUPPORTED, naming the column, the length found and the limit, when a selected live string of a key is longer than
+ * DFDB_SORT_MAX_STRING_BYTES — decided when the key's length has been keyed and before any chunk runs; nothing is written to `out` (the cost grows with m;
+ * longer keys are a follow-up).  DFDB_ERR_NOMEM as dfdb_sort_indices_n, with 4 more bytes per table row for the offsets.  Every argument
+ * is checked before the first launch; the query's selection is left as it was found.  dfdb_sort_indices and dfdb_sort_indices_n refuse String keys as before. */
+enum { DFDB_SORT_MAX_STRING_BYTES = 256 };
+int32_t dfdb_sort_indices_any(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
+                              int64_t* n, int64_t* info);
 /* the projection at the 1-based table rows rows[0 .. n), in that order: any order, repeats allowed, independent of the query's selection (with
  * dfdb_sort_indices: sort(collect(col)), sort!(materialize(v), :col)).  `rows` lies in host or device memory (rows_memkind): the device output of
  * dfdb_sort_indices feeds it without leaving the device.  outs[i] (ncols = the view's columns) receives projection column i: data, missing bytes, count = n
