@@ -487,7 +487,7 @@ int32_t dfdb_query_hint_aggregate(dfdb_query* q, int32_t op, int32_t proj_col) {
 int32_t dfdb_query_hint_materialize(dfdb_query* q, int32_t on) {
   return guard([&] { NEEDQ(q); if (q->hint_materialize != (on != 0)) { q->hint_materialize = on != 0; q->executed_stages = -1; q->count = -1; q->prefix_valid = false; } });
 }
-int32_t dfdb_query_reset(dfdb_query* q) { return guard([&] { NEEDQ(q); ooc_reset(q); q->executed_stages = -1; q->count = -1; q->prefix_valid = false; q->gr_state = 0; }); }
+int32_t dfdb_query_reset(dfdb_query* q) { return guard([&] { NEEDQ(q); ooc_reset(q); q->executed_stages = -1; q->count = -1; q->prefix_valid = false; q->gr_state = 0; query_join_drop(q); }); }
 int32_t dfdb_count(dfdb_query* q, int64_t* n) { return guard([&] { NEEDQT(q); NEED(n); *n = query_out_of_core(q) ? ooc_count(q) : query_count(q, -1); }); }
 int32_t dfdb_count_to(dfdb_query* q, int64_t* out, int32_t memkind) {
   return guard([&] {
@@ -540,6 +540,12 @@ int32_t dfdb_gather_rows_string_bytes(dfdb_query* q, int32_t i, const int64_t* r
 int32_t dfdb_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols) {
   return guard([&] { NEEDQT(q); if (n > 0) NEED(rows); if (ncols > 0) NEED(outs); query_gather_rows(q, rows, n, rows_memkind, outs, ncols, true); });
 }
+int32_t dfdb_query_join(dfdb_query* left, int32_t left_col, dfdb_query* right, int32_t right_col, int32_t kind, int64_t* npairs, int64_t* info) {
+  return guard([&] { NEEDQ(left); NEEDQ(right); query_join(left, left_col, right, right_col, kind, npairs, info); });
+}
+int32_t dfdb_query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* right_rows, int64_t cap, int32_t memkind) {
+  return guard([&] { NEEDQ(left); query_join_fetch(left, left_rows, right_rows, cap, memkind); });
+}
 
 
 /* ---- only what the view needs, resident only if it fits (view.jl:183-190, blocksiterator.jl:20-33) ---- */
@@ -554,7 +560,7 @@ int32_t dfdb_table_unload(dfdb_table* t, const int32_t* ordinals, int32_t ncols)
     NEED(t); if (ncols > 0) NEED(ordinals);
     HIP_CHECK(hipSetDevice(t->ctx->device));
     HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-    for (dfdb_query* q : t->queries) { query_return_mask(q); q->executed_stages = -1; q->count = -1; q->prefix_valid = false; q->gr_state = 0; q->arenas.clear(); ooc_reset(q); }
+    for (dfdb_query* q : t->queries) { query_return_mask(q); q->executed_stages = -1; q->count = -1; q->prefix_valid = false; q->gr_state = 0; query_join_drop(q); q->arenas.clear(); ooc_reset(q); }
     std::vector<int32_t> all;
     if (!ordinals) { for (size_t i = 0; i < t->cols.size(); i++) all.push_back((int32_t)i); ordinals = all.data(); ncols = (int32_t)all.size(); }
     for (int32_t k = 0; k < ncols; k++) {

@@ -281,6 +281,29 @@ void launch_sort_emit(hipStream_t s, const uint32_t* rows, int64_t n, int64_t* o
 void launch_gather_rows(hipStream_t s, const int64_t* rows, int64_t n, const void* col, int width, void* out, const uint64_t* missing, uint8_t* mout, int64_t row_base,
                         int64_t nrows, uint32_t* flag);
 
+// ---- K14: the row lists of a join of two selections on one fixed-width key (k_join.hip; the rules: join_rule.hpp) ---------------------------------
+// The probe: order[0 .. nl) holds the selected left rows (0-based, ascending: launch_sort_rows); rkeys[0 .. nr) the right side's select keys, ascending (the
+// sorted pairs of k_sort.hip).  Entry i gets lo[i] = the right keys below its key and cnt[i] = the right keys equal to it; a left row whose key is missing, and
+// every entry of the last 1024-entry group at or beyond nl, gets cnt = 0 (lo and cnt hold groups * 1024 entries).  grp_total[g] = the sum of
+// join_emitted(kind, cnt) over the group's entries below nl; a sum of 2^32 or more raises *flag.  *nmiss (zeroed) += the left rows whose key is missing.
+// steps = join_search_steps(nr)
+struct JoinProbe {
+  const uint32_t* order; int64_t nl; int64_t nrows;
+  const uint64_t* rkeys; uint32_t nr; int32_t steps; int32_t kind;
+  uint32_t* lo; uint32_t* cnt; uint32_t* grp_total;
+  unsigned long long* nmiss; uint32_t* flag;
+};
+void launch_join_probe(hipStream_t s, const ColRef& col, const JoinProbe& P);
+// The expand: the pairs of entry i start at out_base[i / 1024] (launch_scan_counts of grp_total) + the pairs of the group's entries before it.  Pair k of an
+// entry: left_rows = lbase + order[i] + 1, right_rows = cnt ? rbase + rrows[lo + k] + 1 : 0 (rrows: the sorted pairs' rows; right_rows null: not written).
+// Nothing is stored at or beyond cap
+struct JoinExpand {
+  const uint32_t* order; const uint32_t* lo; const uint32_t* cnt; int64_t nl;
+  const uint64_t* out_base; const uint32_t* rrows; int32_t kind;
+  int64_t lbase, rbase; int64_t* left_rows; int64_t* right_rows; int64_t cap;
+};
+void launch_join_expand(hipStream_t s, const JoinExpand& E);
+
 // ---- the control words of unique / groupreduce: 128 bytes of device memory through which the kernels of k_unique.hip and k_radix.hip report to the host, which
 // reads every retry decision from them.  The host sets them with device memsets (all zero, then all ones where a field says so) and reads them back whole.
 // KeyAux is the head every form shares — all the radix kernels and the `special` pointers of AccArgs / RankArgs see —, UniqueAux what unique's table and dense

@@ -16,7 +16,7 @@ namespace dfdb {
 
 // the plain fixed-width projection column p of q, resident and decoded — or the refusal that names the form (`what`: "sorting by" / "gathering rows of").
 // strings: a plain String column is admitted too (its flat form: sizes, arena, tile offsets — a column with a dictionary keeps it) when its tiles are short enough
-static const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool strings = false) {
+const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool strings) {
   if (p < 0 || (size_t)p >= q->proj.size()) fail(DFDB_ERR_BOUNDS, "BoundsError: projection column %d", p);
   const Node& e = *q->proj[(size_t)p].expr;
   const bool str = dt_base(e.dtype) == DFDB_STRING;
@@ -297,6 +297,22 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
 
 void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
   query_sort_indices_n(q, &p, &flags, 1, limit, out, cap, memkind, n, info, false);
+}
+
+// The sorted pairs of the selected rows of q that are not missing in `col` — ascending, no cut, no limit: the build and the passes of the driver above,
+// without its plan and its emit — handed to the caller: `keys` / `rows` receive the half that won (npairs entries; equal keys in ascending row order, the sort
+// being stable), *nmiss the selected missing rows (they are not keyed), *passes the digit passes run.  col: a column of q's table that the caller has checked
+// (ordered_column; a table below 2^31 rows).  Everything else of the sort goes back to the pool here, the stream drained first; the selection is left as it was found
+void query_sorted_key_pairs(dfdb_query* q, const Column& col, DevBuf& keys, DevBuf& rows, int64_t* npairs, int64_t* nmiss, int64_t* passes) {
+  ensure_executed_checked(q);
+  const int64_t sel = query_count(q, -1);
+  *npairs = 0; *nmiss = 0; *passes = 0;
+  if (sel == 0) return;
+  SortScratch S(q->t->ctx);
+  SortPlan P; P.L = sel;                                    // no cut: every selected row that is not missing is kept
+  *npairs = sort_build_pairs(q, col, S, false, P, false, sel, nmiss);
+  const int cur = sort_run_passes(q->t->ctx, S, *npairs, *npairs, select_key_bits(dt_base(col.dtype), false) / 8, passes);
+  keys = std::move(S.keys[cur]); rows = std::move(S.rows[cur]);
 }
 
 // ---- the projection at given rows: a fixed-width column by one kernel; a String column (k_str_rows.hip) by the offsets of the gathered sizes, then the bytes -------

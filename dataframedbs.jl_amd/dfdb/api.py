@@ -912,6 +912,40 @@ class _Query:
 
         return self._columns_out(n, lambda outs, ncols: N.check(L.dfdb_gather_rows_any(self._h, ptr, n, kind, outs, ncols)), string_bytes)
 
+    def join_count(self, other: "_Query", col: int, other_col: int, kind: int = N.JOIN_INNER):
+        """dfdb_query_join: (npairs, info) of the join of this query's selected rows (the left side) with `other`'s on projection columns col / other_col;
+        info = (selected left rows, selected right rows, left rows with a missing key, right rows with a missing key, digit passes run on the right side).
+        The lists stay pending in this query until join_fetch; `other` is not needed for it"""
+        n = C.c_int64()
+        info = np.zeros(5, np.int64)
+        N.check(N.load().dfdb_query_join(self._h, int(col), other._h, int(other_col), int(kind), C.byref(n), info.ctypes.data))
+        return n.value, tuple(int(x) for x in info)
+
+    def join_fetch(self, npairs: int, dev_ptrs=None, want_right: bool = True):
+        """dfdb_query_join_fetch of the pending join: (left_rows, right_rows) as host arrays of npairs 1-based table rows (right_rows None unless wanted; 0 in
+        it: no match), or — dev_ptrs = (left pointer, right pointer or None), each holding npairs entries of device memory — written there: (None, None)"""
+        L = N.load()
+        if dev_ptrs is not None:
+            lp, rp = dev_ptrs
+            N.check(L.dfdb_query_join_fetch(self._h, C.c_void_p(lp), C.c_void_p(rp) if rp else None, int(npairs), N.MEM_DEVICE))
+            return None, None
+        lr = np.empty(npairs, np.int64)
+        rr = np.empty(npairs, np.int64) if want_right else None
+        N.check(L.dfdb_query_join_fetch(self._h, lr.ctypes.data if npairs else None, rr.ctypes.data if (want_right and npairs) else None, int(npairs), N.MEM_HOST))
+        return lr, rr
+
+    def join(self, other: "_Query", col: int, other_col: int, kind: int = N.JOIN_INNER, device: bool = False):
+        """both calls: (left_rows, right_rows, info) — two parallel lists of 1-based table rows ordered by left row, then by right row; right_rows[i] = 0: no
+        match.  device: the lists stay on the device, as two int64 tensors of the context's device (torch), ready for gather_rows_any(dev_ptr = ..)"""
+        n, info = self.join_count(other, col, other_col, kind)
+        if not device:
+            return self.join_fetch(n) + (info,)
+        import torch
+        dev = torch.device("cuda", self.view.table.ctx.device)
+        lt, rt = torch.empty(max(n, 1), dtype=torch.int64, device=dev), torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        self.join_fetch(n, (lt.data_ptr(), rt.data_ptr()))
+        return lt[:n], rt[:n], info
+
 
 class _ChunkQuery(_Query):
     """One chunk of a streamed view: the engine owns the handle (valid until the stream advances)."""
@@ -1387,6 +1421,85 @@ def take(v: Union[DFView, DFTable], rows):
     import pandas as pd
     lg = _logicals(v)
     return pd.DataFrame({k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(v.projection.keys(), v._query().gather_rows_any(rows)))})
+
+
+_JOIN_KINDS = {"inner": N.JOIN_INNER, "left": N.JOIN_LEFT, "semi": N.JOIN_SEMI, "anti": N.JOIN_ANTI}
+
+
+def _join_sides(v, w, on):
+    """(left view, right view, left key's projection column, right key's) of a join `on` a name or (left name, right name)"""
+    v = DFView(v) if isinstance(v, DFTable) else v
+    w = DFView(w) if isinstance(w, DFTable) else w
+    ln, rn = (on, on) if isinstance(on, str) else on
+    lnames, rnames = list(v.projection.keys()), list(w.projection.keys())
+    for name, names in ((ln, lnames), (rn, rnames)):
+        if name not in names:
+            raise KeyError(f"KeyError: column {name} not found")
+    return v, w, lnames.index(ln), rnames.index(rn)
+
+
+def _join_call(v, w, on, kind, matchmissing):
+    """call 1 of the join of two views: (left view, right view, left query, npairs, info, right key's column); matchmissing = "error" raises on a missing key"""
+    if kind not in _JOIN_KINDS:
+        raise ValueError(f"ArgumentError: join kind {kind!r} (inner, left, semi or anti)")
+    if matchmissing not in ("error", "notequal"):
+        raise ValueError(f"ArgumentError: matchmissing = {matchmissing!r} (error or notequal)")
+    v, w, lc, rc = _join_sides(v, w, on)
+    q = v._query()
+    n, info = q.join_count(w._query(), lc, rc, _JOIN_KINDS[kind])
+    if matchmissing == "error" and (info[2] or info[3]):      # (the pending lists stay until the query's next join or reset: its executed selection is kept)
+        raise ValueError(f"ArgumentError: missing values in the key column of the {'left' if info[2] else 'right'} side ({info[2]} left, {info[3]} right rows): "
+                         "pass matchmissing = \"notequal\" to let them match nothing")
+    return v, w, q, n, info, rc
+
+
+def join_rows(v, w, on, kind: str = "inner", matchmissing: str = "error"):
+    """The row lists of innerjoin / leftjoin / semijoin / antijoin of two views on one key column (dfdb_query_join): (left_rows, right_rows, info) — parallel
+    arrays of 1-based TABLE rows ordered by left row, then by right row; right_rows[i] = 0: no match (kind "left" and "anti").  `on`: a column name, or
+    (left name, right name).  Keys compare with isequal; matchmissing = "error" (DataFrames.jl's default) raises ValueError when a selected key is missing on
+    either side, "notequal" lets such a row match nothing.  info: (selected left rows, selected right rows, left / right rows with a missing key, digit passes)"""
+    _, _, q, n, info, _ = _join_call(v, w, on, kind, matchmissing)
+    return q.join_fetch(n) + (info,)
+
+
+def _join_frame(v, w, on, kind, matchmissing):
+    import pandas as pd
+    import torch
+    v, w, _, rc = _join_sides(v, w, on)
+    lnames, rnames = list(v.projection.keys()), list(w.projection.keys())
+    rkeep = [i for i in range(len(rnames)) if i != rc] if kind == "inner" else []
+    dup = [rnames[i] for i in rkeep if rnames[i] in lnames]
+    if dup:                                                   # (before anything runs, as DataFrames.jl checks its names)
+        raise ValueError(f"ArgumentError: Duplicate variable names: {', '.join(dup)}. Pass makeunique=true to make them unique")
+    v, w, q, n, info, rc = _join_call(v, w, on, kind, matchmissing)
+    dev = torch.device("cuda", v.table.ctx.device)
+    lt = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    rt = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if rkeep else None
+    q.join_fetch(n, (lt.data_ptr(), rt.data_ptr() if rkeep else None))
+    lg = _logicals(v)
+    cols = {k: _to_user(c, lg[i]) for i, (k, c) in enumerate(zip(lnames, q.gather_rows_any(dev_ptr=lt.data_ptr(), n=n)))}
+    if rkeep:
+        rg = _logicals(w)
+        rcols = w._query().gather_rows_any(dev_ptr=rt.data_ptr(), n=n)
+        cols.update({rnames[i]: _to_user(rcols[i], rg[i]) for i in rkeep})
+    return pd.DataFrame(cols)
+
+
+def innerjoin(v, w, on, matchmissing: str = "error"):
+    """innerjoin(materialize(v), materialize(w); on) as a DataFrame: the left view's columns, then the right view's without its key, one row per match, ordered
+    by left row then right row.  The row lists stay on the device (dfdb_query_join_fetch into device memory) and both sides are gathered from them with
+    dfdb_gather_rows_any.  A non-key name present on both sides is an ArgumentError (makeunique = false)"""
+    return _join_frame(v, w, on, "inner", matchmissing)
+
+
+def semijoin(v, w, on, matchmissing: str = "error"):
+    """semijoin: the left view's columns at its selected rows that have a match in `w`, in table order"""
+    return _join_frame(v, w, on, "semi", matchmissing)
+
+
+def antijoin(v, w, on, matchmissing: str = "error"):
+    """antijoin: the left view's columns at its selected rows that have no match in `w`, in table order"""
+    return _join_frame(v, w, on, "anti", matchmissing)
 
 
 def col_equal(a: DFColumn, b: DFColumn) -> bool:

@@ -510,6 +510,39 @@ int32_t dfdb_gather_rows_string_bytes(dfdb_query* q, int32_t i, const int64_t* r
  * one 1024-row tile of which holds 2^22 bytes or more (the byte total of 1024 outputs is kept in 32 bits and they may all name the longest row).  Every
  * argument and every column is checked before the first launch; the query's selection is left as it was found. */
 int32_t dfdb_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int32_t rows_memkind, dfdb_outcol* outs, int32_t ncols);
+/* Two views related on one key: the row lists of innerjoin / leftjoin / semijoin / antijoin (DataFrames.jl) of the selected rows of `left` and `right`.  The
+ * reference has no join — "several tables with possibility of joins" stands on its roadmap (docs/src/index.md:598) —; this is this library's completion, as
+ * dfdb_query_groupreduce is.  `left` and `right` are queries of the SAME context, over two tables or over one (a self-join; the same query twice too);
+ * left_col / right_col name one projection column each.  Two calls, as dfdb_query_groupreduce / _fetch; the state lives in `left`.
+ *   keys     compare with isequal: all NaNs are one key, -0.0 and 0.0 are two, integers by value (the select key of csrc/select_key.hpp).  A row whose key is
+ *            missing matches nothing, a missing key on the other side included (matchmissing = :notequal); the bytes under a missing bit are never read.  The
+ *            counts of such rows come back in info, so that a caller can raise instead (matchmissing = :error).
+ *   result   two parallel lists of 1-based table rows, each table's row_base included, as dfdb_sort_indices emits them; right_rows[i] = 0: no match.
+ *   order    by left row ascending (table order), and within one left row by right row ascending.  The answer is unique: it does not depend on grid size,
+ *            launch order or timing (no hash table, no atomics on the result path).
+ *   kind     DFDB_JOIN_INNER  one pair per match;
+ *            DFDB_JOIN_LEFT   the inner pairs, and (l, 0) in place for every selected left row without a match (a missing key is without a match);
+ *            DFDB_JOIN_SEMI   (l, its first matching right row) once per selected left row that has a match;
+ *            DFDB_JOIN_ANTI   (l, 0) per selected left row without a match.
+ *   dfdb_query_join   *npairs (may be NULL) receives the length of the lists; info [5] (may be NULL): selected left rows, selected right rows, selected left
+ *            rows whose key is missing, selected right rows whose key is missing (these never enter the sort), digit passes run on the right side.  On the
+ *            device (csrc/join.cpp, csrc/k_join.hip): the right side's selected non-missing keys sorted as dfdb_sort_indices sorts them, the selected left
+ *            rows laid ascending, one probe launch (per left row a binary search for its run of equal right keys), one scan.  What `left` keeps for the fetch
+ *            are copies — 12 bytes per selected left row, 4 per selected right row —: `right` may be reset or freed afterwards, and neither query's selection,
+ *            count or indices change.
+ *   dfdb_query_join_fetch   writes the lists (right_rows may be NULL) to host or device memory (memkind); it may be repeated.  cap < npairs is
+ *            DFDB_ERR_BOUNDS, a fetch without a pending join DFDB_ERR_ARGUMENT; in both cases neither output is touched.  The state is dropped — its device memory goes back to the
+ *            buffer pool — by dfdb_query_reset, dfdb_table_unload, dfdb_query_free and a dfdb_query_join on `left` that fails; the next successful
+ *            dfdb_query_join on `left` replaces it.
+ * Refusals, by name and before anything is launched.  DFDB_ERR_UNSUPPORTED: a String key; a computed key (materialise it as a column first:
+ * dfdb_table_add_from_query); a key that is not numeric or Bool; keys of different base dtypes (the message names both; the nullable flag may differ); a view that
+ * is out of core; a compressed-only key column; a table of 2^31 rows or more on either side (rows travel in 32 bits).  DFDB_ERR_ARGUMENT: an unknown `kind`,
+ * queries of two contexts.  DFDB_ERR_BOUNDS: a column the view does not have.  After the probe: DFDB_ERR_UNSUPPORTED when 1024 consecutive selected left rows
+ * have more than 2^32 - 1 pairs between them (their pairs are counted in 32 bits).  Tuple and String keys, the leftjoin frame (a gather that turns row 0 into
+ * missing), right and outer joins, and the out-of-core and sharded forms have no entry point yet. */
+enum { DFDB_JOIN_INNER = 0, DFDB_JOIN_LEFT = 1, DFDB_JOIN_SEMI = 2, DFDB_JOIN_ANTI = 3 };
+int32_t dfdb_query_join(dfdb_query* left, int32_t left_col, dfdb_query* right, int32_t right_col, int32_t kind, int64_t* npairs, int64_t* info);
+int32_t dfdb_query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* right_rows, int64_t cap, int32_t memkind);
 
 /* ---- out of core behind the ordinary entry points (round 6) ----
  * The reference never holds more than one block per column (src/io/blocksiterator.jl:98-121, src/io/BlockStreams.jl:9-15; "memory use is O(block)",
