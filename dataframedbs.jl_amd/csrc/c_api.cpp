@@ -543,6 +543,10 @@ int32_t dfdb_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int3
 int32_t dfdb_query_join(dfdb_query* left, int32_t left_col, dfdb_query* right, int32_t right_col, int32_t kind, int64_t* npairs, int64_t* info) {
   return guard([&] { NEEDQ(left); NEEDQ(right); query_join(left, left_col, right, right_col, kind, npairs, info); });
 }
+int32_t dfdb_query_join_n(dfdb_query* left, const int32_t* left_cols, dfdb_query* right, const int32_t* right_cols, int32_t nkeys, int32_t kind, int64_t* npairs,
+                          int64_t* info) {
+  return guard([&] { NEEDQ(left); NEEDQ(right); query_join_n(left, left_cols, right, right_cols, nkeys, kind, npairs, info); });
+}
 int32_t dfdb_query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* right_rows, int64_t cap, int32_t memkind) {
   return guard([&] { NEEDQ(left); query_join_fetch(left, left_rows, right_rows, cap, memkind); });
 }

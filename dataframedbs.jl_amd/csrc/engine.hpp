@@ -252,8 +252,12 @@ int select_keys(dfdb_query* q, const Column& col, bool full, bool count, int max
 void query_order_statistics(dfdb_query* q, int32_t p, const int64_t* ranks, int32_t nranks, int64_t* out_i, double* out_f, int64_t* counts);   // project.cpp over k_select.hip
 // sort.cpp over k_sort.hip: the stable sortperm of the selected rows by projection columns proj_cols[0] (major) .. [nkeys - 1]; one column p: its n = 1 case.
 // strings: String keys are admitted (dfdb_sort_indices_any) — else refused by name
+// sink: the driver emits nothing and hands out the order of ALL n selected rows on the device — ascending by the key tuple, a key's missing rows behind its
+// live ones, ties in ascending row order —, the digit passes it ran and, per String key, the chunks m its longest live string has and the in-tile offsets of
+// its column's rows that the driver built (launch_str_row_offsets; empty when the selection is) (see sort.cpp)
+struct SortOrderSink { DevBuf order; int64_t n = 0, passes = 0; int32_t str_chunks[DFDB_SORT_MAX_KEYS] = {}; DevBuf row_off[DFDB_SORT_MAX_KEYS]; };
 void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
-                          int64_t* n, int64_t* info, bool strings);
+                          int64_t* n, int64_t* info, bool strings, SortOrderSink* sink = nullptr);
 void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info);
 // the plain fixed-width projection column p of q, resident and decoded, or the refusal that names the form after `what` ("sorting by", "joining on")
 const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool strings = false);
@@ -261,6 +265,8 @@ const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool st
 void query_sorted_key_pairs(dfdb_query* q, const Column& col, DevBuf& keys, DevBuf& rows, int64_t* npairs, int64_t* nmiss, int64_t* passes);
 // join.cpp over k_join.hip: the row lists of a join of two selections on one fixed-width key (dfdb_query_join / _fetch)
 void query_join(dfdb_query* left, int32_t left_col, dfdb_query* right, int32_t right_col, int32_t kind, int64_t* npairs, int64_t* info);
+// the same on nkeys (1 .. DFDB_JOIN_MAX_KEYS) key columns per side, String keys among them (dfdb_query_join_n); the fetch is query_join_fetch
+void query_join_n(dfdb_query* left, const int32_t* left_cols, dfdb_query* right, const int32_t* right_cols, int32_t nkeys, int32_t kind, int64_t* npairs, int64_t* info);
 void query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* right_rows, int64_t cap, int32_t memkind);
 void query_join_drop(dfdb_query* q);              // a pending join's lists go back to the pool (dfdb_query_reset, dfdb_table_unload, a join that fails)
 // the projection at given rows (strings: String columns are admitted, k_str_rows.hip — else refused), and the string bytes projection column i needs at those rows

@@ -1,14 +1,17 @@
-// join_rule.hpp — the two rules of K14 (k_join.hip) that the host states too: how many pairs a left row emits from its match count, and the bounded lower-bound
-// search over the sorted right keys.  No HIP header is needed: tests/join_rule_main.cpp compiles this file with the host compiler and the sanitizers over heap
-// arrays of exactly nr keys, so one read at or beyond nr is caught there.
+// join_rule.hpp — the rules of K14 (k_join.hip) that the host states too: how many pairs a left row emits from its match count, the bounded lower-bound
+// search over the sorted right keys, and — the join on several keys — one refinement stage and a String key's chunk sub-key.  No HIP header is needed:
+// tests/join_rule_main.cpp and tests/join_refine_main.cpp compile this file with the host compiler and the sanitizers over heap arrays of exactly as many
+// keys as a search may read, so one read beyond them is caught there.
 #pragma once
 #include <cstdint>
 #include "../../include/dfdb.h"
 
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
 #define DFDB_JOIN_HD __host__ __device__ __forceinline__
+#define DFDB_JOIN_UNROLL _Pragma("unroll")
 #else
 #define DFDB_JOIN_HD inline
+#define DFDB_JOIN_UNROLL
 #endif
 
 namespace dfdb {
@@ -55,6 +58,49 @@ template <bool LE> DFDB_JOIN_HD uint32_t join_bound(const uint64_t* keys, uint32
     if (i >= 0 && join_step_take<LE>(keys[i], x)) pos = (uint32_t)i + 1u;
   }
   return pos;
+}
+
+// ---- the join on several keys (dfdb_query_join_n): one REFINEMENT STAGE per 8-byte sub-key, the major one first ------------------------------------------
+// Every left entry carries a run [lo, lo + cnt) of the right side's rows in tuple order, on which every sub-key before this stage's equals the entry's own —
+// so this stage's sub-keys rsub[lo .. lo + cnt) are ascending.  With x the entry's sub-key, a = #{rsub < x} and z = #{rsub <= x} within the run:
+//   (lo, cnt, x) -> (lo + a, z - a)
+// N entries IN LOCK STEP: a step issues the 2 N loads of all their searches before any is used.  steps: any count >= the bit length of the largest cnt (more
+// steps read nothing more: join_step_index refuses a candidate beyond cnt).  An entry with cnt = 0 reads nothing and stays (lo, 0).  No index at or beyond
+// lo + cnt is read.  The kernel (k_join_refine, N = 8) and the host test (tests/join_refine_main.cpp, over arrays of exactly cnt keys) run this text
+template <int N> DFDB_JOIN_HD void join_refine_stage(const uint64_t* rsub, uint32_t* lo, uint32_t* cnt, const uint64_t* x, int steps) {
+  uint32_t a[N], z[N];
+  DFDB_JOIN_UNROLL
+  for (int j = 0; j < N; j++) { a[j] = 0; z[j] = 0; }
+  for (int b = steps - 1; b >= 0; b--) {
+    uint64_t ka[N], kz[N];
+    DFDB_JOIN_UNROLL
+    for (int j = 0; j < N; j++) {                  // the step's 2 N loads
+      const int64_t ia = join_step_index(a[j], b, cnt[j]), iz = join_step_index(z[j], b, cnt[j]);
+      ka[j] = 0; kz[j] = 0;
+      if (ia >= 0) ka[j] = rsub[(uint64_t)lo[j] + (uint64_t)ia];
+      if (iz >= 0) kz[j] = rsub[(uint64_t)lo[j] + (uint64_t)iz];
+    }
+    DFDB_JOIN_UNROLL
+    for (int j = 0; j < N; j++) {
+      const int64_t ia = join_step_index(a[j], b, cnt[j]), iz = join_step_index(z[j], b, cnt[j]);
+      if (ia >= 0 && join_step_take<false>(ka[j], x[j])) a[j] = (uint32_t)ia + 1u;
+      if (iz >= 0 && join_step_take<true>(kz[j], x[j])) z[j] = (uint32_t)iz + 1u;
+    }
+  }
+  DFDB_JOIN_UNROLL
+  for (int j = 0; j < N; j++) { lo[j] += a[j]; cnt[j] = z[j] - a[j]; }
+}
+
+// A String key is the sub-keys (chunk_0, .., chunk_{m-1}, length): chunk_c = the string's bytes [8 c, 8 c + 8) read big-endian, zero beyond its end.
+//   join_chunk_reaches  whether a string of `len` bytes has a byte in chunk c (else its sub-key is 0 and nothing is loaded)
+//   join_chunk_key      the sub-key from `raw`, the 8 bytes at the chunk's first byte loaded little-endian (the load may look up to 7 bytes past the string:
+//                       the arenas are padded), and rem = len - 8 c >= 1, the string's bytes from there on: the bytes behind its end are masked away
+// (k_sort.hip's k_sort_strkey states the same rule in its own text)
+DFDB_JOIN_HD bool join_chunk_reaches(uint32_t len, uint32_t chunk) { return (uint64_t)len > 8ull * chunk; }
+DFDB_JOIN_HD uint64_t join_chunk_key(uint64_t raw, uint32_t rem) {
+  uint64_t k = __builtin_bswap64(raw);               // the first byte of the chunk becomes the key's top byte
+  if (rem - 1u < 7u) k &= ~0ull << (8u * (8u - rem));
+  return k;
 }
 
 }  // namespace dfdb

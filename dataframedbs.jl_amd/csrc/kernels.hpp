@@ -304,6 +304,41 @@ struct JoinExpand {
 };
 void launch_join_expand(hipStream_t s, const JoinExpand& E);
 
+// ---- K14c: the join on several keys, String keys among them (dfdb_query_join_n; k_join.hip; the rules: join_rule.hpp) -----------------------------
+// Which entries of a row order have a missing component: per NULLABLE key one of a missing bitmap (a fixed-width column) or the sizes of a String column
+// (negative: missing); keys that cannot be missing are not listed.  The bytes under a missing row are never read
+constexpr int kJoinMaxKeys = 8;
+struct JoinKeyMiss { const uint64_t* missing[kJoinMaxKeys]; const int32_t* sizes[kJoinMaxKeys]; int32_t n; };
+// One walk over order[0 .. n) (0-based rows; a row that is not < nrows counts as missing: a guard), one wave per 1024 entries, in three modes:
+//   COUNT  live_cnt[tile] = the tile's entries without a missing component
+//   PLACE  those entries' rows, in the order of `order`, to out[live_base[tile] + rank in the tile]  (live_base: launch_scan_counts of live_cnt; nothing at or
+//          beyond cap)
+//   START  the left side's first ranges: lo[i] = 0 and cnt[i] = nr for such an entry, cnt[i] = 0 for every other one and for the entries of the last tile at or
+//          beyond n (lo and cnt hold tiles * 1024 entries); *nmiss (zeroed) += the entries below n with a missing component, each once
+enum JoinLiveMode : int { JOIN_LIVE_COUNT = 0, JOIN_LIVE_PLACE = 1, JOIN_LIVE_START = 2 };
+struct JoinLive {
+  const uint32_t* order; int64_t n; int64_t nrows; JoinKeyMiss keys;
+  uint32_t* live_cnt; const uint64_t* live_base; uint32_t* out; int64_t cap;
+  uint32_t* lo; uint32_t* cnt; uint32_t nr; unsigned long long* nmiss;
+  uint32_t* grp_total; uint32_t emit0;               // START, not null (no stage follows: nr = 0): grp_total[tile] = the tile's entries below n times emit0
+};
+void launch_join_live(hipStream_t s, const JoinLive& L, JoinLiveMode mode);
+// One refinement stage (join_rule.hpp join_refine_stage): entry i < nl with cnt[i] > 0 loads x, the sub-key of left row order[i], and narrows its run of
+// rsub — the stage's sub-keys of the right rows in tuple order — to the sub-keys equal to x: lo[i] += #{< x}, cnt[i] = #{= x} within [lo, lo + cnt).  An entry
+// with cnt = 0 and every entry at or beyond nl writes cnt = 0; a wave whose 1024 entries all have cnt = 0 loads no key and takes no step; the step count is
+// the bit length of the wave's largest cnt.  last: grp_total[g] = the sum of join_emitted(kind, cnt) over the group's entries below nl, and a sum of 2^32 or
+// more raises *flag — as the probe leaves them.  The left sub-key: a fixed-width column's select key, or (JoinStrSub) a String column's chunk / length
+// (chunk < 0) through its sizes, in-tile offsets (launch_str_row_offsets) and tile offsets
+struct JoinRefine {
+  const uint32_t* order; int64_t nl; int64_t nrows;
+  const uint64_t* rsub;
+  uint32_t* lo; uint32_t* cnt;
+  int32_t last, kind; uint32_t* grp_total; uint32_t* flag;
+};
+struct JoinStrSub { StrSide col; const uint32_t* row_off; int32_t chunk; };
+void launch_join_refine(hipStream_t s, const ColRef& col, const JoinRefine& P);
+void launch_join_refine_str(hipStream_t s, const JoinStrSub& K, const JoinRefine& P);
+
 // ---- the control words of unique / groupreduce: 128 bytes of device memory through which the kernels of k_unique.hip and k_radix.hip report to the host, which
 // reads every retry decision from them.  The host sets them with device memsets (all zero, then all ones where a field says so) and reads them back whole.
 // KeyAux is the head every form shares — all the radix kernels and the `special` pointers of AccArgs / RankArgs see —, UniqueAux what unique's table and dense

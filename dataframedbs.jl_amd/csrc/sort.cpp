@@ -177,9 +177,11 @@ static void sort_emit_rows(dfdb_table* t, SortScratch& S, const uint32_t* first,
 // by what is kept, where several keys sort every selected row and the limit only cuts what comes back.
 // strings (dfdb_sort_indices_any): a key may be a plain String column.  It IS m + 1 keys of this driver — (chunk_0, .., chunk_{m-1}, length), 8 key bytes each,
 // the length first (k_sort_strkey) — over row_off built once for the key; m is known when the length has been keyed.  A call with a String key takes the
-// several-keys plan whatever nkeys is, and a String key that is the most minor one starts from the selected rows laid ascending into S.order
+// several-keys plan whatever nkeys is, and a String key that is the most minor one starts from the selected rows laid ascending into S.order.
+// sink (the join on several keys): nothing is emitted; the last key's two lists are laid into one order of ALL selected rows, which leaves with the sink
+// together with every String key's m and its column's in-tile offsets.  Such a call takes the several-keys plan too (no cut); what the public entry points answer does not pass through it
 void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t* flags, int32_t nkeys, int64_t limit, int64_t* out, int64_t cap, int32_t memkind,
-                          int64_t* n, int64_t* info, bool strings) {
+                          int64_t* n, int64_t* info, bool strings, SortOrderSink* sink) {
   if (nkeys < 1 || nkeys > DFDB_SORT_MAX_KEYS) fail(DFDB_ERR_ARGUMENT, "ArgumentError: %d sort keys (1 to %d)", nkeys, (int)DFDB_SORT_MAX_KEYS);
   if (!proj_cols || !flags) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no sort %s", proj_cols ? "flags" : "columns");
   for (int32_t j = 0; j < nkeys; j++) check_sort_flags(flags[j]);
@@ -198,7 +200,8 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
   if (m > 0 && !out) fail(DFDB_ERR_ARGUMENT, "ArgumentError: no output buffer");
   // nothing to do: one key with nothing to return (limit = 0 too: the cut would keep no pair); several keys sort whatever the limit is and report that sort
   // in info, so only an empty selection ends them here
-  const bool one = nkeys == 1 && !any_str;
+  const bool one = nkeys == 1 && !any_str && !sink;
+  if (sink) { sink->n = 0; sink->passes = 0; for (int32_t j = 0; j < nkeys; j++) sink->str_chunks[j] = 0; }
   if (one ? total == 0 : sel == 0) { if (info) memcpy(info, inf, sizeof inf); return; }
 
   SortScratch S(ctx);
@@ -261,8 +264,10 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
                  col.name.c_str(), (unsigned long long)longest, (int)DFDB_SORT_MAX_STRING_BYTES);
           nchunks = (int64_t)(longest + 7) / 8;
           inf[3] += 8 * nchunks;
+          if (sink) sink->str_chunks[j] = (int32_t)nchunks;
         }
       }
+      if (sink) sink->row_off[j] = std::move(S.row_off);      // the key's in-tile offsets leave with the sink (the next String key builds its own)
       continue;
     }
     const int nbits = select_key_bits(dt_base(col.dtype), false), nbytes = nbits / 8;
@@ -289,6 +294,12 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
     const int cur = sort_run_passes(ctx, S, npairs, one ? npairs : sel, nbytes, &run);
     key_done(cur, rev, npairs, nmiss, run);
   }
+  if (sink) {                                               // the order of every selected row, handed out instead of emitted
+    lay_order();
+    sink->order = std::move(S.order); sink->n = sel; sink->passes = inf[2];
+    if (info) memcpy(info, inf, sizeof inf);
+    return;
+  }
   // the first m of the two lists (a cut keeps every pair up to the cut key: no fewer than the limit takes of the live rows)
   const int64_t first_n = std::min(m, first_len);
   sort_emit_rows(t, S, first, first_n, second, m - first_n, out, memkind);
@@ -296,7 +307,7 @@ void query_sort_indices_n(dfdb_query* q, const int32_t* proj_cols, const int32_t
 }
 
 void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, int64_t* out, int64_t cap, int32_t memkind, int64_t* n, int64_t* info) {
-  query_sort_indices_n(q, &p, &flags, 1, limit, out, cap, memkind, n, info, false);
+  query_sort_indices_n(q, &p, &flags, 1, limit, out, cap, memkind, n, info, false, nullptr);
 }
 
 // The sorted pairs of the selected rows of q that are not missing in `col` — ascending, no cut, no limit: the build and the passes of the driver above,

@@ -20,6 +20,7 @@ SORT_REV = 1
 SORT_MAX_KEYS = 8
 SORT_MAX_STRING_BYTES = 256
 JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
+JOIN_MAX_KEYS = 8
 
 
 class DfdbError(RuntimeError):
@@ -60,7 +61,7 @@ SYMBOLS = [
     "dfdb_query_add_predicate", "dfdb_query_nstages", "dfdb_query_set_projection", "dfdb_query_ncols", "dfdb_query_coltype",
     "dfdb_expr_result_type", "dfdb_expr_result_logical", "dfdb_query_set_stage_base", "dfdb_query_count_prefix",
     "dfdb_query_execute", "dfdb_query_reset", "dfdb_count", "dfdb_count_to", "dfdb_select_bitmap", "dfdb_select_indices", "dfdb_result_string_bytes",
-    "dfdb_materialize", "dfdb_aggregate", "dfdb_order_statistics", "dfdb_sort_indices", "dfdb_sort_indices_n", "dfdb_sort_indices_any", "dfdb_gather_rows", "dfdb_gather_rows_string_bytes", "dfdb_gather_rows_any", "dfdb_query_join", "dfdb_query_join_fetch", "dfdb_query_prepare", "dfdb_table_unload", "dfdb_query_read_stats",
+    "dfdb_materialize", "dfdb_aggregate", "dfdb_order_statistics", "dfdb_sort_indices", "dfdb_sort_indices_n", "dfdb_sort_indices_any", "dfdb_gather_rows", "dfdb_gather_rows_string_bytes", "dfdb_gather_rows_any", "dfdb_query_join", "dfdb_query_join_n", "dfdb_query_join_fetch", "dfdb_query_prepare", "dfdb_table_unload", "dfdb_query_read_stats",
     # multi-GPU groups (block-range shards + RCCL)
     "dfdb_group_create", "dfdb_group_unique_id", "dfdb_group_create_rank", "dfdb_group_create_rank_callbacks", "dfdb_group_destroy", "dfdb_group_info", "dfdb_group_ctx",
     "dfdb_group_synchronize", "dfdb_group_barrier", "dfdb_group_set_option", "dfdb_group_allreduce_f64",
@@ -130,6 +131,7 @@ def load() -> C.CDLL:
         lib.dfdb_gather_rows_string_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         lib.dfdb_gather_rows_any.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(OutCol), C.c_int32]
         lib.dfdb_query_join.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.dfdb_query_join_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         lib.dfdb_query_join_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
         lib.dfdb_query_prepare.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         lib.dfdb_table_unload.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]

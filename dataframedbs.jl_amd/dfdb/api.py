@@ -921,6 +921,18 @@ class _Query:
         N.check(N.load().dfdb_query_join(self._h, int(col), other._h, int(other_col), int(kind), C.byref(n), info.ctypes.data))
         return n.value, tuple(int(x) for x in info)
 
+    def join_count_n(self, other: "_Query", cols, other_cols, kind: int = N.JOIN_INNER):
+        """dfdb_query_join_n: join_count on several key columns per side (projection columns, the major key first; String keys are admitted); info =
+        (selected left rows, selected right rows, left / right rows with a missing component, digit passes run on the right side, sub-keys refined).
+        The lists stay pending in this query until join_fetch"""
+        lc, rc = np.ascontiguousarray(cols, np.int32), np.ascontiguousarray(other_cols, np.int32)
+        if lc.ndim != 1 or lc.shape != rc.shape:
+            raise ValueError(f"ArgumentError: {lc.size} left and {rc.size} right key columns")
+        n = C.c_int64()
+        info = np.zeros(6, np.int64)
+        N.check(N.load().dfdb_query_join_n(self._h, lc.ctypes.data, other._h, rc.ctypes.data, int(lc.size), int(kind), C.byref(n), info.ctypes.data))
+        return n.value, tuple(int(x) for x in info)
+
     def join_fetch(self, npairs: int, dev_ptrs=None, want_right: bool = True):
         """dfdb_query_join_fetch of the pending join: (left_rows, right_rows) as host arrays of npairs 1-based table rows (right_rows None unless wanted; 0 in
         it: no match), or — dev_ptrs = (left pointer, right pointer or None), each holding npairs entries of device memory — written there: (None, None)"""
@@ -934,10 +946,11 @@ class _Query:
         N.check(L.dfdb_query_join_fetch(self._h, lr.ctypes.data if npairs else None, rr.ctypes.data if (want_right and npairs) else None, int(npairs), N.MEM_HOST))
         return lr, rr
 
-    def join(self, other: "_Query", col: int, other_col: int, kind: int = N.JOIN_INNER, device: bool = False):
+    def join(self, other: "_Query", col, other_col, kind: int = N.JOIN_INNER, device: bool = False):
         """both calls: (left_rows, right_rows, info) — two parallel lists of 1-based table rows ordered by left row, then by right row; right_rows[i] = 0: no
-        match.  device: the lists stay on the device, as two int64 tensors of the context's device (torch), ready for gather_rows_any(dev_ptr = ..)"""
-        n, info = self.join_count(other, col, other_col, kind)
+        match.  col / other_col: one projection column each (dfdb_query_join) or two lists of them (dfdb_query_join_n: several keys, String keys).
+        device: the lists stay on the device, as two int64 tensors of the context's device (torch), ready for gather_rows_any(dev_ptr = ..)"""
+        n, info = self.join_count(other, col, other_col, kind) if isinstance(col, (int, np.integer)) else self.join_count_n(other, col, other_col, kind)
         if not device:
             return self.join_fetch(n) + (info,)
         import torch
@@ -1427,37 +1440,53 @@ _JOIN_KINDS = {"inner": N.JOIN_INNER, "left": N.JOIN_LEFT, "semi": N.JOIN_SEMI, 
 
 
 def _join_sides(v, w, on):
-    """(left view, right view, left key's projection column, right key's) of a join `on` a name or (left name, right name)"""
+    """(left view, right view, the left keys' projection columns, the right keys') of a join `on` a name, a (left name, right name) pair, or a list of either"""
     v = DFView(v) if isinstance(v, DFTable) else v
     w = DFView(w) if isinstance(w, DFTable) else w
-    ln, rn = (on, on) if isinstance(on, str) else on
+    pairs = [(o, o) if isinstance(o, str) else tuple(o) for o in (on if isinstance(on, list) else [on])]
+    if not pairs or any(len(p) != 2 for p in pairs):
+        raise ValueError(f"ArgumentError: on = {on!r} (a column name, a (left name, right name) pair, or a list of them)")
     lnames, rnames = list(v.projection.keys()), list(w.projection.keys())
-    for name, names in ((ln, lnames), (rn, rnames)):
-        if name not in names:
-            raise KeyError(f"KeyError: column {name} not found")
-    return v, w, lnames.index(ln), rnames.index(rn)
+    for ln, rn in pairs:
+        for name, names in ((ln, lnames), (rn, rnames)):
+            if name not in names:
+                raise KeyError(f"KeyError: column {name} not found")
+    return v, w, [lnames.index(ln) for ln, _ in pairs], [rnames.index(rn) for _, rn in pairs]
+
+
+def _join_single(v, w, lc, rc):
+    """whether the join takes dfdb_query_join: one key, fixed-width on both sides (a String key and several keys take dfdb_query_join_n)"""
+    if len(lc) != 1:
+        return False
+    q, p = v._query(), w._query()
+    return (q.coltype(lc[0]) & ~ir.NULLABLE) != ir.STRING and (p.coltype(rc[0]) & ~ir.NULLABLE) != ir.STRING
 
 
 def _join_call(v, w, on, kind, matchmissing):
-    """call 1 of the join of two views: (left view, right view, left query, npairs, info, right key's column); matchmissing = "error" raises on a missing key"""
+    """call 1 of the join of two views: (left view, right view, left query, npairs, info, the right keys' columns); matchmissing = "error" raises on a missing key"""
     if kind not in _JOIN_KINDS:
         raise ValueError(f"ArgumentError: join kind {kind!r} (inner, left, semi or anti)")
     if matchmissing not in ("error", "notequal"):
         raise ValueError(f"ArgumentError: matchmissing = {matchmissing!r} (error or notequal)")
     v, w, lc, rc = _join_sides(v, w, on)
     q = v._query()
-    n, info = q.join_count(w._query(), lc, rc, _JOIN_KINDS[kind])
+    if _join_single(v, w, lc, rc):
+        n, info = q.join_count(w._query(), lc[0], rc[0], _JOIN_KINDS[kind])
+    else:
+        n, info = q.join_count_n(w._query(), lc, rc, _JOIN_KINDS[kind])
     if matchmissing == "error" and (info[2] or info[3]):      # (the pending lists stay until the query's next join or reset: its executed selection is kept)
-        raise ValueError(f"ArgumentError: missing values in the key column of the {'left' if info[2] else 'right'} side ({info[2]} left, {info[3]} right rows): "
+        raise ValueError(f"ArgumentError: missing values in the key column{'s' if len(lc) > 1 else ''} of the {'left' if info[2] else 'right'} side ({info[2]} left, {info[3]} right rows): "
                          "pass matchmissing = \"notequal\" to let them match nothing")
     return v, w, q, n, info, rc
 
 
 def join_rows(v, w, on, kind: str = "inner", matchmissing: str = "error"):
-    """The row lists of innerjoin / leftjoin / semijoin / antijoin of two views on one key column (dfdb_query_join): (left_rows, right_rows, info) — parallel
-    arrays of 1-based TABLE rows ordered by left row, then by right row; right_rows[i] = 0: no match (kind "left" and "anti").  `on`: a column name, or
-    (left name, right name).  Keys compare with isequal; matchmissing = "error" (DataFrames.jl's default) raises ValueError when a selected key is missing on
-    either side, "notequal" lets such a row match nothing.  info: (selected left rows, selected right rows, left / right rows with a missing key, digit passes)"""
+    """The row lists of innerjoin / leftjoin / semijoin / antijoin of two views (dfdb_query_join; several keys or a String key: dfdb_query_join_n):
+    (left_rows, right_rows, info) — parallel arrays of 1-based TABLE rows ordered by left row, then by right row; right_rows[i] = 0: no match (kind "left" and
+    "anti").  `on`: a column name, a (left name, right name) pair, or a list of either (the major key first).  Keys compare with isequal; matchmissing = "error" (DataFrames.jl's default) raises ValueError when a selected key is missing on
+    either side, "notequal" lets such a row match nothing.  info: (selected left rows, selected right rows, left / right rows with a missing key, digit passes)
+    for a single fixed-width key; with several keys or a String key those five — a row with ANY component missing counted once — and a sixth, the 8-byte
+    sub-keys refined (dfdb_query_join_n's info[6])"""
     _, _, q, n, info, _ = _join_call(v, w, on, kind, matchmissing)
     return q.join_fetch(n) + (info,)
 
@@ -1467,7 +1496,7 @@ def _join_frame(v, w, on, kind, matchmissing):
     import torch
     v, w, _, rc = _join_sides(v, w, on)
     lnames, rnames = list(v.projection.keys()), list(w.projection.keys())
-    rkeep = [i for i in range(len(rnames)) if i != rc] if kind == "inner" else []
+    rkeep = [i for i in range(len(rnames)) if i not in rc] if kind == "inner" else []
     dup = [rnames[i] for i in rkeep if rnames[i] in lnames]
     if dup:                                                   # (before anything runs, as DataFrames.jl checks its names)
         raise ValueError(f"ArgumentError: Duplicate variable names: {', '.join(dup)}. Pass makeunique=true to make them unique")
@@ -1486,7 +1515,7 @@ def _join_frame(v, w, on, kind, matchmissing):
 
 
 def innerjoin(v, w, on, matchmissing: str = "error"):
-    """innerjoin(materialize(v), materialize(w); on) as a DataFrame: the left view's columns, then the right view's without its key, one row per match, ordered
+    """innerjoin(materialize(v), materialize(w); on) as a DataFrame: the left view's columns, then the right view's without its key columns, one row per match, ordered
     by left row then right row.  The row lists stay on the device (dfdb_query_join_fetch into device memory) and both sides are gathered from them with
     dfdb_gather_rows_any.  A non-key name present on both sides is an ArgumentError (makeunique = false)"""
     return _join_frame(v, w, on, "inner", matchmissing)

@@ -538,11 +538,36 @@ int32_t dfdb_gather_rows_any(dfdb_query* q, const int64_t* rows, int64_t n, int3
  * dfdb_table_add_from_query); a key that is not numeric or Bool; keys of different base dtypes (the message names both; the nullable flag may differ); a view that
  * is out of core; a compressed-only key column; a table of 2^31 rows or more on either side (rows travel in 32 bits).  DFDB_ERR_ARGUMENT: an unknown `kind`,
  * queries of two contexts.  DFDB_ERR_BOUNDS: a column the view does not have.  After the probe: DFDB_ERR_UNSUPPORTED when 1024 consecutive selected left rows
- * have more than 2^32 - 1 pairs between them (their pairs are counted in 32 bits).  Tuple and String keys, the leftjoin frame (a gather that turns row 0 into
- * missing), right and outer joins, and the out-of-core and sharded forms have no entry point yet. */
+ * have more than 2^32 - 1 pairs between them (their pairs are counted in 32 bits).  Several keys and String keys: dfdb_query_join_n below.  The leftjoin frame
+ * (a gather that turns row 0 into missing), right and outer joins, and the out-of-core, sharded and compressed-only forms have no entry point yet (DESIGN.md
+ * section 10). */
 enum { DFDB_JOIN_INNER = 0, DFDB_JOIN_LEFT = 1, DFDB_JOIN_SEMI = 2, DFDB_JOIN_ANTI = 3 };
 int32_t dfdb_query_join(dfdb_query* left, int32_t left_col, dfdb_query* right, int32_t right_col, int32_t kind, int64_t* npairs, int64_t* info);
 int32_t dfdb_query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* right_rows, int64_t cap, int32_t memkind);
+/* The same join on SEVERAL key columns, String keys among them: innerjoin(a, b, on = [:k1, :k2]) and on = :brand.  left_cols[j] / right_cols[j] (nkeys of
+ * each, 1 .. DFDB_JOIN_MAX_KEYS) name projection columns; key j of the left is compared with key j of the right, key 0 is the major key; a column may appear
+ * twice.  A key is a plain fixed-width column (numeric or Bool) or a plain String column (a column with a dictionary included); the two sides of a key have the
+ * same base dtype (the nullable flag may differ; String pairs only with String).  The fetch is dfdb_query_join_fetch: this call leaves the pending state in
+ * `left` that dfdb_query_join leaves, and drops, replaces and keeps it by the same rules.
+ *   keys     two rows match when EVERY component is isequal: a fixed-width component by its select key (all NaNs one key, -0.0 and 0.0 two), a String by its
+ *            bytes and its length ("a" and "a\0" differ; the empty string is a key and matches the empty string).  A row with ANY component missing matches
+ *            nothing (matchmissing = :notequal).  Kinds, order, row bases and the 0 for "no match": dfdb_query_join's.
+ *   info [6] (may be NULL): selected left rows; selected right rows; selected left rows with at least one missing component (each counted once); the same
+ *            for the right side; digit passes run on the right side; sub-keys refined — a fixed-width key is 1, a String key m + 1 with m the 8-byte chunks of
+ *            the right side's longest selected live string (0 when no right row is live or no left row is selected).
+ *   device   (csrc/join.cpp, csrc/k_join.hip) the right side's selected rows ordered by the key tuple as dfdb_sort_indices_any orders them, the rows with a
+ *            missing component dropped from that order; every selected left row starts at the whole run of right rows and one k_join_refine launch per
+ *            sub-key — the major key first; a String key: its chunks, then its length — narrows its run to the rows equal in that sub-key by a bounded binary
+ *            search; then the scan.  No hash table, no atomics on the result path: the answer does not depend on grid size, launch order or timing.
+ * Refusals, by name and before anything is launched, nothing left pending and no output touched: everything dfdb_query_join refuses except a String key (base
+ * dtypes that differ: the message names the key position and both types); DFDB_ERR_ARGUMENT: nkeys outside 1 .. DFDB_JOIN_MAX_KEYS, a null column list.  After
+ * the right side's sort: DFDB_ERR_UNSUPPORTED, with dfdb_sort_indices_any's message, when a selected right String holds more than DFDB_SORT_MAX_STRING_BYTES
+ * bytes; a LEFT String of any length is not refused — it cannot match.  After the last stage: the 2^32 - 1 pairs per 1024 consecutive left rows rule.
+ * dfdb_query_join keeps its own path (one probe launch) and its own refusals.  The leftjoin frame, right and outer joins, and the out-of-core, sharded and
+ * compressed-only forms have no entry point yet. */
+enum { DFDB_JOIN_MAX_KEYS = 8 };
+int32_t dfdb_query_join_n(dfdb_query* left, const int32_t* left_cols, dfdb_query* right, const int32_t* right_cols, int32_t nkeys, int32_t kind, int64_t* npairs,
+                          int64_t* info /* [6] */);
 
 /* ---- out of core behind the ordinary entry points (round 6) ----
  * The reference never holds more than one block per column (src/io/blocksiterator.jl:98-121, src/io/BlockStreams.jl:9-15; "memory use is O(block)",
