@@ -183,8 +183,8 @@ struct dfdb_query {
   // records its one key, operator and kind here too
   int gr_multi = 0;
   std::vector<int32_t> gr_keys_n; std::vector<int> gr_ops_n, gr_kinds_n;
-  // dfdb_query_join (join.cpp): what the fetch needs, all of it copies — the selected left rows ascending (jn_order), per left row the first equal right key
-  // and their number (jn_lo, jn_cnt), where each 1024-entry group's pairs start (jn_base), the right rows in key order (jn_rrows), both row bases
+  // dfdb_query_join / dfdb_query_join_n (join.cpp's one driver, whichever plan matched): what the fetch needs, all of it copies — the selected left rows ascending
+  // (jn_order), per left row the first equal right key and their number (jn_lo, jn_cnt), where each 1024-entry group's pairs start (jn_base), the right rows in key order (jn_rrows), both row bases
   dfdb::DevBuf jn_order, jn_lo, jn_cnt, jn_base, jn_rrows;
   int64_t jn_nl = 0, jn_npairs = 0, jn_lbase = 0, jn_rbase = 0; int jn_kind = 0; bool jn_pending = false;
   int mask_from = -1;          // table ordinal of the column whose calibrated bitmap this query has borrowed (-1: its own)
@@ -263,9 +263,9 @@ void query_sort_indices(dfdb_query* q, int32_t p, int32_t flags, int64_t limit, 
 const Column& ordered_column(dfdb_query* q, int32_t p, const char* what, bool strings = false);
 // the sorted {select key, row} pairs of q's selected rows that are not missing in `col`, a column the caller checked with ordered_column (ascending; see sort.cpp)
 void query_sorted_key_pairs(dfdb_query* q, const Column& col, DevBuf& keys, DevBuf& rows, int64_t* npairs, int64_t* nmiss, int64_t* passes);
-// join.cpp over k_join.hip: the row lists of a join of two selections on one fixed-width key (dfdb_query_join / _fetch)
+// join.cpp over k_join.hip, two entry points of ONE driver: the join of two selections on one fixed-width key, matched by one probe launch (dfdb_query_join)
 void query_join(dfdb_query* left, int32_t left_col, dfdb_query* right, int32_t right_col, int32_t kind, int64_t* npairs, int64_t* info);
-// the same on nkeys (1 .. DFDB_JOIN_MAX_KEYS) key columns per side, String keys among them (dfdb_query_join_n); the fetch is query_join_fetch
+// and on nkeys (1 .. DFDB_JOIN_MAX_KEYS) key columns per side, String keys among them, matched by one refinement stage per sub-key (dfdb_query_join_n); one fetch for both
 void query_join_n(dfdb_query* left, const int32_t* left_cols, dfdb_query* right, const int32_t* right_cols, int32_t nkeys, int32_t kind, int64_t* npairs, int64_t* info);
 void query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* right_rows, int64_t cap, int32_t memkind);
 void query_join_drop(dfdb_query* q);              // a pending join's lists go back to the pool (dfdb_query_reset, dfdb_table_unload, a join that fails)

@@ -563,7 +563,7 @@ int32_t dfdb_query_join_fetch(dfdb_query* left, int64_t* left_rows, int64_t* rig
  * dtypes that differ: the message names the key position and both types); DFDB_ERR_ARGUMENT: nkeys outside 1 .. DFDB_JOIN_MAX_KEYS, a null column list.  After
  * the right side's sort: DFDB_ERR_UNSUPPORTED, with dfdb_sort_indices_any's message, when a selected right String holds more than DFDB_SORT_MAX_STRING_BYTES
  * bytes; a LEFT String of any length is not refused — it cannot match.  After the last stage: the 2^32 - 1 pairs per 1024 consecutive left rows rule.
- * dfdb_query_join keeps its own path (one probe launch) and its own refusals.  The leftjoin frame, right and outer joins, and the out-of-core, sharded and
+ * dfdb_query_join keeps its own match step (one probe launch) and its own message for a type mismatch; the rest of call 1 is shared.  The leftjoin frame, right and outer joins, and the out-of-core, sharded and
  * compressed-only forms have no entry point yet. */
 enum { DFDB_JOIN_MAX_KEYS = 8 };
 int32_t dfdb_query_join_n(dfdb_query* left, const int32_t* left_cols, dfdb_query* right, const int32_t* right_cols, int32_t nkeys, int32_t kind, int64_t* npairs,
